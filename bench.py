@@ -10,7 +10,13 @@ data-path collective except the all-gather of the CLIP vectors (for the FAISS in
     python bench.py                       # 1 GPU
     python bench.py --gpus 4              # self-launching: starts 4 ranks (children of this process), rank 0 prints
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 bench.py --gpus 4
+    python bench.py --full                # + roofline (per-launch profile of the timed steps), secondary lines, CPU baseline
+    python bench.py --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy (float32)
 Prints ONE JSON line on rank 0.  `--gpus N` must equal WORLD_SIZE when a launcher set it (loud failure otherwise).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+Everything else it can measure -- the `roofline` block (every GEMM / conv launch of the timed steps timed by its own dispatch
+events), `secondary.decompress`, `secondary.compress_f32_mfma`, `arithmetic_check` and `cpu_baseline` -- runs under --full only.
 """
 import argparse
 import json
@@ -289,6 +295,47 @@ def roofline_block(prof, ops, dev, dt, steps, flops_per_step, pmc_file, pmc_shap
     return blk
 
 
+# ------------------------------------------------------------------------------------------------ outputs (--dump-outputs)
+DUMP_BUDGET = 64_000_000       # bytes of .npy files in all
+_NPY_HEADER = 128              # np.save's header for these arrays
+
+
+def output_arrays(result):
+    """what the timed path hands its caller, as float32 arrays.  Compress: a list of B (z_bit_stream, h_bit_stream, clip_stream)
+    host byte strings -> one (B, longest stream) array per field holding the byte values 0..255, -1 past the end of a shorter
+    stream.  Decompress: the reconstructed images x_hat (B, 3, H, W)."""
+    import numpy as np
+    if not isinstance(result, list):
+        return {"x_hat": result.float().cpu().numpy()}
+    arrays = {}
+    for j, name in enumerate(("z_bit_stream", "h_bit_stream", "clip_stream")):
+        rows = [np.frombuffer(r[j], dtype=np.uint8) for r in result]
+        a = np.full((len(rows), max(len(r) for r in rows)), -1.0, dtype=np.float32)
+        for i, r in enumerate(rows):
+            a[i, :len(r)] = r
+        arrays[name] = a
+    return arrays
+
+
+def dump_outputs(out_dir, result, budget=DUMP_BUDGET):
+    """write output_arrays(result) as out_dir/<name>.npy.  Smallest first; an array that would take the total over `budget`
+    is written as a fixed, seeded sample of its elements (<name>.npy, flat) with their flat positions (<name>_index.npy,
+    float64), so runs with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget
+    for name, a in sorted(output_arrays(result).items(), key=lambda kv: kv[1].nbytes):
+        if a.nbytes + _NPY_HEADER > left:
+            k = max(0, (left - 2 * _NPY_HEADER) // 12)          # 4 bytes of value + 8 of position per sampled element
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, size=k)).astype(np.float64)
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx)
+            left -= idx.nbytes + _NPY_HEADER
+            a = a.reshape(-1)[idx.astype(np.int64)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes + _NPY_HEADER
+    return out_dir
+
+
 # ------------------------------------------------------------------------------------------------ the bench
 def main():
     ap = argparse.ArgumentParser()
@@ -306,7 +353,15 @@ def main():
     ap.add_argument("--h2d", action="store_true", help="also copy the input batch host->device inside every step "
                     "(PCIe-inclusive rate for DESIGN.md; never the headline value)")
     ap.add_argument("--rehearse-cpu", action="store_true", help="launcher/rendezvous/all-gather protocol on gloo, no GPU work")
+    ap.add_argument("--full", action="store_true", help="also the roofline block (per-launch profile window over the timed steps), "
+                    "the secondary lines, the arithmetic check and the CPU baseline (--no-secondary / --no-cpu-baseline still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0's "
+                    "shard) as DIR/<name>.npy in float32, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if os.environ.get("SGIC_BENCH_SHAPES") and not args.full and not args.rehearse_cpu:
+        ap.error("SGIC_BENCH_SHAPES lists the launches of the profile window, which only --full opens")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus, sys.argv[1:])     # before anything here touches the GPU
@@ -336,7 +391,7 @@ def main():
     from sgic_amd.data import synth_images
 
     cfg, clip_cfg = (SMALL, CLIP_TINY) if args.small else (LARGE, CLIP_B32)
-    want_dec = args.mode == "decompress" or (world == 1 and not args.no_secondary)
+    want_dec = args.mode == "decompress" or (args.full and world == 1 and not args.no_secondary)
     spec = W.full_spec(cfg) if want_dec else W.encoder_spec(cfg) + W.codec_misc_spec(cfg) + W.bottleneck_spec(cfg)
     sd = W.synth_weights(spec, seed=1234)
     clip_sd = W.synth_weights(W.clip_spec(clip_cfg), seed=4321)
@@ -400,11 +455,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    dec_last = {}
+
     def dec_step_factory():
         encs = codec.encode_batch(x)          # outside the timed region: the bitstreams to decode
 
         def dstep():   # one batch of .c2df payloads -> reconstructed pixels (device-resident fp32)
-            x_hat = codec.decode_batch(encs)
+            x_hat = dec_last["x_hat"] = codec.decode_batch(encs)
             return [(b"", b"", b"")] * B if x_hat is not None else None
         return dstep
 
@@ -422,10 +479,14 @@ def main():
         out = step()
     out = drain() or out
 
-    # profile window: closes pending in-context tile races (no tuning inside the timed region) and times every GEMM /
-    # conv launch with its own dispatch-level event pair (hipExtLaunchKernel, no extra packets on the stream)
+    # pending in-context tile races are closed first (no tuning inside the timed region).  --full: the profile window (which
+    # also closes them) times every GEMM / conv launch with its own dispatch-level event pair (hipExtLaunchKernel, no extra
+    # packets on the stream) for the roofline block
     gather_events.clear()
-    ops.profile_begin()
+    if args.full:
+        ops.profile_begin()
+    else:
+        ops.finalize_autotune()
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -433,7 +494,9 @@ def main():
     out = drain() or out      # the last step's host work is inside the timed region too
     sync()
     dt_local = dt = time.perf_counter() - t0
-    prof = ops.profile_end()      # [(flops, ms, shape key)] per launch of the timed region
+    prof = ops.profile_end() if args.full else None    # [(flops, ms, shape key)] per launch of the timed region
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out if args.mode == "compress" else dec_last["x_hat"])
     if rank == 0 and os.environ.get("SGIC_BENCH_SHAPES"):   # launch-ordered shape list (tools/pmc_by_shape.py joins it with PMC rows)
         tiles = list(ops.PROFILE_TILES) if len(ops.PROFILE_TILES) == len(prof) else [ops.tile_of(k, dev) for _, _, k in prof]   # the mode each launch really took
         json.dump([[list(k) if isinstance(k, tuple) else k, fl, ms, t] for (fl, ms, k), t in zip(prof, tiles)], open(os.environ["SGIC_BENCH_SHAPES"], "w"))
@@ -468,10 +531,11 @@ def main():
                        "global_batch": world * B, "bytes_per_image": round(total_bytes / B, 1)},
             "per_rank_images_per_s": [round(B * args.steps / p[0], 2) for p in per_rank],
             "allgather_ms_per_step": [round(p[1] / args.steps, 4) for p in per_rank],
-            "roofline": roofline_block(prof, ops, dev, dt, args.steps, gflop * 1e9 * B,
-                                       "round3_pmc_decompress_gemm_summary.json" if dec_primary else "round3_pmc_gemm_summary.json"),
         }
-        if world == 1 and not dec_primary and not args.no_secondary:
+        if args.full:
+            res["roofline"] = roofline_block(prof, ops, dev, dt, args.steps, gflop * 1e9 * B,
+                                             "round3_pmc_decompress_gemm_summary.json" if dec_primary else "round3_pmc_gemm_summary.json")
+        if args.full and world == 1 and not dec_primary and not args.no_secondary:
             # secondary line (configs[2]): the decompress path on the same process, a few steps, its own profile window
             dstep = dec_step_factory()
             dstep()
@@ -492,7 +556,7 @@ def main():
                 "roofline": roofline_block(dprof, ops, dev, ddt, args.secondary_steps,
                                            GFLOP_PER_IMAGE_DEC * (S / 256.0) ** 2 * 1e9 * B,
                                            "round3_pmc_decompress_gemm_summary.json")}}
-        if world == 1 and not dec_primary and not args.no_secondary and ops.PRECISION == "split3":
+        if args.full and world == 1 and not dec_primary and not args.no_secondary and ops.PRECISION == "split3":
             # the same compress step with every GEMM on the exact-fp32 MFMA kernel (SGIC_GEMM=f32), for reference
             ops.set_precision("f32")
             try:
@@ -516,7 +580,7 @@ def main():
                 "ms_per_step": round(fdt / args.secondary_steps * 1e3, 3),
                 "roofline": roofline_block(fprof, ops, dev, fdt, args.secondary_steps, gflop * 1e9 * B, "round3_pmc_f32_gemm_summary.json",
                                            "round3_pmc_f32_gemm_by_shape.json")}
-        if world == 1 and not args.small:
+        if args.full and world == 1 and not args.small:
             # live check of the claim behind `arithmetic`: rms error of a K = 4096 GEMM against an fp64 product, split GEMM vs the
             # exact-fp32 MFMA GEMM on the same operands (measurement only: the fp64 product is a torch matmul, not the product path)
             gg = torch.Generator(device=dev).manual_seed(7)
@@ -528,7 +592,7 @@ def main():
             e1 = float((ops.gemm(ta, tw, precision="f32").double() - ref).pow(2).mean().sqrt()) / rms
             res["arithmetic_check"] = {"what": "rms error / rms(C) of a 512x512x4096 GEMM vs an fp64 product, same operands",
                                        "split3_bf16x3": float(f"{e3:.3e}"), "fp32_mfma_chain": float(f"{e1:.3e}")}
-        if world == 1 and not args.no_cpu_baseline and not args.small and not dec_primary:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.small and not dec_primary:
             res["cpu_baseline"] = cpu_baseline(sd, clip_sd, cfg, clip_cfg)
         print(json.dumps(res), flush=True)
     ops.save_tile_cache()

@@ -1,4 +1,4 @@
-"""Join the rocprofv3 --pmc passes of `bench.py --steps 1 --warmup 0 --no-secondary --no-cpu-baseline` with the
+"""Join the rocprofv3 --pmc passes of `bench.py --steps 1 --warmup 0 --full --no-secondary --no-cpu-baseline` with the
 launch-ordered GEMM shape list bench.py writes (SGIC_BENCH_SHAPES) -> per-shape HBM-side counter bytes per launch
 (FETCH_SIZE x2-corrected per MI355X_MICROARCH.md + WRITE_SIZE), next to the algorithmic bytes, plus the whole-step summary.
 usage: python tools/pmc_by_shape.py gpurun_out/pmcC gpurun_out/shapes.json profiles/round3_pmc_gemm_by_shape.json profiles/round3_pmc_gemm_summary.json"""
@@ -118,12 +118,12 @@ for (M, N, K), a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"]):
                  "counter_over_algorithmic": round(cnt / algo, 2), "fetch_MB_x2": round(2 * a["fetch"] * 1024 / a["calls"] / 1e6, 1),
                  "write_MB": round(a["write"] * 1024 / a["calls"] / 1e6, 1),
                  "mfma_busy_fraction": round(a["busy"] / (a["act"] / 8 * 1024), 4) if a["act"] else None})
-json.dump({"command": "tools/pmc_collect.sh (three rocprofv3 --pmc passes over bench.py --steps 1 --warmup 0 --no-secondary --no-cpu-baseline) "
+json.dump({"command": "tools/pmc_collect.sh (three rocprofv3 --pmc passes over bench.py --steps 1 --warmup 0 --full --no-secondary --no-cpu-baseline) "
                       "+ tools/pmc_by_shape.py", "note": "FETCH_SIZE doubled (gfx950 reports half of a wide coalesced stream); Infinity-Cache "
                       "hits are counted; the Infinity Cache (256 MiB) holds the weights + activations of neighbouring launches, so counter bytes "
                       "above the algorithmic bytes are L2 misses served on-die, not HBM re-reads", "shapes": rows}, open(out_shape, "w"), indent=1)
 fs, ws, bs, ga = sum(fetch), sum(write), sum(busy), sum(act)
-summ = {"command": "rocprofv3 --pmc <counter set> --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-secondary --no-cpu-baseline "
+summ = {"command": "rocprofv3 --pmc <counter set> --output-format csv -- python3 bench.py --steps 1 --warmup 0 --full --no-secondary --no-cpu-baseline "
                    "(three separate passes: FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE)",
         "kernel": "gemm_split3_kernel" if s3_share > 0.5 else "gemm_f32_kernel", "what": f"the {n} GEMM-class launches of the timed step", "launches": n,
         "hbm_fetch_MB_per_launch_x2_corrected": round(2 * fs * 1024 / n / 1e6, 2), "hbm_write_MB_per_launch": round(ws * 1024 / n / 1e6, 2),

@@ -7,7 +7,7 @@ PARTS=${@:-bench trace pmc attn misc tests}
 O=gpurun_out/r3F
 mkdir -p $O
 has() { [[ " $PARTS " == *" $1 "* ]]; }
-if has bench; then python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1; fi
+if has bench; then python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || exit 1; fi
 if has trace; then
   cd /tmp && export TMPDIR=/tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/kt_c -o kt -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-secondary > $GRAFT_REPO_ROOT/$O/kt_c.json 2> $GRAFT_REPO_ROOT/$O/kt_c.err || exit 1
