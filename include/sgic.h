@@ -331,6 +331,19 @@ int sgic_jpeg_decode_batch(const int32_t *d_params, const uint8_t *d_scan, const
                            uint8_t *d_planes, uint8_t *d_out, int32_t *d_err, int B, int H, int W, int max_blocks,
                            sgic_stream_t stream);
 
+/* Multi-scan JPEG decode (progressive Huffman, T.81 Annex G; multi-scan sequential; baseline files as one scan each, so mixed
+ * batches decode together) of a batch of B equal-geometry files to RGB u8 HWC (B, H, W, 3), bit-exact with Pillow / libjpeg-turbo
+ * for files it takes (the host refuses those on which libjpeg would run block smoothing).  The host parses every scan and strips
+ * byte stuffing (sgic_amd/jpeg.py ScanJpegBatch); d_descs: 32-int32 scan descriptors sorted by dependency level -- level l is
+ * [h_level_start[l], h_level_start[l + 1]) of the HOST array h_level_start (nlevels + 1 entries), one launch per level, one wave per
+ * scan; d_tabs: the batch's deduplicated Huffman lookup-table pool.  d_coef (total_blocks * 64 int16) is zeroed here.  Other
+ * arguments as sgic_jpeg_decode_batch; d_err[b]: 0 ok / 1 invalid code / 2 missing restart segment / 3 coefficient past its band. */
+int sgic_jpeg_decode_scans_batch(const int32_t *d_params, const int32_t *d_descs, const uint8_t *d_scan, const uint8_t *d_tabs,
+                                 const int32_t *d_segs, const uint16_t *d_quant, int32_t *d_work_params, uint16_t *d_work_quant,
+                                 int16_t *d_coef, uint8_t *d_planes, uint8_t *d_out, int32_t *d_err, int B, int H, int W,
+                                 long total_blocks, int max_blocks, const int32_t *h_level_start, int nlevels,
+                                 sgic_stream_t stream);
+
 /* CLIP text tower front end: out[b*L+l,:] = table[ids[b,l],:] + pos[l,:] (open_clip CLIP.encode_text, reached from
  * search.py:93-97; ids outside [0,vocab) are clamped).  D multiple of 4. */
 int sgic_embed_tokens(const int32_t *d_ids, const float *d_table, const float *d_pos, float *d_out, int B, int L, int D,

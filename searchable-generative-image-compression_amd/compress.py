@@ -104,6 +104,9 @@ def main(argv=None):
     ap.add_argument("--workers", type=int, default=None, help="image decode threads (default: min(16, cores))")
     ap.add_argument("--prefetch", type=int, default=3, help="decoded batches held ahead of the GPU (bounds host memory)")
     ap.add_argument("--small", action="store_true", help="SMALL/TINY test architectures")
+    ap.add_argument("--gpu_progressive_jpeg", action="store_true",
+                    help="decode progressive (and mixed baseline / progressive) JPEG batches on the GPU too (default: host; "
+                         "also SGIC_GPU_JPEG_PROGRESSIVE=1)")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -189,7 +192,8 @@ def main(argv=None):
     io_pool, writes = ThreadPoolExecutor(max_workers=4), deque()
     loader = None
     try:
-        loader = ShardLoader(mine, args.batch_size, workers=args.workers, depth=args.prefetch)
+        loader = ShardLoader(mine, args.batch_size, workers=args.workers, depth=args.prefetch,
+                             gpu_progressive=True if args.gpu_progressive_jpeg else None)
         # two-deep pipeline: the GPU works on batch k+1 while the host packs and writes batch k, and the decode threads
         # are already filling the pinned buffers of batches k+2 .. k+1+prefetch
         pending = None
@@ -260,7 +264,8 @@ def main(argv=None):
                           "collectives": (dist.get_backend() if distributed else None),
                           "seconds_rank0": round(dt, 3), "batch_size": args.batch_size,
                           "host_ms_per_batch": {k: round(v / max(1, host_ms.get("batches", 1)), 2) for k, v in host_ms.items() if k != "batches"},
-                          "gpu_jpeg_batches": getattr(loader, "gpu_batches", 0), "host_decoded_batches": getattr(loader, "host_batches", 0),
+                          "gpu_jpeg_batches": getattr(loader, "gpu_batches", 0), "gpu_scan_jpeg_batches": getattr(loader, "gpu_scan_batches", 0),
+                          "host_decoded_batches": getattr(loader, "host_batches", 0),
                           "note": "files -> .c2df: header pass, JPEG/PNG decode, H2D, encoder+entropy+CLIP, container + .npy writes"}),
               flush=True)
     ops.save_tile_cache()

@@ -13,7 +13,9 @@
 //   jpeg_idct_kernel      one thread per 8x8 block: dequantise, two 1-D passes of the LL&M integer IDCT, range limit -> u8 planes.
 //   jpeg_color_kernel     one thread per output pixel: chroma upsampling of the 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0 layouts + colour
 //                         conversion (or grey -> RGB).
-// All integer arithmetic: parity with Pillow is exact (tests/test_gpu_jpeg.py), not a tolerance.
+// Progressive / multi-scan files replace the first kernel by jpeg_scan_kernel (one wave per (image, scan), one launch per dependency
+// level of the batch's scans) and then run the same two.
+// All integer arithmetic: parity with Pillow is exact (tests/test_gpu_jpeg.py, tests/test_gpu_jpeg_scans.py), not a tolerance.
 #include "common.h"
 
 #define JPG_NP 64            // int32 parameters per image (sgic_amd/jpeg.py: PARAM_*)
@@ -32,46 +34,37 @@ __constant__ unsigned char jpg_natural[80] = {0,  1,  8,  16, 9,  2,  3,  10, 17
                                               6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
                                               39, 46, 53, 60, 61, 54, 47, 55, 62, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
 
-// ---- Huffman decode: one wave per image -------------------------------------------------------------------------------------------
-// params / scan / tabs / segs / quant_in may live in PINNED HOST memory (the kernel pulls them over PCIe: a batch is ~1 MB, read once,
-// in coalesced 1 KiB chunks) -- there is then no H2D copy to schedule; the descriptors and quantisation tables the two later kernels
-// need are left in device memory (params_dev, quant_dev) by this one.
-__global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ params, const unsigned char *__restrict__ scan,
-                                                       const unsigned char *__restrict__ tabs, const int *__restrict__ segs,
-                                                       const unsigned short *__restrict__ quant_in, int *__restrict__ params_dev,
-                                                       unsigned short *__restrict__ quant_dev, short *__restrict__ coef,
-                                                       int *__restrict__ err) {
-  __shared__ __attribute__((aligned(16))) unsigned char ring[JPG_RING];
-  __shared__ __attribute__((aligned(16))) unsigned char tab[4 * JPG_TAB_BYTES];
-  __shared__ short blk[64];
-  const int img = blockIdx.x, lane = threadIdx.x;
-  __shared__ int Ps[JPG_NP];
-  Ps[lane] = params[(size_t)img * JPG_NP + lane];
-  params_dev[(size_t)img * JPG_NP + lane] = Ps[lane];
-  __syncthreads();
-  const int *P = Ps;
-  for (int i = lane; i < 256; i += 64) quant_dev[(size_t)img * 256 + i] = quant_in[P[P_QUANT_OFF] + i];
-  const unsigned char *src = scan + P[P_SCAN_OFF];
-  const int total = P[P_SCAN_LEN];   // bytes, padded by the host to a multiple of JPG_CHUNK with zeros
-  {
-    const uint4 *t4 = reinterpret_cast<const uint4 *>(tabs + P[P_TAB_OFF]);
-    for (int i = lane; i < 4 * JPG_TAB_BYTES / 16; i += 64) reinterpret_cast<uint4 *>(tab)[i] = t4[i];
-  }
-  int filled = 0;   // bytes of the scan staged so far (wave-uniform)
-  auto fill = [&]() {
+// ---- the entropy-coded segment, shared by jpeg_huff_kernel and jpeg_scan_kernel --------------------------------------------------------
+// One wave reads one cleaned segment: 1 KiB coalesced chunks (lane = 16 B) into a 4 KiB LDS ring, and a 64-bit bit accumulator that every
+// lane holds identically (wave-uniform state).  The segment is padded by the host to a multiple of JPG_CHUNK with zeros.
+struct JpgBits {
+  unsigned char *ring;
+  const unsigned char *src;
+  int total, lane;
+  int filled;   // bytes of the segment staged so far (wave-uniform)
+  // bit reader: `acc` holds `cnt` valid bits, MSB first; rp = byte position of the next 32-bit word to fetch
+  unsigned long long acc;
+  int cnt, rp, bad;
+
+  __device__ __forceinline__ void fill() {
     const uint4 *s4 = reinterpret_cast<const uint4 *>(src + filled);
     uint4 *d4 = reinterpret_cast<uint4 *>(ring + (filled & (JPG_RING - 1)));
 #pragma unroll
     for (int i = 0; i < JPG_CHUNK / 16 / 64; i++) d4[lane + 64 * i] = s4[lane + 64 * i];
     filled += JPG_CHUNK;
-  };
-  fill();
-  if (total > JPG_CHUNK) fill();
-  __syncthreads();
-  // bit reader: `acc` holds `cnt` valid bits, MSB first; rp = byte position of the next 32-bit word to fetch
-  unsigned long long acc = 0;
-  int cnt = 0, rp = 0, bad = 0;
-  auto refill = [&]() {
+  }
+  __device__ __forceinline__ void start(unsigned char *ring_, const unsigned char *src_, int total_, int lane_) {
+    ring = ring_;
+    src = src_;
+    total = total_;
+    lane = lane_;
+    filled = 0;
+    acc = 0;
+    cnt = rp = bad = 0;
+    fill();
+    if (total > JPG_CHUNK) fill();
+  }
+  __device__ __forceinline__ void refill() {
     while (cnt <= 32) {
       if (filled - rp < JPG_CHUNK + 8 && filled < total) {   // uniform: stage the next chunk (the ring keeps > 4 KiB unread at most)
         fill();
@@ -84,8 +77,8 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
       cnt += 32;
       rp += 4;
     }
-  };
-  auto seek = [&](int byte_off) {   // restart boundary: continue at a byte offset of the cleaned scan
+  }
+  __device__ __forceinline__ void seek(int byte_off) {   // restart boundary: continue at a byte offset of the cleaned segment
     const int aligned = byte_off & ~3;
     if (aligned >= filled || aligned < filled - JPG_RING + JPG_CHUNK) {   // outside the staged window: restage from there
       filled = aligned & ~(JPG_CHUNK - 1);
@@ -100,8 +93,8 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
     const int skip = (byte_off - aligned) * 8;
     acc <<= skip;
     cnt -= skip;
-  };
-  auto decode = [&](const unsigned char *T) -> int {   // one Huffman symbol
+  }
+  __device__ __forceinline__ int decode(const unsigned char *T) {   // one Huffman symbol
     refill();
     const unsigned e = reinterpret_cast<const unsigned short *>(T)[(unsigned)(acc >> (64 - JPG_LOOK))];
     if (e) {
@@ -122,13 +115,46 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
     acc <<= l;
     cnt -= l;
     return sym;
-  };
-  auto receive = [&](int s) -> int {   // s extra bits, sign-extended (jdhuff.c HUFF_EXTEND)
-    const int v = (int)(acc >> (64 - s));
-    acc <<= s;
-    cnt -= s;
+  }
+  __device__ __forceinline__ unsigned bits(int n) {   // n raw bits, 1 <= n <= 32 (after a refill)
+    const unsigned v = (unsigned)(acc >> (64 - n));
+    acc <<= n;
+    cnt -= n;
+    return v;
+  }
+  __device__ __forceinline__ int receive(int s) {   // s extra bits, sign-extended (jdhuff.c HUFF_EXTEND)
+    const int v = (int)bits(s);
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-  };
+  }
+};
+
+// ---- Huffman decode: one wave per image -------------------------------------------------------------------------------------------
+// params / scan / tabs / segs / quant_in may live in PINNED HOST memory (the kernel pulls them over PCIe: a batch is ~1 MB, read once,
+// in coalesced 1 KiB chunks) -- there is then no H2D copy to schedule; the descriptors and quantisation tables the two later kernels
+// need are left in device memory (params_dev, quant_dev) by this one.
+__global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ params, const unsigned char *__restrict__ scan,
+                                                       const unsigned char *__restrict__ tabs, const int *__restrict__ segs,
+                                                       const unsigned short *__restrict__ quant_in, int *__restrict__ params_dev,
+                                                       unsigned short *__restrict__ quant_dev, short *__restrict__ coef,
+                                                       int *__restrict__ err) {
+  __shared__ __attribute__((aligned(16))) unsigned char ring[JPG_RING];
+  __shared__ __attribute__((aligned(16))) unsigned char tab[4 * JPG_TAB_BYTES];
+  __shared__ short blk[64];
+  const int img = blockIdx.x, lane = threadIdx.x;
+  __shared__ int Ps[JPG_NP];
+  Ps[lane] = params[(size_t)img * JPG_NP + lane];
+  params_dev[(size_t)img * JPG_NP + lane] = Ps[lane];
+  __syncthreads();
+  const int *P = Ps;
+  for (int i = lane; i < 256; i += 64) quant_dev[(size_t)img * 256 + i] = quant_in[P[P_QUANT_OFF] + i];
+  {
+    const uint4 *t4 = reinterpret_cast<const uint4 *>(tabs + P[P_TAB_OFF]);
+    for (int i = lane; i < 4 * JPG_TAB_BYTES / 16; i += 64) reinterpret_cast<uint4 *>(tab)[i] = t4[i];
+  }
+  JpgBits br;
+  br.start(ring, scan + P[P_SCAN_OFF], P[P_SCAN_LEN], lane);
+  __syncthreads();
+  int &bad = br.bad;
 
   const int ncomp = P[P_NCOMP], mcus = P[P_MCUS_X] * P[P_MCUS_Y], mcus_x = P[P_MCUS_X], restart = P[P_RESTART];
   const int *seg = segs + P[P_SEG_OFF];
@@ -140,7 +166,7 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
         bad = 2;
         break;
       }
-      seek(seg[next_seg++]);
+      br.seek(seg[next_seg++]);
       pred[0] = pred[1] = pred[2] = 0;
     }
     const int my = mcu / mcus_x, mx = mcu - my * mcus_x;
@@ -151,14 +177,14 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
       for (int by = 0; by < vs; by++)
         for (int bx = 0; bx < hs; bx++) {
           blk[lane] = 0;
-          int s = decode(Tdc);
+          int s = br.decode(Tdc);
           if (s) {
-            refill();
-            pred[c] += receive(s);
+            br.refill();
+            pred[c] += br.receive(s);
           }
           if (lane == 0) blk[0] = (short)pred[c];
           for (int k = 1; k < 64;) {
-            const int rs = decode(Tac);
+            const int rs = br.decode(Tac);
             const int r = rs >> 4;
             s = rs & 15;
             if (s == 0) {
@@ -167,8 +193,8 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
               continue;
             }
             k += r;
-            refill();
-            const int v = receive(s);
+            br.refill();
+            const int v = br.receive(s);
             if (lane == 0) blk[jpg_natural[k]] = (short)v;   // k <= 63 + 15: the table is padded to 80 entries
             k++;
           }
@@ -178,6 +204,251 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
     }
   }
   if (lane == 0) err[img] = bad;
+}
+
+// ---- progressive / multi-scan decode: one wave per (image, scan) ------------------------------------------------------------------
+// The decode procedures of T.81 G.1.2 as libjpeg-turbo's jdphuff.c runs them, plus the sequential block loop above for one scan of a
+// baseline or multi-scan sequential file.  The host (sgic_amd/jpeg.py ScanJpegBatch) groups the scans of a batch into dependency
+// levels: the scans of one level touch disjoint (component, coefficient) sets of the coefficient array, so one launch runs a whole
+// level and stream order between the launches is the only synchronisation.  A scan therefore stores ONLY the coefficients of its
+// band (2-byte stores), never a whole 64-entry block, and reads only its band (refinement scans).  The array is zeroed beforehand.
+enum {   // per-scan descriptor, 32 int32 (sgic_amd/jpeg.py: S_*)
+  S_IMG = 0, S_MODE, S_NCOMP, S_COMP0, S_SS = 6, S_SE, S_AH, S_AL, S_RESTART, S_SCAN_OFF, S_SCAN_LEN, S_SEG_OFF, S_NSEG,
+  S_GW = 15, S_GH,   // units of the scan: MCUs of the frame (interleaved) or the component's own ceil(cw/8) x ceil(ch/8) blocks
+  S_NTAB = 17, S_TAB0,   // the scan's (<= 4) Huffman tables: indices into the batch's table pool
+  S_DC0 = 22, S_AC0 = 25,   // per scan component: its DC / AC table among the scan's (0..3)
+  S_FIRST = 28,   // the image's first scan (level 0): copies params / quant into device memory for the IDCT / colour kernels
+  JPG_NS = 32
+};
+enum { M_SEQ = 0, M_DC_FIRST, M_DC_REFINE, M_AC_FIRST, M_AC_REFINE };
+
+__global__ __launch_bounds__(64) void jpeg_scan_kernel(const int *__restrict__ params, const int *__restrict__ descs,
+                                                       const unsigned char *__restrict__ scan, const unsigned char *__restrict__ tabs,
+                                                       const int *__restrict__ segs, const unsigned short *__restrict__ quant_in,
+                                                       int *__restrict__ params_dev, unsigned short *__restrict__ quant_dev,
+                                                       short *__restrict__ coef, int *__restrict__ err) {
+  __shared__ __attribute__((aligned(16))) unsigned char ring[JPG_RING];
+  __shared__ __attribute__((aligned(16))) unsigned char tab[4 * JPG_TAB_BYTES];
+  __shared__ int Ps[JPG_NP], Ss_[JPG_NS];
+  const int lane = threadIdx.x;
+  if (lane < JPG_NS) Ss_[lane] = descs[(size_t)blockIdx.x * JPG_NS + lane];
+  __syncthreads();
+  const int *S = Ss_;
+  const int img = S[S_IMG];
+  Ps[lane] = params[(size_t)img * JPG_NP + lane];
+  if (S[S_FIRST]) params_dev[(size_t)img * JPG_NP + lane] = Ps[lane];
+  __syncthreads();
+  const int *P = Ps;
+  if (S[S_FIRST])
+    for (int i = lane; i < 256; i += 64) quant_dev[(size_t)img * 256 + i] = quant_in[P[P_QUANT_OFF] + i];
+  for (int t = 0; t < S[S_NTAB]; t++) {
+    const uint4 *t4 = reinterpret_cast<const uint4 *>(tabs + (size_t)S[S_TAB0 + t] * JPG_TAB_BYTES);
+    for (int i = lane; i < JPG_TAB_BYTES / 16; i += 64) reinterpret_cast<uint4 *>(tab + t * JPG_TAB_BYTES)[i] = t4[i];
+  }
+  JpgBits br;
+  br.start(ring, scan + S[S_SCAN_OFF], S[S_SCAN_LEN], lane);
+  __syncthreads();
+
+  const int mode = S[S_MODE], ns = S[S_NCOMP], Ss = S[S_SS], Se = S[S_SE], Al = S[S_AL], restart = S[S_RESTART];
+  const int gw = S[S_GW], units = S[S_GW] * S[S_GH];
+  const int *seg = segs + S[S_SEG_OFF];
+  // block `j` (scan order) of unit `u` -> index of the block in the coefficient array
+  auto block_of = [&](int u, int j) -> size_t {
+    const int uy = u / gw, ux = u - uy * gw;
+    if (ns == 1) {
+      const int *C = P + P_COMP0 + S[S_COMP0] * P_CSTRIDE;
+      return (size_t)C[9] + (size_t)uy * C[5] + ux;
+    }
+    for (int i = 0;; i++) {
+      const int *C = P + P_COMP0 + S[S_COMP0 + i] * P_CSTRIDE;
+      const int hs = C[0], vs = C[1];
+      if (j < hs * vs || i == ns - 1) {
+        const int by = j / hs, bx = j - by * hs;
+        return (size_t)C[9] + (size_t)(uy * vs + by) * C[5] + (ux * hs + bx);
+      }
+      j -= hs * vs;
+    }
+  };
+  int bpu = 0;   // blocks per unit
+  for (int i = 0; i < ns; i++) {
+    const int *C = P + P_COMP0 + S[S_COMP0 + i] * P_CSTRIDE;
+    bpu += ns == 1 ? 1 : C[0] * C[1];
+  }
+  // lane = zig-zag index k of the coefficient it holds (AC scans and the sequential loop)
+  const int nat = jpg_natural[lane];
+  const bool inband = lane >= Ss && lane <= Se;
+  const unsigned long long band = (~0ull >> (63 - Se)) & (~0ull << Ss);
+  int pred[3] = {0, 0, 0};
+  int eobrun = 0, next_seg = 1;
+  int &bad = br.bad;
+
+  if (mode == M_DC_REFINE) {
+    // one raw bit per block, no Huffman code: lane-parallel over 32 blocks at a time (within a restart interval)
+    const int p1 = 1 << Al;
+    for (int u0 = 0; u0 < units && !bad;) {
+      if (restart && u0) {
+        if (next_seg >= S[S_NSEG]) {
+          bad = 2;
+          break;
+        }
+        br.seek(seg[next_seg++]);
+      }
+      const int u1 = restart ? min(u0 + restart, units) : units;
+      const int nb = (u1 - u0) * bpu;
+      for (int j0 = 0; j0 < nb; j0 += 32) {
+        const int m = min(32, nb - j0);
+        br.refill();
+        const unsigned b = br.bits(m);
+        const int j = j0 + lane;
+        if (lane < m && ((b >> (m - 1 - lane)) & 1)) {
+          const int q = j / bpu;
+          short *c = coef + block_of(u0 + q, j - q * bpu) * 64;
+          c[0] = (short)(c[0] | p1);
+        }
+      }
+      u0 = u1;
+    }
+  } else if (mode == M_AC_REFINE) {
+    const int p1 = 1 << Al;
+    const unsigned char *Tac = tab + S[S_AC0] * JPG_TAB_BYTES;
+    const unsigned long long below = (1ull << lane) - 1;   // zig-zag positions before this lane's
+    int nextv = inband && units ? coef[block_of(0, 0) * 64 + nat] : 0;
+    for (int u = 0; u < units && !bad; u++) {
+      if (restart && u && u % restart == 0) {
+        if (next_seg >= S[S_NSEG]) {
+          bad = 2;
+          break;
+        }
+        br.seek(seg[next_seg++]);
+        eobrun = 0;
+      }
+      const size_t blk = block_of(u, 0);
+      int v = nextv;   // this block's band, loaded one block ahead: the load latency hides under the previous block's decode
+      if (inband && u + 1 < units) nextv = coef[block_of(u + 1, 0) * 64 + nat];
+      const unsigned long long nz = __ballot(v != 0) & band;   // the band's already-nonzero coefficients (wave-uniform)
+      // correction bits, in zig-zag order, for the nonzero coefficients of mask `cm`: each lane applies its own bit
+      auto correct = [&](unsigned long long cm) {
+        const int n = __popcll(cm), rank = __popcll(cm & below);
+        const bool mine = (cm >> lane) & 1;
+        for (int done = 0; done < n; done += 32) {
+          const int m = min(32, n - done);
+          br.refill();
+          const unsigned b = br.bits(m);
+          if (mine && rank >= done && rank < done + m && ((b >> (m - 1 - (rank - done))) & 1) && (v & p1) == 0) v += v >= 0 ? p1 : -p1;
+        }
+      };
+      int k = Ss;
+      if (eobrun == 0) {
+        while (k <= Se) {
+          const int rs = br.decode(Tac);
+          if (bad) break;
+          const int r = rs >> 4, s = rs & 15;
+          int sv = 0;
+          if (s) {   // a new coefficient of magnitude 1 << Al (s != 1 only in a corrupt file; libjpeg takes it the same way)
+            br.refill();
+            sv = br.bits(1) ? p1 : -p1;
+          } else if (r != 15) {   // EOBn: the rest of this block and eobrun - 1 more take correction bits only
+            eobrun = 1 << r;
+            if (r) {
+              br.refill();
+              eobrun += (int)br.bits(r);
+            }
+            break;
+          }
+          // skip r zero coefficients (ZRL: 15, and the 16th is skipped too) taking a correction bit for every nonzero one passed
+          unsigned long long z = ~nz & band & (~0ull << k);
+          for (int i = 0; i < r && z; i++) z &= z - 1;
+          const int t = z ? __ffsll((long long)z) - 1 : Se + 1;
+          correct(nz & (~0ull << k) & (t > 63 ? ~0ull : (1ull << t) - 1));
+          if (s) {
+            if (t > Se) {   // a new coefficient past the band end: corrupt
+              bad = 3;
+              break;
+            }
+            if (lane == t) v = sv;
+          }
+          k = t + 1;
+        }
+      }
+      if (eobrun > 0 && !bad) {
+        if (k <= Se) correct(nz & (~0ull << k));
+        eobrun--;
+      }
+      if (inband) coef[blk * 64 + nat] = (short)v;
+    }
+  } else {
+    for (int u = 0; u < units && !bad; u++) {
+      if (restart && u && u % restart == 0) {
+        if (next_seg >= S[S_NSEG]) {
+          bad = 2;
+          break;
+        }
+        br.seek(seg[next_seg++]);
+        pred[0] = pred[1] = pred[2] = 0;
+        eobrun = 0;
+      }
+      for (int i = 0, j = 0; i < ns && !bad; i++) {
+        const int *C = P + P_COMP0 + S[S_COMP0 + i] * P_CSTRIDE;
+        const int nbl = ns == 1 ? 1 : C[0] * C[1];
+        const unsigned char *Tdc = tab + S[S_DC0 + i] * JPG_TAB_BYTES, *Tac = tab + S[S_AC0 + i] * JPG_TAB_BYTES;
+        for (int q = 0; q < nbl; q++, j++) {
+          const size_t blk = block_of(u, j);
+          if (mode == M_SEQ || mode == M_DC_FIRST) {
+            int s = br.decode(Tdc);
+            if (s > 15) bad = 1;
+            if (bad) break;
+            if (s) {
+              br.refill();
+              pred[i] += br.receive(s);
+            }
+            if (mode == M_DC_FIRST) {
+              if (lane == 0) coef[blk * 64] = (short)(int)((unsigned)pred[i] << Al);
+              continue;
+            }
+          }
+          // AC first (Ss..Se, EOBRUN) or the sequential block (1..63): the value of zig-zag position `lane`
+          if (mode == M_AC_FIRST && eobrun > 0) {
+            eobrun--;
+            continue;
+          }
+          int v = mode == M_SEQ && lane == 0 ? pred[i] : 0;
+          bool any = mode == M_SEQ;
+          for (int k = mode == M_SEQ ? 1 : Ss; k <= (mode == M_SEQ ? 63 : Se);) {
+            const int rs = br.decode(Tac);
+            if (bad) break;
+            const int r = rs >> 4, s = rs & 15;
+            if (s == 0) {
+              if (r == 15) {   // ZRL
+                k += 16;
+                continue;
+              }
+              if (mode == M_AC_FIRST) {   // EOBn
+                eobrun = 1 << r;
+                if (r) {
+                  br.refill();
+                  eobrun += (int)br.bits(r);
+                }
+                eobrun--;
+              }
+              break;
+            }
+            k += r;
+            if (k > (mode == M_SEQ ? 63 : Se)) {   // a coefficient past the band end: corrupt
+              bad = 3;
+              break;
+            }
+            br.refill();
+            const int val = br.receive(s);
+            if (lane == k) v = (int)((unsigned)val << Al);
+            any = true;
+            k++;
+          }
+          if (any && (mode == M_SEQ || inband)) coef[blk * 64 + nat] = (short)v;
+        }
+      }
+    }
+  }
+  if (lane == 0 && bad) atomicMax(err + img, bad);
 }
 
 // ---- dequantise + islow IDCT (jidctint.c jpeg_idct_islow), one thread per block ------------------------------------------------------
@@ -353,6 +624,39 @@ extern "C" int sgic_jpeg_decode_batch(const int32_t *d_params, const uint8_t *d_
   if (rc) return rc;
   jpeg_idct_kernel<<<dim3(cdiv(max_blocks, 64), B), 64, 0, st>>>(d_work_params, d_coef, d_work_quant, d_planes, max_blocks);
   rc = sgic::check_launch("jpeg_idct_kernel");
+  if (rc) return rc;
+  const long px = (long)H * W;
+  jpeg_color_kernel<<<dim3((unsigned)min((px + 255) / 256, 4096L), B), 256, 0, st>>>(d_work_params, d_planes, d_out, H, W);
+  return sgic::check_launch("jpeg_color_kernel");
+}
+
+// Decode a batch of B JPEGs of equal geometry given as SCANS (progressive files, multi-scan sequential files, and baseline files as one
+// sequential scan each) to RGB u8 HWC (B, H, W, 3).  d_descs: nscans x 32 int32 scan descriptors sorted by dependency level, level l
+// being descriptors [h_level_start[l], h_level_start[l + 1]) (host array, nlevels + 1 entries); d_tabs: the batch's Huffman table pool
+// (1424 B each).  Other arguments as sgic_jpeg_decode_batch; d_err[b]: 0 ok, 1 invalid Huffman code, 2 missing restart segment,
+// 3 coefficient past the end of its band.
+extern "C" int sgic_jpeg_decode_scans_batch(const int32_t *d_params, const int32_t *d_descs, const uint8_t *d_scan, const uint8_t *d_tabs,
+                                            const int32_t *d_segs, const uint16_t *d_quant, int32_t *d_work_params, uint16_t *d_work_quant,
+                                            int16_t *d_coef, uint8_t *d_planes, uint8_t *d_out, int32_t *d_err, int B, int H, int W,
+                                            long total_blocks, int max_blocks, const int32_t *h_level_start, int nlevels,
+                                            sgic_stream_t stream) {
+  SGIC_REQUIRE(d_params && d_descs && d_scan && d_tabs && d_segs && d_quant && d_work_params && d_work_quant && d_coef && d_planes && d_out &&
+                   d_err && h_level_start, "null");
+  SGIC_REQUIRE(B > 0 && H > 0 && W > 0 && max_blocks > 0 && total_blocks > 0 && nlevels > 0, "shape");
+  SGIC_REQUIRE((((uintptr_t)d_scan | (uintptr_t)d_tabs | (uintptr_t)d_planes) & 15) == 0, "16-byte alignment");
+  hipStream_t st = to_stream(stream);
+  SGIC_HIP(hipMemsetAsync(d_coef, 0, (size_t)total_blocks * 64 * sizeof(int16_t), st));
+  SGIC_HIP(hipMemsetAsync(d_err, 0, (size_t)B * sizeof(int32_t), st));
+  for (int l = 0; l < nlevels; l++) {
+    const int n = h_level_start[l + 1] - h_level_start[l];
+    SGIC_REQUIRE(n > 0, "empty level");
+    jpeg_scan_kernel<<<n, 64, 0, st>>>(d_params, d_descs + (size_t)h_level_start[l] * JPG_NS, d_scan, d_tabs, d_segs, d_quant,
+                                       d_work_params, d_work_quant, d_coef, d_err);
+    const int rc = sgic::check_launch("jpeg_scan_kernel");
+    if (rc) return rc;
+  }
+  jpeg_idct_kernel<<<dim3(cdiv(max_blocks, 64), B), 64, 0, st>>>(d_work_params, d_coef, d_work_quant, d_planes, max_blocks);
+  int rc = sgic::check_launch("jpeg_idct_kernel");
   if (rc) return rc;
   const long px = (long)H * W;
   jpeg_color_kernel<<<dim3((unsigned)min((px + 255) / 256, 4096L), B), 256, 0, st>>>(d_work_params, d_planes, d_out, H, W);

@@ -10,7 +10,9 @@ has to be a pipeline of its own, with bounded memory whatever the corpus size:
   2. decode        -- JPEG batches (baseline Huffman files: what cameras and Pillow write) are decoded ON THE GPU: the thread
                       pool only reads the file bytes and parses markers (sgic_amd.jpeg), the compressed bytes cross PCIe
                       (~1/10 of the pixels) and csrc/jpeg.hip does Huffman decode, IDCT, chroma upsampling and colour
-                      conversion, bit-exact with Pillow.  Other files (PNG, progressive / CMYK JPEG, ...) take the host
+                      conversion, bit-exact with Pillow.  With `gpu_progressive` (SGIC_GPU_JPEG_PROGRESSIVE=1; off by
+                      default) progressive JPEG batches, and batches mixing baseline and progressive files, are decoded
+                      there too, scan by scan (sgic_amd.jpeg.ScanJpegBatch).  Other files (PNG, CMYK JPEG, ...) take the host
                       path: a thread pool (PIL releases the GIL while decoding) fills a PINNED u8 (B,H,W,3) buffer per
                       batch.  At most `depth` batches are prepared ahead of the consumer: memory is O(depth x batch), not
                       O(shard) -- a 10 k-image shard of 1024^2 inputs costs ~100 MB per in-flight batch, not 126 GB.
@@ -65,7 +67,8 @@ def plan_batches(files, sizes, batch_size):
 
 
 class Batch:
-    """u8: pinned (B,H,W,3) host tensor (host-decoded batch), or None when `jpeg` holds a sgic_amd.jpeg.JpegBatch to decode on the GPU"""
+    """u8: pinned (B,H,W,3) host tensor (host-decoded batch), or None when `jpeg` holds a sgic_amd.jpeg.JpegBatch / ScanJpegBatch to
+    decode on the GPU"""
     __slots__ = ("H", "W", "indices", "paths", "u8", "jpeg", "_slot", "_owner")
 
     def release(self):
@@ -82,13 +85,18 @@ class ShardLoader:
             ...; b.release()
     A decode error is re-raised in the consumer at the position of the failing batch."""
 
-    def __init__(self, files, batch_size=32, workers=None, depth=3, pin=True, gpu_jpeg=None):
-        """gpu_jpeg: decode baseline JPEG batches on the GPU (default: when a GPU is present; SGIC_GPU_JPEG=0 turns it off)"""
+    def __init__(self, files, batch_size=32, workers=None, depth=3, pin=True, gpu_jpeg=None, gpu_progressive=None):
+        """gpu_jpeg: decode baseline JPEG batches on the GPU (default: when a GPU is present; SGIC_GPU_JPEG=0 turns it off).
+        gpu_progressive: also decode the JPEG batches the baseline path refuses but the scan decoder takes (progressive and mixed
+        baseline / progressive batches) on the GPU (default: off; SGIC_GPU_JPEG_PROGRESSIVE=1 turns it on); needs gpu_jpeg"""
         self.files = list(files)
         if gpu_jpeg is None:
             gpu_jpeg = torch.cuda.is_available() and os.environ.get("SGIC_GPU_JPEG", "1") != "0"
+        if gpu_progressive is None:
+            gpu_progressive = os.environ.get("SGIC_GPU_JPEG_PROGRESSIVE", "0") == "1"
         self.gpu_jpeg = bool(gpu_jpeg)
-        self.gpu_batches = self.host_batches = 0
+        self.gpu_progressive = self.gpu_jpeg and bool(gpu_progressive)
+        self.gpu_batches = self.gpu_scan_batches = self.host_batches = 0
         self.batch_size, self.depth = int(batch_size), max(1, int(depth))
         self.workers = workers or min(16, max(2, (os.cpu_count() or 4)))
         self.pin = pin and torch.cuda.is_available()
@@ -133,18 +141,29 @@ class ShardLoader:
                 n = len(idxs)
                 b = Batch()
                 b.H, b.W, b.indices, b.paths, b.jpeg = h, w, idxs, [self.files[i] for i in idxs], None
+                scans = False
                 if self.gpu_jpeg and all(p.lower().endswith((".jpg", ".jpeg")) for p in b.paths):
                     from . import jpeg as J
+                    alloc = lambda nbytes: self._buffer(slot, nbytes)     # the slot's pinned buffer: read in place by the kernels
+                    datas = None
                     try:     # file bytes + marker parsing on the pool; the pixels never exist on the host
-                        b.jpeg = J.JpegBatch(list(self._pool.map(_read_bytes, b.paths)), pool=self._pool,
-                                             alloc=lambda nbytes: self._buffer(slot, nbytes))   # the slot's pinned buffer: one async H2D copy
-                        if (b.jpeg.H, b.jpeg.W) != (h, w):
-                            b.jpeg = None
+                        datas = list(self._pool.map(_read_bytes, b.paths))
+                        b.jpeg = J.JpegBatch(datas, pool=self._pool, alloc=alloc)
                     except Exception:      # noqa: BLE001 -- J.Unsupported (progressive / CMYK / ...) or a file the parser chokes on:
                         b.jpeg = None      # this batch takes the host decoder, which raises a proper error for a really broken file
+                    if b.jpeg is None and datas is not None and self.gpu_progressive:
+                        try:     # progressive / mixed batch: decoded scan by scan
+                            b.jpeg, scans = J.ScanJpegBatch(datas, pool=self._pool, alloc=alloc), True
+                        except Exception:  # noqa: BLE001 -- as above: the host decoder takes it
+                            b.jpeg = None
+                    if b.jpeg is not None and (b.jpeg.H, b.jpeg.W) != (h, w):
+                        b.jpeg = None
                 if b.jpeg is not None:
                     b.u8, b._slot, b._owner = None, slot, self     # the slot returns with release(), after the copy has completed
-                    self.gpu_batches += 1
+                    if scans:
+                        self.gpu_scan_batches += 1
+                    else:
+                        self.gpu_batches += 1
                 else:
                     flat = self._buffer(slot, n * h * w * 3)
                     u8 = flat[:n * h * w * 3].view(n, h, w, 3)

@@ -5,7 +5,10 @@ Supported on the GPU (everything Pillow's `save(..., "JPEG")` and ordinary camer
 Huffman JPEG, 8-bit, one interleaved scan, greyscale or YCbCr with 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0 sampling, restart intervals,
 custom Huffman / quantisation tables.  Anything else (progressive, arithmetic coding, CMYK / YCCK, RGB-coded, 12-bit, multi-scan,
 chroma planes too narrow for the fancy upsampler) raises `Unsupported`, and the ingest falls back to the host decoder for that
-batch -- the result is the same pixels either way, the GPU path being bit-exact with Pillow (tests/test_gpu_jpeg.py)."""
+batch -- the result is the same pixels either way, the GPU path being bit-exact with Pillow (tests/test_gpu_jpeg.py).
+
+parse_scans() / ScanJpegBatch take progressive Huffman and multi-scan sequential files as well (and baseline files as one scan, so that
+mixed batches decode together): one descriptor per scan, decoded by csrc/jpeg.hip jpeg_scan_kernel (tests/test_gpu_jpeg_scans.py)."""
 import struct
 
 import numpy as np
@@ -60,6 +63,53 @@ def huff_table(bits, vals):
 
 class Parsed:
     __slots__ = ("W", "H", "ncomp", "comps", "hmax", "vmax", "quant", "tabs", "scan", "segs", "restart", "mcus_x", "mcus_y")
+
+
+def _frame_geometry(frame, adobe_transform):
+    """SOF (H, W, [(id, h, v, tq)]) -> (H, W, ncomp, hmax, vmax, comps); raises Unsupported for layouts outside the GPU path"""
+    H, W, comps = frame
+    nc = len(comps)
+    if nc not in (1, 3):
+        raise Unsupported(f"{nc} components")
+    if nc == 3:
+        ids = [c[0] for c in comps]
+        if adobe_transform == 0 or (adobe_transform is None and ids == [ord("R"), ord("G"), ord("B")]):
+            raise Unsupported("RGB-coded JPEG")
+    hmax, vmax = max(c[1] for c in comps), max(c[2] for c in comps)
+    if nc == 3:
+        if (comps[0][1], comps[0][2]) != (hmax, vmax) or (comps[1][1:3] != comps[2][1:3]) or comps[1][1:3] != (1, 1) or hmax > 2 or vmax > 2:
+            raise Unsupported("sampling factors outside 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0")
+    else:
+        hmax = vmax = 1                      # a single-component scan is never interleaved (T.81 A.2.2)
+        comps = [(comps[0][0], 1, 1, comps[0][3])]
+    for (cid, h, v, tq) in comps:
+        if (h < hmax or v < vmax) and -(-W * h // hmax) <= 2:
+            raise Unsupported("chroma plane too narrow for the fancy upsampler")
+    return H, W, nc, hmax, vmax, comps
+
+
+def _clean_segment(data, pos):
+    """entropy-coded segment starting at byte `pos` -> (cleaned u8 bytes, restart offsets i32, position of the marker ending it).
+    The segment runs up to the marker that is not RSTn / stuffing; un-stuff, drop the RSTn markers and remember where each restart
+    interval starts in the cleaned stream"""
+    raw = np.frombuffer(data, dtype=np.uint8, offset=pos)
+    ff = np.nonzero(raw[:-1] == 0xFF)[0]
+    nxt = raw[ff + 1]
+    stop = ff[(nxt != 0) & ~((nxt >= 0xD0) & (nxt <= 0xD7)) & (nxt != 0xFF)]
+    end = int(stop[0]) if len(stop) else len(raw)
+    raw = raw[:end]
+    ff = ff[ff < end - 1] if end > 0 else ff[:0]
+    nxt = raw[ff + 1] if len(ff) else nxt[:0]
+    keep = np.ones(len(raw), dtype=bool)
+    stuffed = ff[nxt == 0]
+    keep[stuffed + 1] = False
+    rst = ff[(nxt >= 0xD0) & (nxt <= 0xD7)]
+    keep[rst] = False
+    keep[rst + 1] = False
+    keep[ff[nxt == 0xFF]] = False                   # fill bytes (an 0xFF in front of another 0xFF) are not data (T.81 B.1.1.2)
+    newpos = np.cumsum(keep) - keep                 # position of every original byte in the cleaned stream
+    segs = np.concatenate([[0], newpos[rst]]).astype(np.int32) if len(rst) else np.zeros(1, dtype=np.int32)
+    return raw[keep], segs, pos + end
 
 
 def parse(data):
@@ -140,21 +190,7 @@ def parse(data):
         elif m == 0xD9:
             raise Unsupported("EOI before SOS")
         pos += ln
-    H, W, comps = frame
-    nc = len(comps)
-    if nc not in (1, 3):
-        raise Unsupported(f"{nc} components")
-    if nc == 3:
-        ids = [c[0] for c in comps]
-        if adobe_transform == 0 or (adobe_transform is None and ids == [ord("R"), ord("G"), ord("B")]):
-            raise Unsupported("RGB-coded JPEG")
-    hmax, vmax = max(c[1] for c in comps), max(c[2] for c in comps)
-    if nc == 3:
-        if (comps[0][1], comps[0][2]) != (hmax, vmax) or (comps[1][1:3] != comps[2][1:3]) or comps[1][1:3] != (1, 1) or hmax > 2 or vmax > 2:
-            raise Unsupported("sampling factors outside 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0")
-    else:
-        hmax = vmax = 1                      # a single-component scan is never interleaved (T.81 A.2.2)
-        comps = [(comps[0][0], 1, 1, comps[0][3])]
+    H, W, nc, hmax, vmax, comps = _frame_geometry(frame, adobe_transform)
     p = Parsed()
     p.W, p.H, p.ncomp, p.hmax, p.vmax, p.restart = W, H, nc, hmax, vmax, restart
     p.mcus_x, p.mcus_y = -(-W // (8 * hmax)), -(-H // (8 * vmax))
@@ -163,8 +199,6 @@ def parse(data):
         if tq not in qt or cid not in sel or (0, sel[cid][0]) not in ht or (1, sel[cid][1]) not in ht:
             raise Unsupported("missing table")
         cw, ch = -(-W * h // hmax), -(-H * v // vmax)
-        if (h < hmax or v < vmax) and cw <= 2:
-            raise Unsupported("chroma plane too narrow for the fancy upsampler")
         p.comps.append(dict(h=h, v=v, tq=tq, dc=sel[cid][0], ac=sel[cid][1], bw=p.mcus_x * h, bh=p.mcus_y * v, cw=cw, ch=ch))
     p.quant = np.zeros((4, 64), dtype=np.uint16)
     for k, t in qt.items():
@@ -173,26 +207,7 @@ def parse(data):
     p.tabs = np.zeros((4, TAB_BYTES), dtype=np.uint8)
     for (tc, th), t in ht.items():
         p.tabs[2 * tc + th] = t
-    # entropy-coded segment: up to the marker that is not RSTn / stuffing; un-stuff, drop the RSTn markers and remember where each
-    # restart interval starts in the cleaned stream
-    raw = np.frombuffer(data, dtype=np.uint8, offset=pos)
-    ff = np.nonzero(raw[:-1] == 0xFF)[0]
-    nxt = raw[ff + 1]
-    stop = ff[(nxt != 0) & ~((nxt >= 0xD0) & (nxt <= 0xD7)) & (nxt != 0xFF)]
-    end = int(stop[0]) if len(stop) else len(raw)
-    raw = raw[:end]
-    ff = ff[ff < end - 1] if end > 0 else ff[:0]
-    nxt = raw[ff + 1] if len(ff) else nxt[:0]
-    keep = np.ones(len(raw), dtype=bool)
-    stuffed = ff[nxt == 0]
-    keep[stuffed + 1] = False
-    rst = ff[(nxt >= 0xD0) & (nxt <= 0xD7)]
-    keep[rst] = False
-    keep[rst + 1] = False
-    keep[ff[nxt == 0xFF]] = False                   # fill bytes (an 0xFF in front of another 0xFF) are not data (T.81 B.1.1.2)
-    newpos = np.cumsum(keep) - keep                 # position of every original byte in the cleaned stream
-    p.scan = raw[keep]
-    p.segs = np.concatenate([[0], newpos[rst]]).astype(np.int32) if len(rst) else np.zeros(1, dtype=np.int32)
+    p.scan, p.segs, _ = _clean_segment(data, pos)
     if restart and len(p.segs) < -(-p.mcus_x * p.mcus_y // restart):
         raise Unsupported("restart markers missing")
     return p
@@ -280,4 +295,291 @@ class JpegBatch:
         scan = d[self.off_scan:]
         out, self.last_err = ops.jpeg_decode_batch(params, scan, tabs, segs, quant, B, self.H, self.W, self.total_blocks,
                                                    self.plane_bytes, self.max_blocks, out=out, check=check)
+        return out
+
+
+# ---- multi-scan files: progressive Huffman (T.81 Annex G), multi-scan sequential, and baseline files as one scan ---------------------
+S_IMG, S_MODE, S_NCOMP, S_COMP0, S_SS, S_SE, S_AH, S_AL, S_RESTART, S_SCAN_OFF, S_SCAN_LEN, S_SEG_OFF, S_NSEG = 0, 1, 2, 3, 6, 7, 8, 9, 10, 11, 12, 13, 14
+S_GW, S_GH, S_NTAB, S_TAB0, S_DC0, S_AC0, S_FIRST = 15, 16, 17, 18, 22, 25, 28
+NS = 32
+M_SEQ, M_DC_FIRST, M_DC_REFINE, M_AC_FIRST, M_AC_REFINE = range(5)
+
+
+class Scan:
+    """one scan: `comps` indices into ParsedScans.comps (scan order); `dc` / `ac` per scan component an index into ParsedScans.tabs
+    (None where the scan reads no such table); `data` the cleaned entropy-coded bytes, `segs` the restart offsets into it; the scan walks
+    `gw x gh` units (MCUs when interleaved, else the component's own ceil(cw/8) x ceil(ch/8) blocks), `restart` of them per interval;
+    `level` (from 1): 1 + the highest level of an earlier scan sharing a component and overlapping it spectrally"""
+    __slots__ = ("comps", "ss", "se", "ah", "al", "mode", "dc", "ac", "restart", "data", "segs", "gw", "gh", "level")
+
+
+class ParsedScans:
+    __slots__ = ("W", "H", "ncomp", "comps", "hmax", "vmax", "mcus_x", "mcus_y", "quant", "tabs", "scans", "progressive", "nlevels")
+
+
+def parse_scans(data):
+    """bytes of one JPEG file -> ParsedScans: frame geometry (the `comps` fields of parse(), MCU-padded block grid), quant tables,
+    a deduplicated Huffman table pool and the list of scans.  Takes progressive Huffman (SOF2) and sequential (SOF0 / SOF1) files with
+    one or several scans.  Raises Unsupported for what parse() refuses besides progression, for every progression on which libjpeg
+    warns (jdphuff.c start_pass_phuff_decoder: JWRN_BOGUS_PROGRESSION), and for files whose coefficients 0..9 are not all complete
+    (Al = 0) after the last scan -- libjpeg-turbo block-smooths those (jdcoefct.c smoothing_ok), which the GPU path does not restate."""
+    if data[:2] != b"\xff\xd8":
+        raise Unsupported("not a JPEG")
+    qt, ht = {}, {}
+    tabs, tab_idx = [], {}
+    restart, frame, adobe_transform, progressive = 0, None, None, False
+    p, coef_bits, scans = None, None, []
+    pos, n = 2, len(data)
+    while True:
+        if pos + 2 > n or data[pos] != 0xFF:
+            raise Unsupported("truncated file or marker expected")
+        while pos + 2 < n and data[pos + 1] == 0xFF:
+            pos += 1
+        m = data[pos + 1]
+        pos += 2
+        if m == 0xD9:
+            break
+        if m in (0x01,) or 0xD0 <= m <= 0xD7:
+            continue
+        if pos + 2 > n:
+            raise Unsupported("truncated marker segment")
+        ln = struct.unpack(">H", data[pos:pos + 2])[0]
+        seg = data[pos + 2:pos + ln]
+        if m == 0xDB:
+            if scans:
+                raise Unsupported("quantisation table redefined between scans")
+            i = 0
+            while i < len(seg):
+                pq, tq = seg[i] >> 4, seg[i] & 15
+                i += 1
+                if pq:
+                    t = np.frombuffer(seg[i:i + 128], dtype=">u2").astype(np.uint16)
+                    i += 128
+                else:
+                    t = np.frombuffer(seg[i:i + 64], dtype=np.uint8).astype(np.uint16)
+                    i += 64
+                nat = np.zeros(64, dtype=np.uint16)
+                nat[ZIGZAG] = t
+                qt[tq] = nat
+        elif m == 0xC4:
+            i = 0
+            while i < len(seg):
+                tc, th = seg[i] >> 4, seg[i] & 15
+                bits = np.frombuffer(seg[i + 1:i + 17], dtype=np.uint8)
+                cnt = int(bits.sum())
+                vals = np.frombuffer(seg[i + 17:i + 17 + cnt], dtype=np.uint8)
+                i += 17 + cnt
+                if th > 3 or tc > 1:
+                    raise Unsupported("bad Huffman table slot")
+                t = huff_table(bits, vals)
+                ht[(tc, th)] = tab_idx.setdefault(t.tobytes(), len(tabs))
+                if ht[(tc, th)] == len(tabs):
+                    tabs.append(t)
+        elif m in (0xC0, 0xC1, 0xC2):
+            if frame is not None:
+                raise Unsupported("two frames")
+            prec, H, W, nc = struct.unpack(">BHHB", seg[:6])
+            if prec != 8:
+                raise Unsupported("not 8-bit")
+            frame = (H, W, [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nc)])
+            progressive = m == 0xC2
+        elif m in (0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF):
+            raise Unsupported("lossless / hierarchical / arithmetic JPEG")
+        elif m == 0xDD:
+            restart = struct.unpack(">H", seg[:2])[0]
+        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
+            adobe_transform = seg[11]
+        elif m == 0xDA:
+            if frame is None:
+                raise Unsupported("SOS before SOF")
+            if p is None:
+                p = _scan_frame(frame, adobe_transform, qt)
+                p.progressive = progressive
+                coef_bits = np.full((p.ncomp, 64), -1, dtype=np.int32)
+            ids = [c[0] for c in frame[2]]
+            ns = seg[0]
+            sel = [(seg[1 + 2 * c], seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15) for c in range(ns)]
+            if not 1 <= ns <= 3 or any(cid not in ids for cid, _, _ in sel) or len({cid for cid, _, _ in sel}) != ns:
+                raise Unsupported("bad scan component list")
+            s = Scan()
+            s.comps = [ids.index(cid) for cid, _, _ in sel]
+            s.ss, s.se, s.ah, s.al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+            s.mode = _check_progression(s, progressive, coef_bits)
+            need_dc, need_ac = s.mode in (M_SEQ, M_DC_FIRST), s.mode in (M_SEQ, M_AC_FIRST, M_AC_REFINE)
+            if (need_dc and any((0, td) not in ht for _, td, _ in sel)) or (need_ac and any((1, ta) not in ht for _, _, ta in sel)):
+                raise Unsupported("missing Huffman table")
+            s.dc = [ht[(0, td)] if need_dc else None for _, td, _ in sel]
+            s.ac = [ht[(1, ta)] if need_ac else None for _, _, ta in sel]
+            if len({t for t in s.dc + s.ac if t is not None}) > 4:
+                raise Unsupported("more than four Huffman tables in one scan")
+            if ns == 1:
+                d = p.comps[s.comps[0]]
+                s.gw, s.gh = -(-d["cw"] // 8), -(-d["ch"] // 8)
+            else:
+                s.gw, s.gh = p.mcus_x, p.mcus_y
+            s.restart = restart
+            s.data, s.segs, pos = _clean_segment(data, pos + ln)
+            if restart and len(s.segs) < -(-s.gw * s.gh // restart):
+                raise Unsupported("restart markers missing")
+            s.level = 1 + max([t.level for t in scans if set(t.comps) & set(s.comps) and t.ss <= s.se and s.ss <= t.se], default=0)
+            scans.append(s)
+            continue
+        pos += ln
+    if p is None:
+        raise Unsupported("no scan")
+    if progressive and (coef_bits[:, :10] != 0).any():
+        raise Unsupported("incomplete progression: libjpeg would block-smooth this file")
+    if not progressive and (coef_bits[:, 0] != 0).any():
+        raise Unsupported("component without a scan")
+    p.tabs, p.scans, p.nlevels = tabs, scans, max(s.level for s in scans)
+    return p
+
+
+def _scan_frame(frame, adobe_transform, qt):
+    H, W, nc, hmax, vmax, comps = _frame_geometry(frame, adobe_transform)
+    p = ParsedScans()
+    p.W, p.H, p.ncomp, p.hmax, p.vmax = W, H, nc, hmax, vmax
+    p.mcus_x, p.mcus_y = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    p.comps = []
+    for (cid, h, v, tq) in comps:
+        if tq not in qt:
+            raise Unsupported("missing quantisation table")
+        p.comps.append(dict(h=h, v=v, tq=tq, bw=p.mcus_x * h, bh=p.mcus_y * v, cw=-(-W * h // hmax), ch=-(-H * v // vmax)))
+    p.quant = np.zeros((4, 64), dtype=np.uint16)
+    for k, t in qt.items():
+        if k < 4:
+            p.quant[k] = t
+    return p
+
+
+def _check_progression(s, progressive, coef_bits):
+    """-> the scan's decode mode; tracks coef_bits (component x coefficient: Al of the last scan, -1 = not yet coded) as
+    jdphuff.c start_pass_phuff_decoder does and raises Unsupported wherever libjpeg errors out or warns"""
+    if not progressive:
+        if (s.ss, s.se, s.ah, s.al) != (0, 63, 0, 0):
+            raise Unsupported("sequential scan with a spectral band / successive approximation")
+        if (coef_bits[s.comps, 0] >= 0).any():
+            raise Unsupported("component coded in two sequential scans")
+        coef_bits[s.comps] = 0
+        return M_SEQ
+    bad = s.se != 0 if s.ss == 0 else (s.ss > s.se or s.se > 63 or len(s.comps) != 1)
+    if bad or (s.ah != 0 and s.al != s.ah - 1) or s.al > 13:
+        raise Unsupported("bogus progression")
+    for c in s.comps:
+        cb = coef_bits[c]
+        if s.ss != 0 and cb[0] < 0:
+            raise Unsupported("AC scan before the DC scan")
+        band = cb[s.ss:s.se + 1]
+        if (np.maximum(band, 0) != s.ah).any() or (s.ah == 0 and (band >= 0).any()):
+            raise Unsupported("bogus progression")     # (a first scan over coefficients already coded: libjpeg silently overwrites)
+        band[:] = s.al
+    if s.ss == 0:
+        return M_DC_FIRST if s.ah == 0 else M_DC_REFINE
+    return M_AC_FIRST if s.ah == 0 else M_AC_REFINE
+
+
+class ScanJpegBatch:
+    """host-side descriptor of a batch of equal-geometry JPEGs decoded SCAN BY SCAN (progressive, multi-scan sequential, and baseline
+    files as one sequential scan each: mixed batches decode together).  ONE contiguous blob, read by the kernels in place when pinned:
+        params (B x 64 i32, JpegBatch layout) | scan descriptors (nscans x 32 i32, sorted by dependency level) | restart offsets (i32) |
+        quant tables (B x 256 u16) | Huffman table pool (npool x 1424 B, deduplicated over the batch) | cleaned scans
+    decode() runs one kernel launch per dependency level (self.level_start), then the IDCT and colour kernels of the baseline path."""
+
+    def __init__(self, datas, pool=None, alloc=None):
+        import torch
+        ps = list(pool.map(parse_scans, datas)) if pool is not None else [parse_scans(d) for d in datas]
+        self.last_err = None
+        H, W = ps[0].H, ps[0].W
+        if any((p.H, p.W) != (H, W) for p in ps):
+            raise ValueError("a JPEG batch shares one geometry")
+        B = len(ps)
+        self.B, self.H, self.W = B, H, W
+        pool_idx, pool_tabs, remap = {}, [], []
+        for p in ps:
+            r = []
+            for t in p.tabs:
+                k = t.tobytes()
+                if k not in pool_idx:
+                    pool_idx[k] = len(pool_tabs)
+                    pool_tabs.append(t)
+                r.append(pool_idx[k])
+            remap.append(r)
+        items = sorted((s.level, b, i) for b, p in enumerate(ps) for i, s in enumerate(p.scans))
+        self.nlevels = items[-1][0]
+        self.level_start = np.searchsorted([it[0] for it in items], np.arange(1, self.nlevels + 2)).astype(np.int32)
+        nsc = len(items)
+        nseg = sum(len(s.segs) for p in ps for s in p.scans)
+        padded = lambda n: n + ((-n) % CHUNK or (CHUNK if n == 0 else 0))
+        al = lambda n: (n + 255) & ~255
+        self.off_params, n = 0, al(B * NP * 4)
+        self.off_descs, n = n, n + al(nsc * NS * 4)
+        self.off_segs, n = n, n + al(nseg * 4)
+        self.off_quant, n = n, n + al(B * 256 * 2)
+        self.off_tabs, n = n, n + al(len(pool_tabs) * TAB_BYTES)
+        self.off_scan, n = n, n + sum(padded(len(s.data)) for p in ps for s in p.scans)
+        self.nseg, self.nscans, self.npool, self.nbytes = nseg, nsc, len(pool_tabs), n
+        blob = alloc(n + al(4 * B)) if alloc is not None else torch.empty(n + al(4 * B), dtype=torch.uint8)
+        self.blob = blob[:n]
+        self.err_host = blob[n:n + 4 * B].view(torch.int32)     # the error codes come back into the same (pinned) staging buffer
+        host = self.blob.numpy()
+        host[:self.off_scan] = 0
+        params = host[self.off_params:self.off_params + B * NP * 4].view(np.int32).reshape(B, NP)
+        descs = host[self.off_descs:self.off_descs + nsc * NS * 4].view(np.int32).reshape(nsc, NS)
+        segs = host[self.off_segs:self.off_segs + nseg * 4].view(np.int32)
+        quant = host[self.off_quant:self.off_quant + B * 512].view(np.uint16).reshape(B, 256)
+        tabs = host[self.off_tabs:self.off_tabs + len(pool_tabs) * TAB_BYTES].reshape(-1, TAB_BYTES)
+        scan = host[self.off_scan:]
+        for i, t in enumerate(pool_tabs):
+            tabs[i] = t
+        blk_off = plane_off = 0
+        self.max_blocks = 0
+        for b, p in enumerate(ps):
+            r = params[b]
+            r[P_QUANT_OFF], r[P_NCOMP], r[P_W], r[P_H], r[P_HMAX], r[P_VMAX] = b * 256, p.ncomp, W, H, p.hmax, p.vmax
+            r[P_MCUS_X], r[P_MCUS_Y] = p.mcus_x, p.mcus_y
+            nblk = 0
+            for c, d in enumerate(p.comps):
+                o = P_COMP0 + c * P_CSTRIDE
+                r[o:o + 11] = [d["h"], d["v"], d["tq"], 0, 0, d["bw"], d["bh"], d["cw"], d["ch"], blk_off + nblk, plane_off]
+                nblk += d["bw"] * d["bh"]
+                plane_off += (d["bw"] * 8 * d["bh"] * 8 + 15) & ~15
+            self.max_blocks = max(self.max_blocks, nblk)
+            blk_off += nblk
+            quant[b] = p.quant.reshape(-1)
+        scan_off = seg_off = 0
+        for j, (_, b, i) in enumerate(items):
+            s = ps[b].scans[i]
+            local = sorted({t for t in s.dc + s.ac if t is not None})
+            d = descs[j]
+            d[S_IMG], d[S_MODE], d[S_NCOMP] = b, s.mode, len(s.comps)
+            d[S_COMP0:S_COMP0 + len(s.comps)] = s.comps
+            d[S_SS], d[S_SE], d[S_AH], d[S_AL], d[S_RESTART] = s.ss, s.se, s.ah, s.al, s.restart
+            d[S_SCAN_OFF], d[S_SCAN_LEN], d[S_SEG_OFF], d[S_NSEG] = scan_off, padded(len(s.data)), seg_off, len(s.segs)
+            d[S_GW], d[S_GH], d[S_NTAB], d[S_FIRST] = s.gw, s.gh, len(local), int(i == 0)
+            d[S_TAB0:S_TAB0 + len(local)] = [remap[b][t] for t in local]
+            d[S_DC0:S_DC0 + len(s.comps)] = [local.index(t) if t is not None else 0 for t in s.dc]
+            d[S_AC0:S_AC0 + len(s.comps)] = [local.index(t) if t is not None else 0 for t in s.ac]
+            scan[scan_off:scan_off + len(s.data)] = s.data
+            scan[scan_off + len(s.data):scan_off + padded(len(s.data))] = 0
+            segs[seg_off:seg_off + len(s.segs)] = s.segs
+            scan_off += padded(len(s.data))
+            seg_off += len(s.segs)
+        self.params, self.descs, self.tabs, self.scan = params, descs, tabs.reshape(-1), scan     # host views (tests)
+        self.total_blocks, self.plane_bytes = blk_off, plane_off
+
+    def decode(self, device, out=None, check=True):
+        """-> (B, H, W, 3) u8 device tensor on the current stream; the contract of JpegBatch.decode (last_err, err_host)"""
+        import torch
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            return self._decode(self.blob if self.blob.is_pinned() else self.blob.to(dev, non_blocking=True), out, check)
+
+    def _decode(self, d, out, check):
+        from . import ops
+        B = self.B
+        view = lambda off, nbytes: d[off:off + nbytes]
+        out, self.last_err = ops.jpeg_decode_scans_batch(
+            view(self.off_params, B * NP * 4), view(self.off_descs, self.nscans * NS * 4), d[self.off_scan:],
+            view(self.off_tabs, self.npool * TAB_BYTES), view(self.off_segs, max(4, self.nseg * 4)), view(self.off_quant, B * 512),
+            self.level_start, B, self.H, self.W, self.total_blocks, self.plane_bytes, self.max_blocks, out=out, check=check)
         return out

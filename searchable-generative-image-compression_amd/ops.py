@@ -4,6 +4,7 @@ import ctypes
 import json
 import os
 
+import numpy as np
 import torch
 
 from ._lib import call, check, launch_opts, lib, require_gpu
@@ -988,6 +989,30 @@ def jpeg_decode_batch(params, scan, tabs, segs, quant, B, H, W, total_blocks, pl
     err = torch.empty(B, dtype=torch.int32, device=dev)
     call("sgic_jpeg_decode_batch", _p(params), _p(scan), _p(tabs), _p(segs), _p(quant), _p(wparams), _p(wquant), _p(coef), _p(planes), _p(out),
          _p(err), B, H, W, int(max_blocks))
+    if check:
+        e = err.cpu().numpy()
+        if e.any():
+            raise RuntimeError(f"corrupt JPEG stream(s) in the batch: error codes {e.tolist()}")
+    return out, err
+
+
+def jpeg_decode_scans_batch(params, descs, scan, tabs, segs, quant, level_start, B, H, W, total_blocks, plane_bytes, max_blocks, out=None,
+                            check=True):
+    """multi-scan (progressive / sequential / mixed) JPEG batch -> (B,H,W,3) u8 on the device (csrc/jpeg.hip jpeg_scan_kernel, one launch
+    per dependency level; descriptors built by sgic_amd.jpeg.ScanJpegBatch).  level_start: host int32 array, nlevels + 1 entries"""
+    require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if not params.is_cuda else params.device   # inputs may be pinned host memory
+    coef = torch.empty(total_blocks * 64, dtype=torch.int16, device=dev)
+    wparams = torch.empty(B * 64, dtype=torch.int32, device=dev)
+    wquant = torch.empty(B * 256, dtype=torch.int16, device=dev)
+    planes = torch.empty(max(16, plane_bytes), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    assert out.shape == (B, H, W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+    err = torch.empty(B, dtype=torch.int32, device=dev)
+    ls = np.ascontiguousarray(level_start, dtype=np.int32)
+    call("sgic_jpeg_decode_scans_batch", _p(params), _p(descs), _p(scan), _p(tabs), _p(segs), _p(quant), _p(wparams), _p(wquant), _p(coef),
+         _p(planes), _p(out), _p(err), B, H, W, _cl(total_blocks), int(max_blocks), ctypes.c_void_p(ls.ctypes.data), len(ls) - 1)
     if check:
         e = err.cpu().numpy()
         if e.any():

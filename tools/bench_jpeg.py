@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """GPU JPEG decode (csrc/jpeg.hip) vs Pillow on the host: a batch of 32 files 256x256, noise (the CLI benchmark's worst case for an
-entropy decoder) and natural-like content.  Run under `rocprofv3 --kernel-trace --stats` for the per-kernel split."""
+entropy decoder) and natural-like content, and 32 natural-like 256x256 files saved PROGRESSIVE (libjpeg's standard 10-scan script;
+ScanJpegBatch: one jpeg_scan_kernel launch per dependency level) beside the same images saved baseline.  Run under
+`rocprofv3 --kernel-trace --stats` for the per-kernel split."""
 import io
 import os
 import sys
@@ -22,6 +24,9 @@ noise = ((synth_images(32, 256, 256, 3) * 0.5 + 0.5) * 255).round().byte().permu
 sets = {"noise_q90": [(noise[i], dict(quality=90)) for i in range(32)],
         "natural_q90": [(jpeg_cases.natural_like(256, 256, rng), dict(quality=90)) for i in range(32)],
         "natural_q75_1024": [(jpeg_cases.natural_like(1024, 1024, rng), dict(quality=75)) for i in range(8)]}
+prog = [jpeg_cases.natural_like(256, 256, rng) for i in range(32)]
+sets["natural_q90_progressive"] = [(im, dict(quality=90, progressive=True)) for im in prog]
+sets["natural_q90_progressive_same_images_baseline"] = [(im, dict(quality=90)) for im in prog]
 for name, items in sets.items():
     datas = []
     for img, kw in items:
@@ -33,7 +38,7 @@ for name, items in sets.items():
         np.asarray(Image.open(io.BytesIO(d)).convert("RGB"))
     t_pil = (time.perf_counter() - t0) / len(datas)
     t0 = time.perf_counter()
-    b = J.JpegBatch(datas)
+    b = (J.ScanJpegBatch if "progressive" in name and "baseline" not in name else J.JpegBatch)(datas)
     t_parse = (time.perf_counter() - t0) / len(datas)
     out = b.decode("cuda:0")
     torch.cuda.synchronize()
@@ -45,4 +50,4 @@ for name, items in sets.items():
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
     print(f"{name}: {len(datas)} files, {sum(map(len, datas)) / len(datas) / 1024:.1f} KiB each | Pillow {t_pil * 1e3:.2f} ms/file on one core | "
-          f"host parse {t_parse * 1e3:.2f} ms/file | GPU batch decode {ms:.2f} ms ({ms / len(datas):.3f} ms/file, one wave per file)", flush=True)
+          f"host parse {t_parse * 1e3:.2f} ms/file | GPU batch decode {ms:.2f} ms ({ms / len(datas):.3f} ms/file)", flush=True)
