@@ -318,6 +318,29 @@ int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, in
 int sgic_u8hwc_to_f32chw_pad(const uint8_t *d_in, float *d_out, int B, int H, int W, int pl, int pr, int pt, int pb,
                              sgic_stream_t stream);
 
+/* Ragged batches: images of different sizes that pad to one geometry share a batch (sgic_amd/ingest.py pad_to).  The per-image
+ * geometry is a HOST array, validated on the host and handed to the kernels as launch arguments (32 images per launch).
+ *
+ * Ragged ingest: d_in is a u8 canvas (B, Hc, Wc, 3) with image b at its top left, extent h_hw[2b] x h_hw[2b+1] (host int32, B x 2;
+ * 1 <= h <= min(Hc, OH), 1 <= w <= min(Wc, OW)) -> d_out (B, 3, OH, OW) fp32: ToTensor, *2-1 and replicate padding from the
+ * image's OWN right / bottom edge.  Bit-identical per image to sgic_u8hwc_to_f32chw_pad(pl = pt = 0) on that image alone. */
+int sgic_u8canvas_to_f32chw_pad(const uint8_t *d_in, const int32_t *h_hw, float *d_out, int B, int Hc, int Wc, int OH, int OW,
+                                sgic_stream_t stream);
+/* Pillow's bicubic tables of an in_size -> out_size resample built on the device, in double precision in the operation order of
+ * Pillow's precompute_coeffs (sgic_amd/clip.py pil_coeffs): d_bounds (out_size x 2 int32: first input index, count), d_kk
+ * (out_size x ksize 22-bit fixed-point int32, zero past the count); ksize = ceil(2 * max(in_size / out_size, 1)) * 2 + 1 (checked). */
+int sgic_clip_resize_coeffs(int in_size, int out_size, int ksize, int32_t *d_bounds, int32_t *d_kk, sgic_stream_t stream);
+/* Ragged CLIP preprocessing: image b is the top-left H x W region of d_x[b] (strides as sgic_clip_preprocess), with its own resize
+ * geometry h_geo[6b .. 6b+5] = (H, W, OH, OW, top, left) (host int32, B x 6; sgic_amd/clip.py resize_geometry) -> d_out (B, 3, S, S),
+ * every image bit-identical to sgic_clip_preprocess on it alone.  The coefficient tables are built on the device.  d_work: a device
+ * workspace (16-byte aligned) of at least the *bytes sgic_clip_preprocess_ragged_workspace returns (host-only, takes no stream); per
+ * image, in batch order: bounds_h (OW x 2 int32), kk_h (OW x ksize_h), bounds_v (OH x 2), kk_v (OH x ksize_v), the u8 image (3 x H x W)
+ * and the horizontal pass over the S cropped columns (3 x H x S), each 16-byte aligned. */
+int sgic_clip_preprocess_ragged_workspace(int B, const int32_t *h_geo, int S, size_t *bytes);
+int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_stride, int ldx, int B, const int32_t *h_geo, int S,
+                                const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
+                                sgic_stream_t stream);
+
 /* Baseline JPEG decode of a batch of B equal-geometry files to RGB u8 HWC (B, H, W, 3) on the device -- the pixel decode inside
  * the reference's Test_Dataset (`Image.open(path).convert("RGB")`, compress.py:151-168), bit-exact with Pillow / libjpeg-turbo's
  * default decoder (islow IDCT, fancy chroma upsampling, jdcolor tables).  The host parses markers and strips byte stuffing

@@ -70,7 +70,8 @@ def ptr(t):
     return c_void_p(t.ctypes.data)
 
 
-_NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profiler_create", "sgic_profiler_begin", "sgic_profiler_end"}
+_NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profiler_create", "sgic_profiler_begin", "sgic_profiler_end",
+              "sgic_clip_preprocess_ragged_workspace"}
 
 
 def call(name, *args):

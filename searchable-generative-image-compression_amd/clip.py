@@ -91,9 +91,13 @@ class ClipHIP:
             self._coef[key] = (OH, OW, top, left, d(bh), d(kh), ksh, d(bv), d(kv), ksv)
         return self._coef[key]
 
-    def preprocess(self, x, H=None, W=None):
+    def preprocess(self, x, H=None, W=None, hw=None):
         """x (B,3,Hp,Wp) fp32 in [-1,1]; the top-left HxW region of every image is the real (unpadded)
-        image (compress.py:266 feeds the UNPADDED image to CLIP).  -> (B,3,S,S) normalised."""
+        image (compress.py:266 feeds the UNPADDED image to CLIP).  -> (B,3,S,S) normalised.
+        hw: (B, 2) per-image extents instead of one H x W (images of different sizes that pad to one geometry): image b is
+        the top-left hw[b] region of x[b], on its own resize geometry -- bit-identical to preprocess(x[b:b+1], *hw[b])."""
+        if hw is not None:
+            return self._preprocess_ragged(x, hw)
         B, _, Hp, Wp = x.shape
         H, W = H or Hp, W or Wp
         S = self.cfg.image_size
@@ -106,6 +110,23 @@ class ClipHIP:
              B, H, W, OH, OW, S, top, left, ops._p(bh), ops._p(kh), ksh, ops._p(bv), ops._p(kv), ksv,
              self.mean.ctypes.data_as(ctypes.c_void_p), self.std.ctypes.data_as(ctypes.c_void_p), ops._p(u8), ops._p(th),
              ops._p(out))
+        return out
+
+    def _preprocess_ragged(self, x, hw):
+        """the device builds every image's coefficient tables (sgic_clip_preprocess_ragged): six ints per image leave the host"""
+        import ctypes
+        B, _, Hp, Wp = x.shape
+        hw = np.asarray(hw, dtype=np.int64).reshape(B, 2)
+        if (hw <= 0).any() or (hw[:, 0] > Hp).any() or (hw[:, 1] > Wp).any():
+            raise ValueError(f"extents {hw.tolist()} outside the {Hp}x{Wp} batch")
+        S = self.cfg.image_size
+        geo = np.array([(h, w) + resize_geometry(h, w, S) for h, w in hw.tolist()], dtype=np.int32)
+        nbytes = ctypes.c_size_t(0)
+        call("sgic_clip_preprocess_ragged_workspace", B, geo, S, ctypes.byref(nbytes))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=x.device)
+        call("sgic_clip_preprocess_ragged", ops._p(x), ctypes.c_long(x.stride(0)), ctypes.c_long(x.stride(1)), int(x.stride(2)), B, geo, S,
+             self.mean, self.std, ops._p(work), ctypes.c_size_t(nbytes.value), ops._p(out))
         return out
 
     def tower(self, pre):
@@ -124,8 +145,8 @@ class ClipHIP:
         z = ops.gemm(pooled, self.projT)
         return ops.l2norm_u8(z)
 
-    def encode(self, x, H=None, W=None):
-        return self.tower(self.preprocess(x, H, W))
+    def encode(self, x, H=None, W=None, hw=None):
+        return self.tower(self.preprocess(x, H, W, hw))
 
 
 class ClipTextHIP:

@@ -177,9 +177,9 @@ class ClipCodec:
         unit, _ = self.model.encode(img_chw.to(self.device).float().contiguous()[None])
         return unit[0].cpu().numpy().astype("float32")
 
-    def batch_to_codes(self, x, H=None, W=None):
-        """(B,3,Hp,Wp) device batch -> (unit (B,D) device, u8 (B,D) device)"""
-        return self.model.encode(x, H, W)
+    def batch_to_codes(self, x, H=None, W=None, hw=None):
+        """(B,3,Hp,Wp) device batch -> (unit (B,D) device, u8 (B,D) device); hw: per-image extents (ClipHIP.preprocess)"""
+        return self.model.encode(x, H, W, hw)
 
     def meta(self, dim):
         return {"model_id": self.model_name, "dim": int(dim), "quant": "u8_symmetric_-1_1", "codec": "zstd", "zstd_level": 19}

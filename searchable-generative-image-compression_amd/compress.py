@@ -4,7 +4,9 @@ save_dir/{bitstreams/<stem>.c2df, clip_vecs/<stem>.npy, faiss/index.faiss, faiss
 MI355X path.  Differences, all MI355X-native by design:
   * the shard is STREAMED: header-only size pass, bounded read-ahead of decoded u8 batches in pinned memory, u8 H2D
     copies overlapped with the previous batch's GPU work, ToTensor / *2-1 / replicate padding on the GPU (ingest.py);
-  * images of equal size are batched (--batch_size, default 32) instead of B=1;
+  * images that pad to the same geometry are batched (--batch_size, default 32) instead of B=1: each keeps its own extent
+    through decode, padding and CLIP preprocessing, so the output bytes are those of B=1; a batch holds at most
+    4 x batch_size tiles of 256^2 (ingest.plan_batches), so large images come in smaller batches;
   * multi-GPU: one process per GPU (torchrun or `bench.py`-style launch), every rank loads its own weights (no DDP
     broadcast, compress.py:242), takes a contiguous shard of the sorted file list, and the CLIP vectors are
     all-gathered with RCCL instead of going through *.npy files on a shared file system (compress.py:295-306);
@@ -165,22 +167,22 @@ def main(argv=None):
 
     def write_out(job):
         """host side of one batch: .c2df container + clip vector per image (compress.py:268-291)"""
-        h, batch, pad, copied = job
+        h, batch, copied = job
         copied.synchronize()
         if batch.jpeg is not None:            # decoded on the GPU: a corrupt entropy-coded segment shows up as an error code
             codes = batch.jpeg.err_host.numpy()[:len(batch.paths)]          # pinned, filled on the copy stream ahead of `copied`
             if codes.any():
                 raise RuntimeError(f"corrupt JPEG data in {[p for p, c in zip(batch.paths, codes) if c]} (codes {codes[codes != 0].tolist()})")
         batch.release()                       # the pinned u8 buffer goes back to the decode threads
-        pl, pr, pt, pb = pad
         for j, (i, streams) in enumerate(zip(batch.indices, pipe.finish(h))):
+            ih, iw = int(batch.hw[j, 0]), int(batch.hw[j, 1])
             stem = stem_of(mine[i])
             enc = pipe.enc_result(h, j, streams)
             enc["clip_stream"] = streams["clip_stream"]
             enc["clip_meta"] = clip_meta
             header = {"version": 2, "model_id": clip_meta["model_id"], "embed_dim": int(ccfg.embed_dim),
-                      "quant_type": "u8_symmetric_-1_1", "image_hw": [int(batch.H), int(batch.W)],
-                      "padding": [int(pl), int(pr), int(pt), int(pb)]}
+                      "quant_type": "u8_symmetric_-1_1", "image_hw": [ih, iw],
+                      "padding": [int(v) for v in get_padding_size(ih, iw, p=256)]}
             vecs[i] = streams["clip_unit"]
             writes.append(io_pool.submit(_write_outputs, os.path.join(bit_dir, f"{stem}.c2df"), pack_c2df(enc, header),
                                          os.path.join(clip_dir, f"{stem}.npy"), vecs[i].copy()))
@@ -193,7 +195,7 @@ def main(argv=None):
     loader = None
     try:
         loader = ShardLoader(mine, args.batch_size, workers=args.workers, depth=args.prefetch,
-                             gpu_progressive=True if args.gpu_progressive_jpeg else None)
+                             gpu_progressive=True if args.gpu_progressive_jpeg else None, pad_to=256)
         # two-deep pipeline: the GPU works on batch k+1 while the host packs and writes batch k, and the decode threads
         # are already filling the pinned buffers of batches k+2 .. k+1+prefetch
         pending = None
@@ -206,12 +208,14 @@ def main(argv=None):
             t_b = time.perf_counter()
             # one batch AHEAD: the next batch's GPU JPEG decode (or H2D copy) is enqueued before this batch's kernels, so it runs under them
             ntok = ingest.start(nxt) if nxt is not None else None
-            pad = get_padding_size(batch.H, batch.W, p=256)                    # compress.py:257
-            x, copied = ingest.finish(tok, pad)                                # ToTensor*2-1 + replicate pad on the GPU
+            pad = get_padding_size(batch.H, batch.W, p=256)                    # compress.py:257 (of the canvas: the largest extents)
+            ragged = bool((batch.hw != (batch.H, batch.W)).any())             # images of different sizes in one padded geometry
+            x, copied = ingest.finish(tok, pad, hw=batch.hw if ragged else None)   # ToTensor*2-1 + replicate pad on the GPU
             t_c = time.perf_counter()
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
-            h = pipe.submit(x, clip_hw=(batch.H, batch.W))   # CLIP sees the UNPADDED top-left H x W region (compress.py:266)
+            # CLIP sees the UNPADDED top-left region of every image (compress.py:266)
+            h = pipe.submit(x, hw=batch.hw) if ragged else pipe.submit(x, clip_hw=(batch.H, batch.W))
             ev1 = torch.cuda.Event(enable_timing=True)
             ev1.record()
             gpu_evs.append((ev0, ev1))
@@ -222,7 +226,7 @@ def main(argv=None):
             for k, v in (("wait_loader", t_b - t_a), ("ingest", t_c - t_b), ("submit", t_d - t_c), ("write_out_incl_gpu_wait", t_e - t_d)):
                 host_ms[k] = host_ms.get(k, 0.0) + v * 1e3
             host_ms["batches"] = host_ms.get("batches", 0) + 1
-            pending = (h, batch, pad, copied)
+            pending = (h, batch, copied)
             batch, tok = nxt, ntok
         if pending is not None:
             write_out(pending)

@@ -574,6 +574,7 @@ __device__ __forceinline__ int jpg_chroma(const unsigned char *pl, int stride, i
   return (cur * 3 + 3 * r0[c - 1] + r1[c - 1] + 8) >> 4;
 }
 
+// out is a (B, H, W, 3) canvas: image img (its own P_W x P_H, at most H x W) lands at its top left; the rest is not written
 __global__ void jpeg_color_kernel(const int *__restrict__ params, const unsigned char *__restrict__ planes, unsigned char *__restrict__ out,
                                   int H, int W) {
   const int img = blockIdx.y;
@@ -581,8 +582,9 @@ __global__ void jpeg_color_kernel(const int *__restrict__ params, const unsigned
   const int ncomp = P[P_NCOMP];
   const int *C0 = P + P_COMP0, *C1 = C0 + P_CSTRIDE, *C2 = C1 + P_CSTRIDE;
   const int hmax = P[P_HMAX], vmax = P[P_VMAX];
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < (long)H * W; t += (long)gridDim.x * blockDim.x) {
-    const int y = (int)(t / W), x = (int)(t - (long)y * W);
+  const int w = min(P[P_W], W), h = min(P[P_H], H);
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < (long)h * w; t += (long)gridDim.x * blockDim.x) {
+    const int y = (int)(t / w), x = (int)(t - (long)y * w);
     const int yy = planes[(size_t)C0[10] + (size_t)y * (C0[5] * 8) + x];
     int r = yy, g = yy, b = yy;
     if (ncomp == 3) {
@@ -597,7 +599,7 @@ __global__ void jpeg_color_kernel(const int *__restrict__ params, const unsigned
       g = min(max(g, 0), 255);
       b = min(max(b, 0), 255);
     }
-    unsigned char *o = out + ((size_t)img * H * W + (size_t)t) * 3;
+    unsigned char *o = out + (((size_t)img * H + y) * W + x) * 3;
     o[0] = (unsigned char)r;
     o[1] = (unsigned char)g;
     o[2] = (unsigned char)b;

@@ -665,3 +665,271 @@ extern "C" int sgic_u8hwc_to_f32chw_pad(const uint8_t *d_in, float *d_out, int B
   u8hwc_to_f32chw_pad_kernel<<<ew_grid((long)B * 3 * OH * OW), 256, 0, to_stream(stream)>>>(d_in, d_out, B, H, W, pl, pt, OH, OW);
   return sgic::check_launch("u8hwc_to_f32chw_pad_kernel");
 }
+
+// ------------------------------------------------------------------------------------------------
+// Ragged batches: images of different sizes that pad to one geometry (ingest.py pad_to) share a batch.  The per-image
+// geometry travels as KERNEL ARGUMENTS (host arrays, validated here, up to RAGGED_CHUNK images per launch): there is no H2D
+// copy to schedule, and no extent the host has not bounds-checked reaches a kernel.
+// ------------------------------------------------------------------------------------------------
+#define RAGGED_CHUNK 32
+
+struct RaggedExtents {
+  int hw[RAGGED_CHUNK][2];   // (h, w) of image j of the chunk
+};
+
+// u8 canvas (B, Hc, Wc, 3) with image b at its top left, extent (h_b, w_b) -> (B, 3, OH, OW) fp32: ToTensor, *2-1 and replicate
+// padding from the image's OWN right / bottom edge.  The operation order of u8hwc_to_f32chw_pad_kernel: bit-identical to it per image.
+__global__ void u8canvas_to_f32chw_pad_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, RaggedExtents ext, int Hc, int Wc,
+                                              int OH, int OW) {
+  const int b = blockIdx.y;
+  const int h = ext.hw[b][0], w = ext.hw[b][1];
+  const uint8_t *src = in + (long)b * Hc * Wc * 3;
+  float *dst = out + (long)b * 3 * OH * OW;
+  const long total = 3L * OH * OW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ox = (int)(i % OW);
+    const long t = i / OW;
+    const int oy = (int)(t % OH);
+    const int c = (int)(t / OH);
+    const int sy = min(oy, h - 1), sx = min(ox, w - 1);
+    const float v = (float)src[((long)sy * Wc + sx) * 3 + c];
+    dst[i] = __fdiv_rn(v, 255.0f) * 2.0f - 1.0f;
+  }
+}
+
+extern "C" int sgic_u8canvas_to_f32chw_pad(const uint8_t *d_in, const int32_t *h_hw, float *d_out, int B, int Hc, int Wc, int OH, int OW,
+                                           sgic_stream_t stream) {
+  SGIC_REQUIRE(d_in && h_hw && d_out && B > 0 && Hc > 0 && Wc > 0 && OH > 0 && OW > 0, "args");
+  for (int b = 0; b < B; b++) {
+    const int h = h_hw[2 * b], w = h_hw[2 * b + 1];
+    SGIC_REQUIRE(h > 0 && w > 0 && h <= Hc && w <= Wc && h <= OH && w <= OW, "extent outside the canvas or the padded geometry");
+  }
+  hipStream_t st = to_stream(stream);
+  const long per = 3L * OH * OW;
+  const unsigned gx = (unsigned)std::min((per + 255) / 256, 2048L);
+  for (int c0 = 0; c0 < B; c0 += RAGGED_CHUNK) {
+    const int n = std::min(RAGGED_CHUNK, B - c0);
+    RaggedExtents ext{};
+    for (int j = 0; j < n; j++) {
+      ext.hw[j][0] = h_hw[2 * (c0 + j)];
+      ext.hw[j][1] = h_hw[2 * (c0 + j) + 1];
+    }
+    u8canvas_to_f32chw_pad_kernel<<<dim3(gx, n), 256, 0, st>>>(d_in + (long)c0 * Hc * Wc * 3, d_out + (long)c0 * per, ext, Hc, Wc, OH, OW);
+    const int rc = sgic::check_launch("u8canvas_to_f32chw_pad_kernel");
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ragged CLIP preprocessing: every image of the batch has its own resize geometry (H, W, OH, OW, top, left) and its own
+// Pillow bicubic tables, BUILT ON THE DEVICE in double precision in the operation order of Pillow's precompute_coeffs +
+// normalize_coeffs_8bpc (clip.py pil_coeffs; this file is built with -ffp-contract=off and the divisions are correctly
+// rounded), so only six ints per image leave the host.  The pixel passes are those of sgic_clip_preprocess, per image, the
+// horizontal one restricted to the S columns the centre crop keeps: bit-identical to sgic_clip_preprocess on the image alone.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double pil_bicubic(double x) {
+  const double a = -0.5;
+  x = fabs(x);
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+  if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * a;
+  return 0.0;
+}
+
+// Pillow's (bounds, 22-bit ints) for output index xx of an in_size -> out_size bicubic resample; the kk row is zero past its
+// count, as in pil_coeffs
+__device__ void pil_coeff_row(int in_size, int out_size, int ksize, int xx, int *__restrict__ bounds, int *__restrict__ kk) {
+  const double scale = __ddiv_rn((double)in_size, (double)out_size);
+  const double fscale = scale > 1.0 ? scale : 1.0;
+  const double support = 2.0 * fscale;
+  const double ss = __ddiv_rn(1.0, fscale);
+  const double center = ((double)xx + 0.5) * scale;
+  int xmin = (int)(center - support + 0.5);
+  xmin = max(xmin, 0);
+  int xmax = (int)(center + support + 0.5);
+  xmax = min(min(xmax, in_size) - xmin, ksize);
+  double ww = 0.0;
+  for (int x = 0; x < xmax; x++) ww += pil_bicubic(((double)(x + xmin) - center + 0.5) * ss);
+  int *k = kk + (long)xx * ksize;
+  for (int x = 0; x < ksize; x++) {
+    int q = 0;
+    if (x < xmax) {
+      double v = pil_bicubic(((double)(x + xmin) - center + 0.5) * ss);
+      if (ww != 0.0) v = __ddiv_rn(v, ww);
+      q = v < 0.0 ? (int)(-0.5 + v * 4194304.0) : (int)(0.5 + v * 4194304.0);
+    }
+    k[x] = q;
+  }
+  bounds[2 * xx] = xmin;
+  bounds[2 * xx + 1] = xmax;
+}
+
+__global__ void pil_coeffs_kernel(int in_size, int out_size, int ksize, int *__restrict__ bounds, int *__restrict__ kk) {
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (xx < out_size) pil_coeff_row(in_size, out_size, ksize, xx, bounds, kk);
+}
+
+static int pil_ksize(int in_size, int out_size) {   // clip.py pil_coeffs: int(ceil(2 * max(in / out, 1))) * 2 + 1
+  const double scale = (double)in_size / (double)out_size;
+  return (int)std::ceil(2.0 * (scale > 1.0 ? scale : 1.0)) * 2 + 1;
+}
+
+extern "C" int sgic_clip_resize_coeffs(int in_size, int out_size, int ksize, int32_t *d_bounds, int32_t *d_kk, sgic_stream_t stream) {
+  SGIC_REQUIRE(d_bounds && d_kk && in_size > 0 && out_size > 0, "args");
+  SGIC_REQUIRE(ksize == pil_ksize(in_size, out_size), "ksize");
+  pil_coeffs_kernel<<<cdiv(out_size, 64), 64, 0, to_stream(stream)>>>(in_size, out_size, ksize, d_bounds, d_kk);
+  return sgic::check_launch("pil_coeffs_kernel");
+}
+
+struct ClipRaggedImg {
+  int g[8];            // H, W, OH, OW, top, left, ksize_h, ksize_v
+  long long off[6];    // workspace byte offsets: bounds_h (OW x 2 int32), kk_h (OW x ksize_h), bounds_v (OH x 2), kk_v (OH x ksize_v),
+                       // the u8 copy (3 x H x W) and the horizontal-pass output (3 x H x S)
+};
+
+struct ClipRaggedChunk {
+  ClipRaggedImg img[RAGGED_CHUNK];
+};
+
+// image b's slice of the workspace, at byte offset *off (advanced past it): its four tables, its u8 copy, its horizontal-pass output,
+// each 16-byte aligned
+static int clip_ragged_image(const int32_t *q, int S, long long *off, ClipRaggedImg *m) {
+  const int H = q[0], W = q[1], OH = q[2], OW = q[3], top = q[4], left = q[5];
+  SGIC_REQUIRE(H > 0 && W > 0 && OH > 0 && OW > 0 && H <= 65535 && W <= 65535 && OH <= 65535 && OW <= 65535, "image geometry");
+  SGIC_REQUIRE(top >= 0 && left >= 0 && top + S <= OH && left + S <= OW, "crop window");
+  m->g[0] = H, m->g[1] = W, m->g[2] = OH, m->g[3] = OW, m->g[4] = top, m->g[5] = left;
+  m->g[6] = pil_ksize(W, OW), m->g[7] = pil_ksize(H, OH);
+  const long long size[6] = {8LL * OW, 4LL * OW * m->g[6], 8LL * OH, 4LL * OH * m->g[7], 3LL * H * W, 3LL * H * S};
+  for (int k = 0; k < 6; k++) {
+    m->off[k] = *off;
+    *off += (size[k] + 15) & ~15LL;
+  }
+  return 0;
+}
+
+__global__ void clip_ragged_coeffs_kernel(ClipRaggedChunk ch, uint8_t *__restrict__ work) {
+  const ClipRaggedImg &m = ch.img[blockIdx.y];
+  const int H = m.g[0], W = m.g[1], OH = m.g[2], OW = m.g[3];
+  int *bh = reinterpret_cast<int *>(work + m.off[0]), *kh = reinterpret_cast<int *>(work + m.off[1]);
+  int *bv = reinterpret_cast<int *>(work + m.off[2]), *kv = reinterpret_cast<int *>(work + m.off[3]);
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < OW + OH; t += gridDim.x * blockDim.x) {
+    if (t < OW) pil_coeff_row(W, OW, m.g[6], t, bh, kh);
+    else pil_coeff_row(H, OH, m.g[7], t - OW, bv, kv);
+  }
+}
+
+__global__ void clip_ragged_to_u8_kernel(const float *__restrict__ x, long img_stride, long ch_stride, int ldx, ClipRaggedChunk ch,
+                                         uint8_t *__restrict__ work) {
+  const ClipRaggedImg &m = ch.img[blockIdx.y];
+  const int H = m.g[0], W = m.g[1];
+  const float *src = x + (long)blockIdx.y * img_stride;
+  uint8_t *out = work + m.off[4];
+  const long total = 3L * H * W;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % W);
+    const long t = i / W;
+    const int yy = (int)(t % H);
+    const int c = (int)(t / H);
+    float v = src[c * ch_stride + (long)yy * ldx + xx];
+    v = fminf(fmaxf(v, -1.f), 1.f);
+    v = (v * 0.5f + 0.5f) * 255.f;
+    out[i] = (uint8_t)v;  // .byte() truncates
+  }
+}
+
+__global__ void clip_ragged_resize_h_kernel(ClipRaggedChunk ch, int S, uint8_t *__restrict__ work) {
+  const ClipRaggedImg &m = ch.img[blockIdx.y];
+  const int H = m.g[0], W = m.g[1], left = m.g[5], ksize = m.g[6];
+  const int *bounds = reinterpret_cast<const int *>(work + m.off[0]), *kk = reinterpret_cast<const int *>(work + m.off[1]);
+  const uint8_t *in = work + m.off[4];
+  uint8_t *out = work + m.off[5];
+  const long total = 3L * H * S;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ox = (int)(i % S) + left;
+    const long row = i / S;  // c*H + y
+    const int xmin = bounds[2 * ox], cnt = bounds[2 * ox + 1];
+    int ss = 1 << 21;
+    const uint8_t *p = in + row * W + xmin;
+    const int *k = kk + (long)ox * ksize;
+    for (int x = 0; x < cnt; x++) ss += (int)p[x] * k[x];
+    ss >>= 22;
+    out[i] = (uint8_t)(ss < 0 ? 0 : (ss > 255 ? 255 : ss));
+  }
+}
+
+__global__ void clip_ragged_resize_v_norm_kernel(ClipRaggedChunk ch, int S, const uint8_t *__restrict__ work, float m0, float m1, float m2,
+                                                 float s0, float s1, float s2, float *__restrict__ out) {
+  const ClipRaggedImg &m = ch.img[blockIdx.y];
+  const int H = m.g[0], top = m.g[4], ksize = m.g[7];
+  const int *bounds = reinterpret_cast<const int *>(work + m.off[2]), *kk = reinterpret_cast<const int *>(work + m.off[3]);
+  const uint8_t *in = work + m.off[5];
+  float *dst = out + (long)blockIdx.y * 3 * S * S;
+  const long total = 3L * S * S;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % S);
+    const long t = i / S;
+    const int yy = (int)(t % S);
+    const int c = (int)(t / S);
+    const int oy = yy + top;
+    const int ymin = bounds[2 * oy], cnt = bounds[2 * oy + 1];
+    const int *k = kk + (long)oy * ksize;
+    const uint8_t *p = in + ((long)c * H + ymin) * S + xx;
+    int ss = 1 << 21;
+    for (int y = 0; y < cnt; y++) ss += (int)p[(long)y * S] * k[y];
+    ss >>= 22;
+    const int u = ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+    dst[i] = ((float)u / 255.0f - mean) / sd;
+  }
+}
+
+extern "C" int sgic_clip_preprocess_ragged_workspace(int B, const int32_t *h_geo, int S, size_t *bytes) {
+  SGIC_REQUIRE(B > 0 && h_geo && S > 0 && bytes, "args");
+  long long off = 0;
+  ClipRaggedImg m;
+  for (int b = 0; b < B; b++) {
+    const int rc = clip_ragged_image(h_geo + 6 * b, S, &off, &m);
+    if (rc) return rc;
+  }
+  *bytes = (size_t)off;
+  return 0;
+}
+
+extern "C" int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_stride, int ldx, int B, const int32_t *h_geo, int S,
+                                           const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
+                                           sgic_stream_t stream) {
+  SGIC_REQUIRE(d_x && h_geo && d_work && d_out && mean3 && std3 && B > 0 && S > 0, "args");
+  SGIC_REQUIRE((((uintptr_t)d_work) & 15) == 0, "workspace alignment");
+  hipStream_t st = to_stream(stream);
+  const auto gx = [](long n) { return (unsigned)std::min((n + 255) / 256, 1024L); };
+  long long off = 0;
+  for (int c0 = 0; c0 < B; c0 += RAGGED_CHUNK) {
+    const int n = std::min(RAGGED_CHUNK, B - c0);
+    ClipRaggedChunk ch{};
+    long mx_tab = 0, mx_u8 = 0, mx_th = 0;
+    for (int j = 0; j < n; j++) {
+      ClipRaggedImg &m = ch.img[j];
+      const int rc = clip_ragged_image(h_geo + 6 * (c0 + j), S, &off, &m);
+      if (rc) return rc;
+      SGIC_REQUIRE((size_t)off <= work_bytes, "workspace too small (sgic_clip_preprocess_ragged_workspace)");
+      SGIC_REQUIRE(m.g[1] <= ldx, "image wider than the row stride");
+      mx_tab = std::max(mx_tab, (long)m.g[2] + m.g[3]);
+      mx_u8 = std::max(mx_u8, 3L * m.g[0] * m.g[1]);
+      mx_th = std::max(mx_th, 3L * m.g[0] * S);
+    }
+    clip_ragged_coeffs_kernel<<<dim3(cdiv((size_t)mx_tab, 64), n), 64, 0, st>>>(ch, d_work);
+    int rc = sgic::check_launch("clip_ragged_coeffs_kernel");
+    if (rc) return rc;
+    clip_ragged_to_u8_kernel<<<dim3(gx(mx_u8), n), 256, 0, st>>>(d_x + (long)c0 * img_stride, img_stride, ch_stride, ldx, ch, d_work);
+    rc = sgic::check_launch("clip_ragged_to_u8_kernel");
+    if (rc) return rc;
+    clip_ragged_resize_h_kernel<<<dim3(gx(mx_th), n), 256, 0, st>>>(ch, S, d_work);
+    rc = sgic::check_launch("clip_ragged_resize_h_kernel");
+    if (rc) return rc;
+    clip_ragged_resize_v_norm_kernel<<<dim3(gx(3L * S * S), n), 256, 0, st>>>(ch, S, d_work, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
+                                                                            std3[2], d_out + (long)c0 * 3 * S * S);
+    rc = sgic::check_launch("clip_ragged_resize_v_norm_kernel");
+    if (rc) return rc;
+  }
+  return 0;
+}

@@ -5,8 +5,11 @@ The reference decodes one image per step into fp32 on 4 DataLoader workers.  At 
 has to be a pipeline of its own, with bounded memory whatever the corpus size:
 
   1. header pass   -- `Image.open(path).size` reads the image header only (no pixel decode): every file of the shard
-                      gets its geometry, and consecutive files of equal geometry are cut into batches (a batch shares
-                      padding and CLIP resize geometry).  File order inside a geometry stays the sorted order.
+                      gets its geometry, and files of equal geometry are cut into batches.  File order inside a geometry
+                      stays the sorted order.  With `pad_to` (the compress driver: 256) the geometry is the PADDED one, so
+                      images of different sizes share a batch: the batch is a u8 canvas of its largest extents with every
+                      image at the top left, and per-image extents travel with it (decode, padding and CLIP preprocessing
+                      then work on each image's own extent; plan_batches caps such a batch at 4 x batch_size tiles).
   2. decode        -- JPEG batches (baseline Huffman files: what cameras and Pillow write) are decoded ON THE GPU: the thread
                       pool only reads the file bytes and parses markers (sgic_amd.jpeg), the compressed bytes cross PCIe
                       (~1/10 of the pixels) and csrc/jpeg.hip does Huffman decode, IDCT, chroma upsampling and colour
@@ -54,22 +57,33 @@ def _read_bytes(path):
         return f.read()
 
 
-def plan_batches(files, sizes, batch_size):
-    """-> list of (H, W, [indices into files]): one entry per batch; files of one geometry keep their order"""
+def padded_size(h, w, pad_to):
+    """(ceil(h / pad_to) * pad_to, ceil(w / pad_to) * pad_to): the geometry the encoder sees (get_padding_size)"""
+    return -(-h // pad_to) * pad_to, -(-w // pad_to) * pad_to
+
+
+def plan_batches(files, sizes, batch_size, pad_to=None, max_tiles=None):
+    """-> list of (H, W, [indices into files]): one entry per batch; files of one geometry keep their order, geometries come in
+    order of first appearance.  pad_to: group by the padded geometry (padded_size) instead of the exact size -- (H, W) is then that
+    padded geometry -- and cut a batch before it holds more than max_tiles tiles of pad_to^2 (default 4 * batch_size, i.e.
+    batch_size x 512^2 padded pixels; it never binds for images that pad to <= 512 x 512).  One image always makes a batch."""
     groups = {}
     for i, hw in enumerate(sizes):
-        groups.setdefault(hw, []).append(i)
+        groups.setdefault(hw if pad_to is None else padded_size(hw[0], hw[1], pad_to), []).append(i)
+    cap = 4 * batch_size if max_tiles is None else max_tiles
     plan = []
     for (h, w), idxs in groups.items():
-        for s in range(0, len(idxs), batch_size):
-            plan.append((h, w, idxs[s:s + batch_size]))
+        per = batch_size if pad_to is None else max(1, min(batch_size, cap // ((h // pad_to) * (w // pad_to))))
+        for s in range(0, len(idxs), per):
+            plan.append((h, w, idxs[s:s + per]))
     return plan
 
 
 class Batch:
     """u8: pinned (B,H,W,3) host tensor (host-decoded batch), or None when `jpeg` holds a sgic_amd.jpeg.JpegBatch / ScanJpegBatch to
-    decode on the GPU"""
-    __slots__ = ("H", "W", "indices", "paths", "u8", "jpeg", "_slot", "_owner")
+    decode on the GPU.  H x W: the batch's (canvas) geometry, the largest extents in it; hw: int32 (B, 2) extents of the images, each
+    at the top left of the canvas (the canvas outside an image holds stale bytes); pad_hw: the padded geometry of a pad_to batch"""
+    __slots__ = ("H", "W", "hw", "pad_hw", "indices", "paths", "u8", "jpeg", "_slot", "_owner")
 
     def release(self):
         """hand the pinned buffer back (call once the H2D copy of this batch has completed)"""
@@ -85,8 +99,9 @@ class ShardLoader:
             ...; b.release()
     A decode error is re-raised in the consumer at the position of the failing batch."""
 
-    def __init__(self, files, batch_size=32, workers=None, depth=3, pin=True, gpu_jpeg=None, gpu_progressive=None):
-        """gpu_jpeg: decode baseline JPEG batches on the GPU (default: when a GPU is present; SGIC_GPU_JPEG=0 turns it off).
+    def __init__(self, files, batch_size=32, workers=None, depth=3, pin=True, gpu_jpeg=None, gpu_progressive=None, pad_to=None):
+        """pad_to: batch images that pad to the same multiple of pad_to together (plan_batches); default: equal sizes only.
+        gpu_jpeg: decode baseline JPEG batches on the GPU (default: when a GPU is present; SGIC_GPU_JPEG=0 turns it off).
         gpu_progressive: also decode the JPEG batches the baseline path refuses but the scan decoder takes (progressive and mixed
         baseline / progressive batches) on the GPU (default: off; SGIC_GPU_JPEG_PROGRESSIVE=1 turns it on); needs gpu_jpeg"""
         self.files = list(files)
@@ -102,7 +117,8 @@ class ShardLoader:
         self.pin = pin and torch.cuda.is_available()
         self._pool = ThreadPoolExecutor(max_workers=self.workers)
         self.sizes = list(self._pool.map(image_size, self.files))                 # header pass, no pixel decode
-        self.plan = plan_batches(self.files, self.sizes, self.batch_size)
+        self.pad_to = pad_to
+        self.plan = plan_batches(self.files, self.sizes, self.batch_size, pad_to=pad_to)
         self._free = queue.Queue()
         for s in range(self.depth + 3):      # the consumer holds up to three batches (decoding ahead + GPU in flight + being written out)
             self._free.put(s)
@@ -139,8 +155,14 @@ class ShardLoader:
                     except queue.Empty:
                         continue
                 n = len(idxs)
+                hw = np.array([self.sizes[i] for i in idxs], dtype=np.int32).reshape(n, 2)
                 b = Batch()
-                b.H, b.W, b.indices, b.paths, b.jpeg = h, w, idxs, [self.files[i] for i in idxs], None
+                b.indices, b.paths, b.jpeg, b.hw = idxs, [self.files[i] for i in idxs], None, hw
+                if self.pad_to:      # the canvas: the largest extents of the batch
+                    b.H, b.W, b.pad_hw = int(hw[:, 0].max()), int(hw[:, 1].max()), (h, w)
+                else:
+                    b.H, b.W, b.pad_hw = h, w, None
+                canvas = (b.H, b.W) if self.pad_to else None
                 scans = False
                 if self.gpu_jpeg and all(p.lower().endswith((".jpg", ".jpeg")) for p in b.paths):
                     from . import jpeg as J
@@ -148,15 +170,15 @@ class ShardLoader:
                     datas = None
                     try:     # file bytes + marker parsing on the pool; the pixels never exist on the host
                         datas = list(self._pool.map(_read_bytes, b.paths))
-                        b.jpeg = J.JpegBatch(datas, pool=self._pool, alloc=alloc)
+                        b.jpeg = J.JpegBatch(datas, pool=self._pool, alloc=alloc, canvas=canvas)
                     except Exception:      # noqa: BLE001 -- J.Unsupported (progressive / CMYK / ...) or a file the parser chokes on:
                         b.jpeg = None      # this batch takes the host decoder, which raises a proper error for a really broken file
                     if b.jpeg is None and datas is not None and self.gpu_progressive:
                         try:     # progressive / mixed batch: decoded scan by scan
-                            b.jpeg, scans = J.ScanJpegBatch(datas, pool=self._pool, alloc=alloc), True
+                            b.jpeg, scans = J.ScanJpegBatch(datas, pool=self._pool, alloc=alloc, canvas=canvas), True
                         except Exception:  # noqa: BLE001 -- as above: the host decoder takes it
                             b.jpeg = None
-                    if b.jpeg is not None and (b.jpeg.H, b.jpeg.W) != (h, w):
+                    if b.jpeg is not None and not np.array_equal(b.jpeg.hw, hw):     # a parsed size differs from its header pass
                         b.jpeg = None
                 if b.jpeg is not None:
                     b.u8, b._slot, b._owner = None, slot, self     # the slot returns with release(), after the copy has completed
@@ -165,10 +187,11 @@ class ShardLoader:
                     else:
                         self.gpu_batches += 1
                 else:
-                    flat = self._buffer(slot, n * h * w * 3)
-                    u8 = flat[:n * h * w * 3].view(n, h, w, 3)
+                    ch, cw = b.H, b.W
+                    flat = self._buffer(slot, n * ch * cw * 3)
+                    u8 = flat[:n * ch * cw * 3].view(n, ch, cw, 3)
                     arr = u8.numpy()
-                    list(self._pool.map(lambda j: decode_rgb_u8(self.files[idxs[j]], arr[j]), range(n)))
+                    list(self._pool.map(lambda j: decode_rgb_u8(self.files[idxs[j]], arr[j, :hw[j, 0], :hw[j, 1]]), range(n)))
                     b.u8, b._slot, b._owner = u8, slot, self
                     self.host_batches += 1
                 self._q.put(b)
@@ -224,15 +247,23 @@ class DeviceIngest:
             done.record()
         return d, done
 
-    def finish(self, tok, pad):
-        """pad = (pl, pr, pt, pb) of compress.py:258-261 -> x (B,3,Hp,Wp) fp32 in [-1,1] on the launch stream"""
+    def finish(self, tok, pad, hw=None):
+        """pad = (pl, pr, pt, pb) of compress.py:258-261 -> x (B,3,H+pt+pb,W+pl+pr) fp32 in [-1,1] on the launch stream.
+        hw: the (B, 2) extents of a canvas batch whose images differ in size (Batch.hw); every image is then padded from its OWN
+        right / bottom edge, `pad` being the canvas's padding (right / bottom only)"""
         from . import ops
         d, done = tok
         cur = torch.cuda.current_stream()
         cur.wait_event(done)
         d.record_stream(cur)
-        x = ops.u8hwc_to_f32chw_pad(d, *pad)
+        if hw is not None:
+            pl, pr, pt, pb = pad
+            if pl or pt:
+                raise ValueError("a batch of images of different sizes is padded on the right and bottom only")
+            x = ops.u8canvas_to_f32chw_pad(d, hw, d.shape[1] + pb, d.shape[2] + pr)
+        else:
+            x = ops.u8hwc_to_f32chw_pad(d, *pad)
         return x, done
 
-    def __call__(self, batch, pad):
-        return self.finish(self.start(batch), pad)
+    def __call__(self, batch, pad, hw=None):
+        return self.finish(self.start(batch), pad, hw)

@@ -213,22 +213,37 @@ def parse(data):
     return p
 
 
+def _geometry(ps, canvas):
+    """-> ((H, W) of the decoded batch, per-image extents int32 (B, 2)).  Without a canvas every file must have one size.  With
+    canvas = (H, W) each file (its own P_W x P_H in its params) is decoded at the top left of an H x W canvas it must fit in; the
+    canvas outside an image's extent is NOT written (it holds whatever the output buffer held): a consumer reads each image within
+    its extent only, as ops.u8canvas_to_f32chw_pad does"""
+    hw = np.array([(p.H, p.W) for p in ps], dtype=np.int32).reshape(len(ps), 2)
+    if canvas is None:
+        if (hw != hw[0]).any():
+            raise ValueError("a JPEG batch shares one geometry")
+        return (int(hw[0, 0]), int(hw[0, 1])), hw
+    H, W = int(canvas[0]), int(canvas[1])
+    if (hw[:, 0] > H).any() or (hw[:, 1] > W).any():
+        raise ValueError(f"an image of the batch is larger than the {H}x{W} canvas")
+    return (H, W), hw
+
+
 class JpegBatch:
-    """host-side descriptor of a batch of equal-geometry JPEGs: ONE contiguous blob
+    """host-side descriptor of a batch of equal-geometry JPEGs (or of JPEGs on one canvas): ONE contiguous blob
         params (B x 64 i32) | restart offsets (i32) | quant tables (B x 256 u16) | Huffman lookup tables (B x 4 x 1424 B) | cleaned scans
     so that the batch crosses PCIe in a single copy.  `alloc(nbytes) -> uint8 torch tensor` supplies the staging memory: the ingest
     passes PINNED slot buffers -- a copy from pageable memory is synchronous in HIP and, measured in the CLI trace, waited for the
     previous batch's GPU work (the decode then ran alone instead of under it)."""
 
-    def __init__(self, datas, pool=None, alloc=None):
+    def __init__(self, datas, pool=None, alloc=None, canvas=None):
+        """canvas = (H, W): files of different sizes, each decoded at the top left of an H x W canvas (_geometry)"""
         import torch
         ps = list(pool.map(parse, datas)) if pool is not None else [parse(d) for d in datas]
         self.last_err = None
-        H, W = ps[0].H, ps[0].W
-        if any((p.H, p.W) != (H, W) for p in ps):
-            raise ValueError("a JPEG batch shares one geometry")
         B = len(ps)
-        self.B, self.H, self.W = B, H, W
+        (self.H, self.W), self.hw = _geometry(ps, canvas)
+        self.B = B
         nseg = sum(len(p.segs) for p in ps)
         scan_len = [len(p.scan) + ((-len(p.scan)) % CHUNK or (CHUNK if len(p.scan) == 0 else 0)) for p in ps]
         al = lambda n: (n + 255) & ~255
@@ -253,7 +268,7 @@ class JpegBatch:
         for b, p in enumerate(ps):
             r = params[b]
             r[P_SCAN_OFF], r[P_SCAN_LEN], r[P_TAB_OFF], r[P_QUANT_OFF] = scan_off, scan_len[b], b * 4 * TAB_BYTES, b * 256
-            r[P_NCOMP], r[P_W], r[P_H], r[P_HMAX], r[P_VMAX] = p.ncomp, W, H, p.hmax, p.vmax
+            r[P_NCOMP], r[P_W], r[P_H], r[P_HMAX], r[P_VMAX] = p.ncomp, p.W, p.H, p.hmax, p.vmax
             r[P_MCUS_X], r[P_MCUS_Y], r[P_RESTART], r[P_SEG_OFF], r[P_NSEG] = p.mcus_x, p.mcus_y, p.restart, seg_off, len(p.segs)
             nblk = 0
             for c, d in enumerate(p.comps):
@@ -485,15 +500,14 @@ class ScanJpegBatch:
         quant tables (B x 256 u16) | Huffman table pool (npool x 1424 B, deduplicated over the batch) | cleaned scans
     decode() runs one kernel launch per dependency level (self.level_start), then the IDCT and colour kernels of the baseline path."""
 
-    def __init__(self, datas, pool=None, alloc=None):
+    def __init__(self, datas, pool=None, alloc=None, canvas=None):
+        """canvas = (H, W): files of different sizes, each decoded at the top left of an H x W canvas (_geometry)"""
         import torch
         ps = list(pool.map(parse_scans, datas)) if pool is not None else [parse_scans(d) for d in datas]
         self.last_err = None
-        H, W = ps[0].H, ps[0].W
-        if any((p.H, p.W) != (H, W) for p in ps):
-            raise ValueError("a JPEG batch shares one geometry")
         B = len(ps)
-        self.B, self.H, self.W = B, H, W
+        (self.H, self.W), self.hw = _geometry(ps, canvas)
+        self.B = B
         pool_idx, pool_tabs, remap = {}, [], []
         for p in ps:
             r = []
@@ -535,7 +549,7 @@ class ScanJpegBatch:
         self.max_blocks = 0
         for b, p in enumerate(ps):
             r = params[b]
-            r[P_QUANT_OFF], r[P_NCOMP], r[P_W], r[P_H], r[P_HMAX], r[P_VMAX] = b * 256, p.ncomp, W, H, p.hmax, p.vmax
+            r[P_QUANT_OFF], r[P_NCOMP], r[P_W], r[P_H], r[P_HMAX], r[P_VMAX] = b * 256, p.ncomp, p.W, p.H, p.hmax, p.vmax
             r[P_MCUS_X], r[P_MCUS_Y] = p.mcus_x, p.mcus_y
             nblk = 0
             for c, d in enumerate(p.comps):

@@ -965,6 +965,27 @@ def u8hwc_to_f32chw_pad(x_u8, pl=0, pr=0, pt=0, pb=0):
     return out
 
 
+def u8canvas_to_f32chw_pad(x_u8, hw, OH, OW):
+    """(B,Hc,Wc,3) u8 canvas on the device, image b at its top left with extent hw[b] = (h, w) -> (B,3,OH,OW) fp32 in [-1,1]: ToTensor,
+    *2-1, replicate pad from each image's own right / bottom edge (bit-identical per image to u8hwc_to_f32chw_pad on it alone)"""
+    assert x_u8.dim() == 4 and x_u8.shape[3] == 3 and x_u8.dtype == torch.uint8 and x_u8.is_contiguous() and x_u8.is_cuda
+    B, Hc, Wc, _ = x_u8.shape
+    hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(B, 2)
+    out = torch.empty(B, 3, int(OH), int(OW), device=x_u8.device, dtype=torch.float32)
+    call("sgic_u8canvas_to_f32chw_pad", _p(x_u8), hw, _p(out), B, Hc, Wc, int(OH), int(OW))
+    return out
+
+
+def clip_resize_coeffs(in_size, out_size, device):
+    """Pillow's bicubic tables of an in_size -> out_size resample built on the device (what clip.pil_coeffs computes on the host)
+    -> (bounds int32 (out,2), kk int32 (out,ksize), ksize)"""
+    ksize = int(np.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+    bounds = torch.empty(out_size, 2, dtype=torch.int32, device=device)
+    kk = torch.empty(out_size, ksize, dtype=torch.int32, device=device)
+    call("sgic_clip_resize_coeffs", int(in_size), int(out_size), ksize, _p(bounds), _p(kk))
+    return bounds, kk, ksize
+
+
 def topk_rows(scores, k):
     """scores (nq, n) fp32 on device (consumed) -> (top scores (nq,k), indices (nq,k) int32)"""
     nq, n = scores.shape

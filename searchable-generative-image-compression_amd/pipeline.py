@@ -37,12 +37,20 @@ class CompressPipeline:
         p["busy"] = True
         return p
 
-    def submit(self, x, clip_hw=None):
+    def submit(self, x, clip_hw=None, hw=None):
         """x (B,3,H,W) fp32 in [-1,1] on the device, H and W multiples of 256 (already padded, compress.py:258-261).
-        clip_hw = (h, w): the top-left h x w region is the real image the CLIP tower must see (compress.py:266)."""
+        clip_hw = (h, w): the top-left h x w region is the real image the CLIP tower must see (compress.py:266).
+        hw: (B, 2) per-image extents instead, for a batch of images of different sizes that pad to one geometry."""
         B, _, H, W = x.shape
+        if hw is not None:
+            hw = np.asarray(hw).reshape(B, 2)
+            if (hw == hw[0]).all():           # one size after all: the uniform kernels
+                clip_hw, hw = (int(hw[0, 0]), int(hw[0, 1])), None
         r = self.codec.encode_device(x, side_stream=self.side)
-        unit, q = self.clipc.batch_to_codes(x, *(clip_hw or (None, None)))
+        if hw is not None:
+            unit, q = self.clipc.batch_to_codes(x, hw=hw)
+        else:
+            unit, q = self.clipc.batch_to_codes(x, *(clip_hw or (None, None)))
         if self.on_unit is not None:
             self.on_unit(unit)
         torch.cuda.current_stream().wait_stream(self.side)
