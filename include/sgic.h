@@ -307,6 +307,21 @@ int sgic_nhwc3_to_nchw_clamp(const float *d_in, int ld, int B, int H, int W, flo
  * (nq, n) = sgic_gemm_f32(queries, database) and is consumed (taken entries become -inf). */
 int sgic_topk_rows(float *d_scores, int nq, int n, int k, float *d_out_scores, int32_t *d_out_idx, sgic_stream_t stream);
 
+/* Fused exact search over u8 CLIP codes (sgic_amd/search.py CodeIndex): i8 MFMA inner products and top-k in one kernel; the
+ * (nq, n) score matrix never exists.  d_q (nq, D) and d_db (n, D) are u8 codes, 16-byte aligned; D % 64 == 0, D <= 4096, k <= 128,
+ * k <= n, anything else is SGIC_EINVAL (the caller keeps the fp32 path).  With a = c - 128, S = sum a_q a_d, s_x = sum a_x the
+ * int32 N = 4 S + 2 s_q + 2 s_d + D equals sum (2 c_q - 255)(2 c_d - 255) exactly; d_rq / d_rdb hold r_x = float32(1 / sqrt(
+ * float64(sum (2 c_x - 255)^2))), computed on the host (search.code_rnorm).  Ranking key = float32(N) * r_d, order: key
+ * descending, equal keys -> lower database index; reported score = key * r_q.  No float add, sqrt or division runs on the
+ * device, so numpy reproduces every bit.  The database is cut into contiguous ascending splits (splits <= 0: chosen so that the
+ * grid covers the chip; > 0: an upper bound the caller asks for); with more than one split each (query, split) writes its k best
+ * to d_work and a merge kernel orders them.  sgic_search_codes_u8_work_bytes (host-only, takes no stream) returns the split count
+ * actually used and the workspace size, nq * splits * k * 8 bytes (0 for one split). */
+int sgic_search_codes_u8_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes);
+int sgic_search_codes_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, int k,
+                         int splits, uint8_t *d_work, size_t work_bytes, float *d_out_scores, int32_t *d_out_idx,
+                         sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

@@ -1,0 +1,322 @@
+// Fused exact search over u8 CLIP codes (sgic_amd/search.py CodeIndex): i8 MFMA inner products + top-k in one kernel,
+// no score matrix.  With a = c - 128 (i8), S = sum a_q a_d and s_x = sum a_x, the integer
+//   N(q, d) = 4 S + 2 s_q + 2 s_d + D  ==  sum (2 c_q - 255)(2 c_d - 255)
+// is exact in int32 for D <= 4096.  Ranking key = float(N) * r_d (one RNE conversion, one fp32 multiply), reported score =
+// key * r_q; r = 1 / sqrt(sum (2c - 255)^2) comes from the host, the GPU does no sqrt, division or float add, so every bit is
+// reproducible in numpy.  Order: key descending, equal keys -> lower database index (IndexFlatIP, topk_rows_kernel).
+//
+// Grid = (query tiles of 16*QF) x (contiguous ascending database splits).  A workgroup is 4 waves; the query tile sits in LDS
+// already in MFMA fragment order, each wave streams its own 16-row database tile from global memory as 16-byte fragments
+// (lane l: row l & 15, bytes 64 step + 16 (l >> 4) + j -- the SAME k mapping as the query fragments).  C layout: rows are
+// queries (4 (l >> 4) + reg), columns database rows (l & 15).  Candidates that beat the query's running k-th best go to a
+// per-query LDS buffer of k + 64 entries (one block iteration adds at most 64 per query); a full buffer is pruned to the best k
+// by rank and raises the threshold.  The threshold only moves at block-wide sync points, after which every later candidate has a
+// higher index than everything kept, so a strict `>` implements the tie rule.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+constexpr int kMaxK = 128;
+constexpr int kCandPerIter = 64;   // 4 waves x 16 database rows
+constexpr int kMaxSplits = 2048;
+constexpr int kLdsBigTile = 80 * 1024;   // the 64-query tile is used only while two workgroups still fit a CU
+
+__device__ __forceinline__ bool beats(float ka, int ia, float kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
+
+// one wave: keep the best min(c, k) of the c buffered candidates of one query, sorted by (key desc, index asc), in slots 0..;
+// c <= k + 64 <= 192, so a lane owns at most 3 entries
+__device__ __forceinline__ void prune_wave(float *kq, int *iq, int c, int k, int lane, int *cntp, float *thrp) {
+  float ke[3];
+  int ie[3], rk[3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    const int e = lane + 64 * m;
+    ke[m] = e < c ? kq[e] : -INFINITY;
+    ie[m] = e < c ? iq[e] : 0x7fffffff;
+    rk[m] = 0;
+  }
+  for (int j = 0; j < c; j++) {
+    const float kj = kq[j];
+    const int ij = iq[j];
+#pragma unroll
+    for (int m = 0; m < 3; m++) rk[m] += beats(kj, ij, ke[m], ie[m]) ? 1 : 0;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    if (lane + 64 * m < c && rk[m] < k) {
+      kq[rk[m]] = ke[m];
+      iq[rk[m]] = ie[m];
+      if (rk[m] == k - 1) *thrp = ke[m];
+    }
+  }
+  if (lane == 0) *cntp = c < k ? c : k;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ unsigned sum_bytes16(const uint4 &v, unsigned acc) {
+  acc = __builtin_amdgcn_sad_u8(v.x, 0u, acc);
+  acc = __builtin_amdgcn_sad_u8(v.y, 0u, acc);
+  acc = __builtin_amdgcn_sad_u8(v.z, 0u, acc);
+  return __builtin_amdgcn_sad_u8(v.w, 0u, acc);
+}
+
+__device__ __forceinline__ v4i to_i8x16(const uint4 &v) {   // sixteen u8 codes c -> c - 128 as i8
+  v4i r;
+  r.x = (int)(v.x ^ 0x80808080u);
+  r.y = (int)(v.y ^ 0x80808080u);
+  r.z = (int)(v.z ^ 0x80808080u);
+  r.w = (int)(v.w ^ 0x80808080u);
+  return r;
+}
+
+template <int QF, int U>
+__global__ __launch_bounds__(256) void search_codes_kernel(const uint8_t *__restrict__ q, const float *__restrict__ r_q,
+                                                           const uint8_t *__restrict__ db, const float *__restrict__ r_db, int nq,
+                                                           int n, int D, int k, int rows_per_split, int splits, int final_out,
+                                                           float *__restrict__ out_key, int *__restrict__ out_idx) {
+  constexpr int QT = 16 * QF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int steps = D >> 6;
+  const int cap = k + kCandPerIter;
+  v4i *A = reinterpret_cast<v4i *>(smem);   // [QF][steps][64 lanes] fragments
+  float *keys = reinterpret_cast<float *>(smem + (size_t)QT * D);
+  int *idxs = reinterpret_cast<int *>(keys + QT * cap);
+  int *cnt = idxs + QT * cap;
+  float *thr = reinterpret_cast<float *>(cnt + QT);
+  int *sq = reinterpret_cast<int *>(thr + QT);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+
+  if (tid < QT) {
+    cnt[tid] = 0;
+    thr[tid] = -INFINITY;
+    sq[tid] = 0;
+  }
+  __syncthreads();
+  for (int i = tid; i < QF * steps * 64; i += 256) {   // one 16-byte fragment per (query fragment, step, lane)
+    const int ln = i & 63, t = i >> 6;
+    const int step = t % steps, f = t / steps;
+    const int row = f * 16 + (ln & 15);
+    int qi = qbase + row;
+    qi = qi < nq ? qi : nq - 1;
+    const uint4 v = *reinterpret_cast<const uint4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4));
+    atomicAdd(&sq[row], (int)sum_bytes16(v, 0u));
+    A[i] = to_i8x16(v);
+  }
+  __syncthreads();
+
+  int baseq[QF][4];
+  float thr_r[QF][4];
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      baseq[f][r] = 2 * (sq[f * 16 + 4 * (lane >> 4) + r] - 128 * D) + D;
+      thr_r[f][r] = -INFINITY;
+    }
+
+  const int row0 = split * rows_per_split;
+  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
+  for (int base = row0; base < row_end; base += kCandPerIter) {
+    const int my = base + wave * 16 + (lane & 15);
+    const int myc = my < n ? my : n - 1;
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    v4i acc[QF];
+#pragma unroll
+    for (int f = 0; f < QF; f++) acc[f] = v4i{0, 0, 0, 0};
+    unsigned ssum = 0;
+    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
+      uint4 bv[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        ssum = sum_bytes16(bv[u], ssum);
+        const v4i b = to_i8x16(bv[u]);
+#pragma unroll
+        for (int f = 0; f < QF; f++)
+          acc[f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(f * steps + s0 + u) * 64 + lane], b, acc[f], 0, 0, 0);
+      }
+    }
+    ssum += __shfl_xor(ssum, 16);
+    ssum += __shfl_xor(ssum, 32);
+    const int sd2 = 2 * ((int)ssum - 128 * D);
+    const float rd = r_db[myc];
+    const bool valid = my < row_end;
+    int any = 0;
+#pragma unroll
+    for (int f = 0; f < QF; f++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int N = 4 * acc[f][r] + baseq[f][r] + sd2;
+        const float key = (float)N * rd;
+        if (valid && key > thr_r[f][r]) {
+          const int ql = f * 16 + 4 * (lane >> 4) + r;
+          const int pos = atomicAdd(&cnt[ql], 1);
+          keys[ql * cap + pos] = key;
+          idxs[ql * cap + pos] = my;
+          any = 1;
+        }
+      }
+    if (__syncthreads_or(any)) {
+      for (int ql = wave; ql < QT; ql += 4) {
+        const int c = cnt[ql];
+        if (c > k) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int f = 0; f < QF; f++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) thr_r[f][r] = thr[f * 16 + 4 * (lane >> 4) + r];
+    }
+  }
+  __syncthreads();
+  for (int ql = wave; ql < QT; ql += 4) {
+    const int gq = qbase + ql;
+    if (gq >= nq) break;
+    int c = cnt[ql];
+    if (c > 0) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
+    c = c < k ? c : k;
+    const float rq = final_out ? r_q[gq] : 1.0f;
+    const size_t o = ((size_t)gq * splits + split) * k;
+    for (int j = lane; j < k; j += 64) {
+      const float key = j < c ? keys[ql * cap + j] : -INFINITY;
+      out_key[o + j] = final_out ? key * rq : key;
+      out_idx[o + j] = j < c ? idxs[ql * cap + j] : -1;
+    }
+  }
+}
+
+// per query: k-way selection over the splits' sorted lists (splits ascend in database index, so the index breaks ties)
+__global__ __launch_bounds__(256) void search_merge_kernel(const float *__restrict__ ws_key, const int *__restrict__ ws_idx,
+                                                           const float *__restrict__ r_q, int splits, int k,
+                                                           float *__restrict__ out_s, int *__restrict__ out_i) {
+  __shared__ unsigned short head[kMaxSplits];
+  __shared__ float wk[4];
+  __shared__ int wi[4], wsp[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t qo = (size_t)blockIdx.x * splits * k;
+  const float rq = r_q[blockIdx.x];
+  for (int s = tid; s < splits; s += 256) head[s] = 0;
+  __syncthreads();
+  for (int j = 0; j < k; j++) {
+    float bk = -INFINITY;
+    int bi = 0x7fffffff, bs = -1;
+    for (int s = tid; s < splits; s += 256) {
+      const int h = head[s];
+      if (h >= k) continue;
+      const int idx = ws_idx[qo + (size_t)s * k + h];
+      if (idx < 0) continue;
+      const float key = ws_key[qo + (size_t)s * k + h];
+      if (bs < 0 || beats(key, idx, bk, bi)) bk = key, bi = idx, bs = s;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      const float ok = __shfl_xor(bk, m);
+      const int oi = __shfl_xor(bi, m), os = __shfl_xor(bs, m);
+      if (os >= 0 && (bs < 0 || beats(ok, oi, bk, bi))) bk = ok, bi = oi, bs = os;
+    }
+    if (lane == 0) wk[wave] = bk, wi[wave] = bi, wsp[wave] = bs;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; w++)
+        if (wsp[w] >= 0 && (bs < 0 || beats(wk[w], wi[w], bk, bi))) bk = wk[w], bi = wi[w], bs = wsp[w];
+      out_s[(size_t)blockIdx.x * k + j] = bs >= 0 ? bk * rq : -INFINITY;
+      out_i[(size_t)blockIdx.x * k + j] = bs >= 0 ? bi : -1;
+      if (bs >= 0) head[bs]++;
+    }
+    __syncthreads();
+  }
+}
+
+struct Plan {
+  int qf, qtiles, splits, rows_per_split;
+  size_t lds, work_bytes;
+};
+
+size_t lds_bytes(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)D + (size_t)(k + kCandPerIter) * 8 + 12); }
+
+int make_plan(int nq, int n, int D, int k, int splits, Plan *p) {
+  SGIC_REQUIRE(nq > 0 && n > 0 && k > 0 && k <= n, "sizes");
+  SGIC_REQUIRE(k <= kMaxK, "the fused search keeps at most 128 results per query");
+  SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "D must be a multiple of 64, at most 4096 (int32 exactness)");
+  p->qf = (nq > 16 && lds_bytes(4, D, k) <= (size_t)kLdsBigTile) ? 4 : 1;
+  p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
+  SGIC_REQUIRE(splits <= kMaxSplits, "splits");
+  if (splits <= 0) {   // cover the chip a few times over when there are few query tiles
+    splits = (1024 + p->qtiles - 1) / p->qtiles;
+    const int most = (n + 255) / 256;
+    splits = splits < most ? splits : most;
+  }
+  const int tiles = (n + kCandPerIter - 1) / kCandPerIter;
+  splits = splits < tiles ? splits : tiles;
+  splits = splits < kMaxSplits ? splits : kMaxSplits;
+  const int per = (n + splits - 1) / splits;
+  p->rows_per_split = (per + kCandPerIter - 1) / kCandPerIter * kCandPerIter;
+  p->splits = (n + p->rows_per_split - 1) / p->rows_per_split;   // no empty split
+  p->lds = lds_bytes(p->qf, D, k);
+  p->work_bytes = p->splits > 1 ? (size_t)nq * p->splits * k * 8 : 0;
+  return SGIC_OK;
+}
+
+template <int QF, int U>
+int launch_search(const Plan &p, const uint8_t *q, const float *r_q, const uint8_t *db, const float *r_db, int nq, int n, int D, int k,
+                  float *okey, int *oidx, hipStream_t st) {
+  static bool lds_raised = false;   // beyond the default 64 KiB a kernel has to be allowed its dynamic LDS once (largest use: 90 KiB)
+  if (p.lds > 60 * 1024 && !lds_raised) {
+    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_codes_kernel<QF, U>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 128 * 1024));
+    lds_raised = true;
+  }
+  search_codes_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, r_q, db, r_db, nq, n, D, k, p.rows_per_split, p.splits,
+                                                                         p.splits == 1, okey, oidx);
+  return sgic::check_launch("search_codes_kernel");
+}
+
+}  // namespace
+
+extern "C" int sgic_search_codes_u8_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes) {
+  Plan p;
+  const int rc = make_plan(nq, n, D, k, splits, &p);
+  if (rc != SGIC_OK) return rc;
+  if (splits_used) *splits_used = p.splits;
+  if (bytes) *bytes = p.work_bytes;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_search_codes_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
+                                    int D, int k, int splits, uint8_t *d_work, size_t work_bytes, float *d_out_scores,
+                                    int32_t *d_out_idx, sgic_stream_t stream) {
+  Plan p;
+  const int rc = make_plan(nq, n, D, k, splits, &p);
+  if (rc != SGIC_OK) return rc;
+  SGIC_REQUIRE(d_q && d_rq && d_db && d_rdb && d_out_scores && d_out_idx, "null pointer");
+  SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db | (uintptr_t)d_work) % 16 == 0, "codes and workspace must be 16-byte aligned");
+  SGIC_REQUIRE(p.work_bytes == 0 || (d_work && work_bytes >= p.work_bytes), "workspace (sgic_search_codes_u8_work_bytes)");
+  hipStream_t st = to_stream(stream);
+  float *okey = d_out_scores;
+  int *oidx = d_out_idx;
+  if (p.splits > 1) {
+    okey = reinterpret_cast<float *>(d_work);
+    oidx = reinterpret_cast<int *>(d_work + (size_t)nq * p.splits * k * 4);
+  }
+  const bool u8 = D % 512 == 0;   // eight 64-byte steps per round when D allows it, else one
+  const int lrc = p.qf == 4 ? (u8 ? launch_search<4, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
+                                  : launch_search<4, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st))
+                            : (u8 ? launch_search<1, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
+                                  : launch_search<1, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st));
+  if (lrc != SGIC_OK) return lrc;
+  if (p.splits > 1) {
+    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, d_rq, p.splits, k, d_out_scores, d_out_idx);
+    return sgic::check_launch("search_merge_kernel");
+  }
+  return SGIC_OK;
+}

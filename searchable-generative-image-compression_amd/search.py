@@ -4,7 +4,10 @@
 `query-image` / `query-text` run the MI355X CLIP image / text towers (clip.py).  The BPE tokenizer is open_clip's
 (third-party, its vocabulary file is not in the reference tree): `query-text` uses `open_clip.get_tokenizer` when the
 package is importable and otherwise takes ready-made ids via --token_ids.  The search itself is exact inner product: one fp32 MFMA GEMM (queries x
-database^T) + a top-k kernel on the GPU."""
+database^T) + a top-k kernel on the GPU.
+`build` makes an index directory from a directory of containers (the reference's `build.py build`); besides the fp32 index it
+writes the u8 codes themselves (codes.npy), which `query-c2df --codes` and `neighbours` search with the fused i8 kernel
+(csrc/search.hip): integer inner products, no fp32 database and no score matrix on the device."""
 import argparse
 import json
 import os
@@ -34,9 +37,9 @@ def codes_to_unit(codes_u8):
     return unit_rows((np.asarray(codes_u8).astype(np.float32) / np.float32(255.0)) * np.float32(2.0) - np.float32(1.0))
 
 
-def embedded_clip_vector(path):
-    """query-c2df (search.py:20-41): the CLIP vector a .c2df carries -- entry `clip_stream` is a zstd frame of `dim` u8
-    codes, `clip_meta["dim"]` says how many.  -> (unit vector (dim,) fp32, container header)"""
+def embedded_clip_codes(path):
+    """the u8 CLIP code a .c2df carries -- entry `clip_stream` is a zstd frame of `dim` u8 codes, `clip_meta["dim"]` says how
+    many.  -> (codes (dim,) u8, container header, clip_meta)"""
     from .filemaker import unpack_c2df
     from .zstd import decompress
     entries, header = unpack_c2df(path)
@@ -50,6 +53,12 @@ def embedded_clip_vector(path):
     codes = np.frombuffer(decompress(stream), dtype=np.uint8)
     if codes.size != want:
         raise NotSearchable(f"{path}: clip_stream decodes to {codes.size} codes but clip_meta.dim says {want}")
+    return codes, header, meta
+
+
+def embedded_clip_vector(path):
+    """query-c2df (search.py:20-41): the CLIP vector a .c2df carries, dequantised -> (unit vector (dim,) fp32, container header)"""
+    codes, header, _ = embedded_clip_codes(path)
     return codes_to_unit(codes), header
 
 
@@ -117,8 +126,135 @@ def do_search(q, vecs, paths, topk=10):
     return [(paths[i], float(sim[0, j])) for j, i in enumerate(ids[0]) if i != -1]
 
 
+def code_rnorm(codes, chunk=1 << 16):
+    """r = float32(1 / sqrt(float64(sum (2c - 255)^2))) per row of u8 codes (n, D): the reciprocal length of the dequantised
+    vector, computed here on the host (the device multiplies by it and never takes a root).  Every 2c - 255 is odd, so the sum is
+    at least D and never 0."""
+    codes = np.asarray(codes)
+    assert codes.dtype == np.uint8 and codes.ndim == 2
+    r = np.empty(codes.shape[0], dtype=np.float32)
+    for i in range(0, codes.shape[0], chunk):
+        v = 2 * codes[i:i + chunk].astype(np.int64) - 255
+        r[i:i + chunk] = (1.0 / np.sqrt((v * v).sum(axis=1).astype(np.float64))).astype(np.float32)
+    return r
+
+
+class CodeIndex:
+    """an index of the u8 CLIP codes themselves: `codes` (n, D) u8, `ids` [n].  Searched with the fused i8 kernel
+    (ops.search_codes): scores are the cosine of the dequantised vectors, 1 byte per coordinate on the device."""
+
+    def __init__(self, codes, ids, model_id=None):
+        self.codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        if self.codes.ndim != 2 or self.codes.shape[0] != len(ids):
+            raise ValueError(f"codes {self.codes.shape} do not match {len(ids)} ids")
+        self.ids = list(ids)
+        self.model_id = model_id
+        self.r = code_rnorm(self.codes)
+        self._dev = None
+
+    @property
+    def dim(self):
+        return int(self.codes.shape[1])
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    @classmethod
+    def from_c2df_dir(cls, c2df_dir, log=print):
+        """every searchable *.c2df under c2df_dir (recursive, sorted); unreadable or unsearchable files are skipped with a line"""
+        paths = sorted(Path(c2df_dir).glob("**/*.c2df"))
+        if not paths:
+            raise RuntimeError(f"no .c2df under {c2df_dir}")
+        rows, keep, model_id = [], [], None
+        for p in paths:
+            try:
+                codes, _, meta = embedded_clip_codes(p)
+            except Exception as e:   # NotSearchable, or a file that is not a container at all
+                log(f"[SKIP] {p.name}: {e}")
+                continue
+            if rows and codes.size != rows[0].size:
+                raise ValueError(f"{p}: code of dim {codes.size} in an index of dim {rows[0].size}")
+            rows.append(codes)
+            keep.append(str(p))
+            if model_id is None and meta.get("model_id"):
+                model_id = meta["model_id"]
+        if not rows:
+            raise RuntimeError(f"no searchable .c2df under {c2df_dir}")
+        return cls(np.stack(rows), keep, model_id)
+
+    def save(self, index_dir):
+        root = Path(index_dir)
+        root.mkdir(parents=True, exist_ok=True)
+        np.save(root / "codes.npy", self.codes)
+        (root / "ids.txt").write_text("\n".join(self.ids), encoding="utf-8")
+
+    @classmethod
+    def load(cls, index_dir):
+        root = Path(index_dir)
+        if not (root / "codes.npy").exists() or not (root / "ids.txt").exists():
+            raise FileNotFoundError(f"no code index in {root}: expected codes.npy + ids.txt (sub-command `build`)")
+        ids = [ln.strip() for ln in (root / "ids.txt").read_text(encoding="utf-8").splitlines() if ln.strip()]
+        return cls(np.load(root / "codes.npy"), ids)
+
+    def to(self, device="cuda:0"):
+        dev = torch.device(device)
+        self._dev = (torch.from_numpy(self.codes).to(dev), torch.from_numpy(self.r).to(dev))
+        return self
+
+    def search(self, q_codes, k):
+        """q_codes (nq, D) u8 -> (scores (nq,k) fp32, indices (nq,k) int32), one fused launch for all queries"""
+        from . import ops
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        q = np.ascontiguousarray(np.atleast_2d(q_codes), dtype=np.uint8)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query codes of dim {q.shape[1]} against an index of dim {self.dim}")
+        k = max(1, min(int(k), len(self)))
+        s, i = ops.search_codes(torch.from_numpy(q).to(db.device), torch.from_numpy(code_rnorm(q)).to(db.device), db, r_db, k)
+        return s.cpu().numpy(), i.cpu().numpy()
+
+    def neighbours(self, topk, chunk=4096):
+        """k-NN graph of the index over itself, own id removed: yields (row, [(neighbour row, score)] of length <= topk), queries in
+        chunks so that host and device memory stay bounded"""
+        k1 = min(int(topk) + 1, len(self))
+        for c0 in range(0, len(self), chunk):
+            s, idx = self.search(self.codes[c0:c0 + chunk], k1)
+            for j in range(idx.shape[0]):
+                row = [(int(i), float(v)) for i, v in zip(idx[j], s[j]) if i != c0 + j]
+                yield c0 + j, row[:max(k1 - 1, 0)]   # own id absent from the list (duplicates ranked above it): drop the last
+
+
+def build_index(c2df_dir, index_dir, log=print):
+    """`build`: containers -> index directory.  codes.npy (u8) for the code search; the fp32 IndexFlatIP of the dequantised unit
+    vectors in both layouts load_index accepts (faiss.index + paths.json, index.faiss + ids.txt); meta.json {dim, model_id}"""
+    from .faiss_io import write_index_flat_ip
+    ci = CodeIndex.from_c2df_dir(c2df_dir, log)
+    root = Path(index_dir)
+    ci.save(root)
+    unit = codes_to_unit(ci.codes)
+    write_index_flat_ip(str(root / "faiss.index"), unit)
+    write_index_flat_ip(str(root / "index.faiss"), unit)
+    (root / "paths.json").write_text(json.dumps(ci.ids, ensure_ascii=False, indent=2), encoding="utf-8")
+    (root / "meta.json").write_text(json.dumps({"dim": ci.dim, "model_id": ci.model_id}, ensure_ascii=False, indent=2), encoding="utf-8")
+    log(f"[OK] index of {len(ci)} containers, dim {ci.dim}, in {root}")
+    return ci
+
+
+def _query_codes(index_dir, c2df, topk):
+    """`query-c2df --codes`: a file -> result list; a directory -> {path: result list}, all queries in one fused call"""
+    ci = CodeIndex.load(index_dir)
+    src = Path(c2df)
+    files = sorted(src.glob("**/*.c2df")) if src.is_dir() else [src]
+    if not files:
+        raise RuntimeError(f"no .c2df under {src}")
+    s, idx = ci.search(np.stack([embedded_clip_codes(f)[0] for f in files]), topk)
+    res = [[{"path": ci.ids[i], "score": float(v)} for i, v in zip(idx[j], s[j])] for j in range(len(files))]
+    return {str(f): r for f, r in zip(files, res)} if src.is_dir() else res[0]
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df")
+    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / neighbours")
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name, arg in (("query-text", "--text"), ("query-image", "--image"), ("query-c2df", "--c2df")):
         p = sub.add_parser(name)
@@ -128,7 +264,34 @@ def main(argv=None):
         p.add_argument("--clip_ckpt", type=str, default=None)
         if name == "query-text":
             p.add_argument("--token_ids", type=str, default=None, help="comma-separated BPE ids (offline tokenizer bypass)")
+        if name == "query-c2df":
+            p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused i8 kernel; "
+                           "--c2df may then be a directory")
+    p = sub.add_parser("build", help="index directory from a directory of .c2df containers")
+    p.add_argument("--c2df_dir", type=Path, required=True)
+    p.add_argument("--index_dir", type=Path, required=True)
+    p = sub.add_parser("neighbours", help="k nearest neighbours of every vector of the code index, one JSON line each")
+    p.add_argument("--index_dir", type=Path, required=True)
+    p.add_argument("--topk", type=int, default=10)
+    p.add_argument("--out", type=Path, default=None)
     args = ap.parse_args(argv)
+    if args.cmd == "build":
+        build_index(args.c2df_dir, args.index_dir)
+        return 0
+    if args.cmd == "neighbours":
+        ci = CodeIndex.load(args.index_dir)
+        out = open(args.out, "w", encoding="utf-8") if args.out else sys.stdout
+        try:
+            for row, nb in ci.neighbours(args.topk):
+                out.write(json.dumps({"path": ci.ids[row], "neighbours": [{"path": ci.ids[i], "score": v} for i, v in nb]},
+                                     ensure_ascii=False) + "\n")
+        finally:
+            if args.out:
+                out.close()
+        return 0
+    if args.cmd == "query-c2df" and args.codes:
+        print(json.dumps(_query_codes(args.index_dir, args.c2df, args.topk), ensure_ascii=False, indent=2))
+        return 0
     vecs, paths = load_index(args.index_dir)
     if args.cmd == "query-c2df":
         q = decode_clip_from_c2df(args.c2df)[0][None, :]
