@@ -322,6 +322,23 @@ int sgic_search_codes_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d
                          int splits, uint8_t *d_work, size_t work_bytes, float *d_out_scores, int32_t *d_out_idx,
                          sgic_stream_t stream);
 
+/* The same search with fp32 queries (text / image vectors, CodeIndex.search_vectors): d_q (nq, D) fp32, 16-byte aligned, against
+ * the u8 codes d_db (n, D) and their d_rdb.  D % 64 == 0, D <= 2048 (three query planes in LDS), k <= 128, k <= n, anything
+ * else is SGIC_EINVAL (the caller keeps the fp32 path).  The query goes to fixed point: Q_j = clamp(rint(q_j * 2^22), -2^22,
+ * +2^22) as an integer (round to nearest even; a NaN coordinate gives 0), then to balanced base-256 digits
+ *   d0 = ((Q + 128) & 255) - 128, Q' = (Q - d0) >> 8, d1 = ((Q' + 128) & 255) - 128, d2 = (Q' - d1) >> 8,
+ * so Q = 65536 d2 + 256 d1 + d0 with d0, d1 in [-128, 127] and d2 in [-64, 64], three i8 planes.  With a_d = c_d - 128 and
+ * v_d = 2 c_d - 255 = 2 a_d + 1: S_p = sum_j d_p,j a_d,j (i8 MFMA, |S_p| <= 2^14 D, exact in int32) and, combined in int64,
+ *   M = sum_j Q_j v_d,j = 2 (65536 S_2 + 256 S_1 + S_0) + sum_j Q_j,   |M| <= 2^22 * 255 * D.
+ * Ranking key = float32(M) * r_d (one RNE int64 -> fp32 conversion, one fp32 multiply), order: key descending, equal keys ->
+ * lower database index; reported score = key * 2^-22 (exact).  For finite |q_j| <= 1 the score is within 2^-23 sqrt(D) + 2^-22
+ * of the fp64 q . v_d / |v_d| (query rounding of at most 2^-23 per coordinate times |v|_1 / |v| <= sqrt(D); three fp32
+ * roundings).  Splits, workspace (nq * splits * k * 8 bytes, 0 for one split) and the merge are those of the u8 entry;
+ * sgic_search_codes_f32q_work_bytes is host-only and takes no stream. */
+int sgic_search_codes_f32q_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes);
+int sgic_search_codes_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, int k, int splits,
+                           uint8_t *d_work, size_t work_bytes, float *d_out_scores, int32_t *d_out_idx, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

@@ -12,6 +12,15 @@
 // per-query LDS buffer of k + 64 entries (one block iteration adds at most 64 per query); a full buffer is pruned to the best k
 // by rank and raises the threshold.  The threshold only moves at block-wide sync points, after which every later candidate has a
 // higher index than everything kept, so a strict `>` implements the tie rule.
+//
+// fp32 queries against the same codes (search_f32q_kernel, CodeIndex.search_vectors).  The query goes to fixed point,
+// Q = clamp(rint(q 2^22), -2^22, 2^22) (NaN -> 0), and is cut into balanced base-256 digits Q = 65536 d2 + 256 d1 + d0 with
+// d0, d1 in [-128, 127], d2 in [-64, 64]: three i8 planes, each laid out in LDS exactly like the u8 query tile, quantised in the
+// kernel's prologue.  One database fragment feeds three MFMAs, S_p = sum d_p a_d, and
+//   M = 2 (65536 S_2 + 256 S_1 + S_0) + sum Q  ==  sum Q (2 c_d - 255)
+// in int64 (|M| <= 2^22 255 D needs 41 bits at D = 2048).  Key = float(M) * r_d, score = key * 2^-22 (exact); the candidate
+// buffers, pruning, splits and the merge are those of the u8 kernel.  D <= 2048: three planes of a 16-query tile plus the
+// candidate buffers at k = 128 take 120 KiB of the CU's 160 KiB of LDS, D = 4096 would not fit.
 #include <math.h>
 
 #include "common.h"
@@ -195,16 +204,169 @@ __global__ __launch_bounds__(256) void search_codes_kernel(const uint8_t *__rest
   }
 }
 
+constexpr float kQScale = 4194304.0f;   // 2^22: 2^23 would push the top digit to 128 at q = 1
+constexpr int kMaxDimF32Q = 2048;
+
+// sixteen fp32 query coordinates -> fixed point -> one 16-byte fragment per digit plane (byte j = coordinate j); returns sum Q
+__device__ __forceinline__ int quantise16(const float4 *__restrict__ src, v4i &p0, v4i &p1, v4i &p2) {
+  int sum = 0;
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    const float4 v = src[w];
+    const float x[4] = {v.x, v.y, v.z, v.w};
+    unsigned w0 = 0, w1 = 0, w2 = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      float t = x[b] * kQScale;
+      t = t == t ? t : 0.0f;
+      const int Q = (int)rintf(fminf(fmaxf(t, -kQScale), kQScale));
+      const int d0 = ((Q + 128) & 255) - 128, Q1 = (Q - d0) >> 8;
+      const int d1 = ((Q1 + 128) & 255) - 128, d2 = (Q1 - d1) >> 8;
+      sum += Q;
+      w0 |= (unsigned)(d0 & 255) << (8 * b);
+      w1 |= (unsigned)(d1 & 255) << (8 * b);
+      w2 |= (unsigned)(d2 & 255) << (8 * b);
+    }
+    p0[w] = (int)w0;
+    p1[w] = (int)w1;
+    p2[w] = (int)w2;
+  }
+  return sum;
+}
+
+// search_codes_kernel with an fp32 query tile: three digit planes in LDS, three MFMAs per database fragment, int64 combine.
+// No byte sums of the database rows are needed (v_d = 2 a_d + 1 turns into the `+ sum Q` term).
+template <int QF, int U>
+__global__ __launch_bounds__(256) void search_f32q_kernel(const float *__restrict__ q, const uint8_t *__restrict__ db,
+                                                          const float *__restrict__ r_db, int nq, int n, int D, int k,
+                                                          int rows_per_split, int splits, int final_out, float *__restrict__ out_key,
+                                                          int *__restrict__ out_idx) {
+  constexpr int QT = 16 * QF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int steps = D >> 6;
+  const int cap = k + kCandPerIter;
+  const int plane = QF * steps * 64;         // fragments per digit plane
+  v4i *A = reinterpret_cast<v4i *>(smem);   // [3 planes][QF][steps][64 lanes] fragments
+  float *keys = reinterpret_cast<float *>(smem + (size_t)3 * QT * D);
+  int *idxs = reinterpret_cast<int *>(keys + QT * cap);
+  unsigned long long *sq = reinterpret_cast<unsigned long long *>(idxs + QT * cap);   // sum Q per query: up to 2^33 at D = 2048
+  int *cnt = reinterpret_cast<int *>(sq + QT);
+  float *thr = reinterpret_cast<float *>(cnt + QT);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+
+  if (tid < QT) {
+    cnt[tid] = 0;
+    thr[tid] = -INFINITY;
+    sq[tid] = 0;
+  }
+  __syncthreads();
+  for (int i = tid; i < plane; i += 256) {   // sixteen coordinates -> one fragment in each plane per (query fragment, step, lane)
+    const int ln = i & 63, t = i >> 6;
+    const int step = t % steps, f = t / steps;
+    const int row = f * 16 + (ln & 15);
+    int qi = qbase + row;
+    qi = qi < nq ? qi : nq - 1;
+    v4i p0, p1, p2;
+    const int s = quantise16(reinterpret_cast<const float4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4)), p0, p1, p2);
+    atomicAdd(&sq[row], (unsigned long long)(long long)s);
+    A[i] = p0;
+    A[plane + i] = p1;
+    A[2 * plane + i] = p2;
+  }
+  __syncthreads();
+
+  long long sumq[QF][4];
+  float thr_r[QF][4];
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      sumq[f][r] = (long long)sq[f * 16 + 4 * (lane >> 4) + r];
+      thr_r[f][r] = -INFINITY;
+    }
+
+  const int row0 = split * rows_per_split;
+  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
+  for (int base = row0; base < row_end; base += kCandPerIter) {
+    const int my = base + wave * 16 + (lane & 15);
+    const int myc = my < n ? my : n - 1;
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    v4i acc[3][QF];
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+      for (int f = 0; f < QF; f++) acc[p][f] = v4i{0, 0, 0, 0};
+    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
+      uint4 bv[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const v4i b = to_i8x16(bv[u]);
+#pragma unroll
+        for (int p = 0; p < 3; p++)
+#pragma unroll
+          for (int f = 0; f < QF; f++)
+            acc[p][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[p * plane + (f * steps + s0 + u) * 64 + lane], b, acc[p][f], 0, 0, 0);
+      }
+    }
+    const float rd = r_db[myc];
+    const bool valid = my < row_end;
+    int any = 0;
+#pragma unroll
+    for (int f = 0; f < QF; f++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const long long M = 2 * (65536LL * acc[2][f][r] + 256LL * acc[1][f][r] + acc[0][f][r]) + sumq[f][r];
+        const float key = (float)M * rd;
+        if (valid && key > thr_r[f][r]) {
+          const int ql = f * 16 + 4 * (lane >> 4) + r;
+          const int pos = atomicAdd(&cnt[ql], 1);
+          keys[ql * cap + pos] = key;
+          idxs[ql * cap + pos] = my;
+          any = 1;
+        }
+      }
+    if (__syncthreads_or(any)) {
+      for (int ql = wave; ql < QT; ql += 4) {
+        const int c = cnt[ql];
+        if (c > k) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int f = 0; f < QF; f++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) thr_r[f][r] = thr[f * 16 + 4 * (lane >> 4) + r];
+    }
+  }
+  __syncthreads();
+  for (int ql = wave; ql < QT; ql += 4) {
+    const int gq = qbase + ql;
+    if (gq >= nq) break;
+    int c = cnt[ql];
+    if (c > 0) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
+    c = c < k ? c : k;
+    const size_t o = ((size_t)gq * splits + split) * k;
+    for (int j = lane; j < k; j += 64) {
+      const float key = j < c ? keys[ql * cap + j] : -INFINITY;
+      out_key[o + j] = final_out ? key * (1.0f / kQScale) : key;
+      out_idx[o + j] = j < c ? idxs[ql * cap + j] : -1;
+    }
+  }
+}
+
 // per query: k-way selection over the splits' sorted lists (splits ascend in database index, so the index breaks ties)
 __global__ __launch_bounds__(256) void search_merge_kernel(const float *__restrict__ ws_key, const int *__restrict__ ws_idx,
-                                                           const float *__restrict__ r_q, int splits, int k,
+                                                           const float *__restrict__ r_q, float scale, int splits, int k,
                                                            float *__restrict__ out_s, int *__restrict__ out_i) {
   __shared__ unsigned short head[kMaxSplits];
   __shared__ float wk[4];
   __shared__ int wi[4], wsp[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t qo = (size_t)blockIdx.x * splits * k;
-  const float rq = r_q[blockIdx.x];
+  const float rq = r_q ? r_q[blockIdx.x] : scale;   // u8 queries: their reciprocal norm; fp32 queries: the constant 2^-22
   for (int s = tid; s < splits; s += 256) head[s] = 0;
   __syncthreads();
   for (int j = 0; j < k; j++) {
@@ -243,12 +405,17 @@ struct Plan {
 };
 
 size_t lds_bytes(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)D + (size_t)(k + kCandPerIter) * 8 + 12); }
+size_t lds_bytes_f32q(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)3 * D + (size_t)(k + kCandPerIter) * 8 + 16); }
 
-int make_plan(int nq, int n, int D, int k, int splits, Plan *p) {
+int make_plan(int nq, int n, int D, int k, int splits, bool f32q, Plan *p) {
   SGIC_REQUIRE(nq > 0 && n > 0 && k > 0 && k <= n, "sizes");
   SGIC_REQUIRE(k <= kMaxK, "the fused search keeps at most 128 results per query");
   SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "D must be a multiple of 64, at most 4096 (int32 exactness)");
-  p->qf = (nq > 16 && lds_bytes(4, D, k) <= (size_t)kLdsBigTile) ? 4 : 1;
+  SGIC_REQUIRE(!f32q || D <= kMaxDimF32Q, "fp32 queries: D at most 2048 (three query digit planes have to fit the LDS)");
+  if (f32q)   // three planes: the wide tile is 32 queries
+    p->qf = (nq > 16 && lds_bytes_f32q(2, D, k) <= (size_t)kLdsBigTile) ? 2 : 1;
+  else
+    p->qf = (nq > 16 && lds_bytes(4, D, k) <= (size_t)kLdsBigTile) ? 4 : 1;
   p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
   SGIC_REQUIRE(splits <= kMaxSplits, "splits");
   if (splits <= 0) {   // cover the chip a few times over when there are few query tiles
@@ -262,7 +429,7 @@ int make_plan(int nq, int n, int D, int k, int splits, Plan *p) {
   const int per = (n + splits - 1) / splits;
   p->rows_per_split = (per + kCandPerIter - 1) / kCandPerIter * kCandPerIter;
   p->splits = (n + p->rows_per_split - 1) / p->rows_per_split;   // no empty split
-  p->lds = lds_bytes(p->qf, D, k);
+  p->lds = f32q ? lds_bytes_f32q(p->qf, D, k) : lds_bytes(p->qf, D, k);
   p->work_bytes = p->splits > 1 ? (size_t)nq * p->splits * k * 8 : 0;
   return SGIC_OK;
 }
@@ -281,11 +448,25 @@ int launch_search(const Plan &p, const uint8_t *q, const float *r_q, const uint8
   return sgic::check_launch("search_codes_kernel");
 }
 
+template <int QF, int U>
+int launch_search_f32q(const Plan &p, const float *q, const uint8_t *db, const float *r_db, int nq, int n, int D, int k, float *okey,
+                       int *oidx, hipStream_t st) {
+  static bool lds_raised = false;   // largest use: 16 queries, D = 2048, k = 128 -> 120.25 KiB
+  if (p.lds > 60 * 1024 && !lds_raised) {
+    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_f32q_kernel<QF, U>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 128 * 1024));
+    lds_raised = true;
+  }
+  search_f32q_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, db, r_db, nq, n, D, k, p.rows_per_split, p.splits,
+                                                                        p.splits == 1, okey, oidx);
+  return sgic::check_launch("search_f32q_kernel");
+}
+
 }  // namespace
 
 extern "C" int sgic_search_codes_u8_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes) {
   Plan p;
-  const int rc = make_plan(nq, n, D, k, splits, &p);
+  const int rc = make_plan(nq, n, D, k, splits, false, &p);
   if (rc != SGIC_OK) return rc;
   if (splits_used) *splits_used = p.splits;
   if (bytes) *bytes = p.work_bytes;
@@ -296,7 +477,7 @@ extern "C" int sgic_search_codes_u8(const uint8_t *d_q, const float *d_rq, const
                                     int D, int k, int splits, uint8_t *d_work, size_t work_bytes, float *d_out_scores,
                                     int32_t *d_out_idx, sgic_stream_t stream) {
   Plan p;
-  const int rc = make_plan(nq, n, D, k, splits, &p);
+  const int rc = make_plan(nq, n, D, k, splits, false, &p);
   if (rc != SGIC_OK) return rc;
   SGIC_REQUIRE(d_q && d_rq && d_db && d_rdb && d_out_scores && d_out_idx, "null pointer");
   SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db | (uintptr_t)d_work) % 16 == 0, "codes and workspace must be 16-byte aligned");
@@ -315,7 +496,45 @@ extern "C" int sgic_search_codes_u8(const uint8_t *d_q, const float *d_rq, const
                                   : launch_search<1, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st));
   if (lrc != SGIC_OK) return lrc;
   if (p.splits > 1) {
-    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, d_rq, p.splits, k, d_out_scores, d_out_idx);
+    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, d_rq, 1.0f, p.splits, k, d_out_scores, d_out_idx);
+    return sgic::check_launch("search_merge_kernel");
+  }
+  return SGIC_OK;
+}
+
+extern "C" int sgic_search_codes_f32q_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes) {
+  Plan p;
+  const int rc = make_plan(nq, n, D, k, splits, true, &p);
+  if (rc != SGIC_OK) return rc;
+  if (splits_used) *splits_used = p.splits;
+  if (bytes) *bytes = p.work_bytes;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_search_codes_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, int k, int splits,
+                                      uint8_t *d_work, size_t work_bytes, float *d_out_scores, int32_t *d_out_idx,
+                                      sgic_stream_t stream) {
+  Plan p;
+  const int rc = make_plan(nq, n, D, k, splits, true, &p);
+  if (rc != SGIC_OK) return rc;
+  SGIC_REQUIRE(d_q && d_db && d_rdb && d_out_scores && d_out_idx, "null pointer");
+  SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db | (uintptr_t)d_work) % 16 == 0, "queries, codes and workspace must be 16-byte aligned");
+  SGIC_REQUIRE(p.work_bytes == 0 || (d_work && work_bytes >= p.work_bytes), "workspace (sgic_search_codes_f32q_work_bytes)");
+  hipStream_t st = to_stream(stream);
+  float *okey = d_out_scores;
+  int *oidx = d_out_idx;
+  if (p.splits > 1) {
+    okey = reinterpret_cast<float *>(d_work);
+    oidx = reinterpret_cast<int *>(d_work + (size_t)nq * p.splits * k * 4);
+  }
+  const bool u8 = D % 512 == 0;
+  const int lrc = p.qf == 2 ? (u8 ? launch_search_f32q<2, 8>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
+                                  : launch_search_f32q<2, 1>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st))
+                            : (u8 ? launch_search_f32q<1, 8>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
+                                  : launch_search_f32q<1, 1>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st));
+  if (lrc != SGIC_OK) return lrc;
+  if (p.splits > 1) {
+    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, nullptr, 1.0f / kQScale, p.splits, k, d_out_scores, d_out_idx);
     return sgic::check_launch("search_merge_kernel");
   }
   return SGIC_OK;

@@ -1017,6 +1017,28 @@ def search_codes(q_codes, r_q, db_codes, r_db, k, splits=None):
     return os_, oi
 
 
+def search_codes_f32q(q, db_codes, r_db, k, splits=None):
+    """fused exact search of fp32 queries over u8 codes (csrc/search.hip, search_f32q_kernel): q (nq, D) fp32, db_codes (n, D) u8,
+    r_db (n,) fp32 (search.code_rnorm), all contiguous on one device -> (scores (nq,k) fp32, idx (nq,k) int32), score descending,
+    ties -> lower index.  The query is taken to 2^-22 fixed point (include/sgic.h has the arithmetic).  D % 64 == 0, D <= 2048,
+    k <= min(n, 128); `splits` forces the number of database splits (tests)."""
+    require_gpu()
+    for t, dt in ((q, torch.float32), (db_codes, torch.uint8), (r_db, torch.float32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
+    nq, D = q.shape
+    n, Dd = db_codes.shape
+    assert D == Dd and r_db.shape == (n,)
+    want = 0 if splits is None else int(splits)
+    used, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+    call("sgic_search_codes_f32q_work_bytes", nq, n, D, int(k), want, ctypes.byref(used), ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=db_codes.device) if nbytes.value else None
+    os_ = torch.empty(nq, k, device=db_codes.device, dtype=torch.float32)
+    oi = torch.empty(nq, k, device=db_codes.device, dtype=torch.int32)
+    call("sgic_search_codes_f32q", _p(q), _p(db_codes), _p(r_db), nq, n, D, int(k), want, _p(work), ctypes.c_size_t(nbytes.value), _p(os_),
+         _p(oi))
+    return os_, oi
+
+
 def jpeg_decode_batch(params, scan, tabs, segs, quant, B, H, W, total_blocks, plane_bytes, max_blocks, out=None, check=True):
     """baseline JPEG batch -> (B,H,W,3) u8 on the device (csrc/jpeg.hip; descriptors built by sgic_amd.jpeg.JpegBatch)"""
     require_gpu()

@@ -6,8 +6,9 @@
 package is importable and otherwise takes ready-made ids via --token_ids.  The search itself is exact inner product: one fp32 MFMA GEMM (queries x
 database^T) + a top-k kernel on the GPU.
 `build` makes an index directory from a directory of containers (the reference's `build.py build`); besides the fp32 index it
-writes the u8 codes themselves (codes.npy), which `query-c2df --codes` and `neighbours` search with the fused i8 kernel
-(csrc/search.hip): integer inner products, no fp32 database and no score matrix on the device."""
+writes the u8 codes themselves (codes.npy), which `--codes` (on all three query commands) and `neighbours` search with the fused
+i8 kernels (csrc/search.hip): integer inner products, no fp32 database and no score matrix on the device.  A u8 query code is used
+as it is; an fp32 text / image vector is taken to 2^-22 fixed point and searched as three i8 digit planes."""
 import argparse
 import json
 import os
@@ -141,7 +142,10 @@ def code_rnorm(codes, chunk=1 << 16):
 
 class CodeIndex:
     """an index of the u8 CLIP codes themselves: `codes` (n, D) u8, `ids` [n].  Searched with the fused i8 kernel
-    (ops.search_codes): scores are the cosine of the dequantised vectors, 1 byte per coordinate on the device."""
+    (ops.search_codes) for u8 query codes and with its fp32-query sibling (ops.search_codes_f32q) for text / image vectors: scores
+    are the cosine of the dequantised vectors, 1 byte per coordinate on the device."""
+    MAX_DIM_F32Q = 2048     # three query digit planes have to fit the LDS (csrc/search.hip)
+    MAX_QUERY_NORM = 1.0 + 1e-3
 
     def __init__(self, codes, ids, model_id=None):
         self.codes = np.ascontiguousarray(codes, dtype=np.uint8)
@@ -214,6 +218,30 @@ class CodeIndex:
         s, i = ops.search_codes(torch.from_numpy(q).to(db.device), torch.from_numpy(code_rnorm(q)).to(db.device), db, r_db, k)
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def search_vectors(self, q, k):
+        """q (nq, D) fp32 unit vectors (text / image queries), numpy or a tensor on either side -> (scores (nq,k) fp32, indices
+        (nq,k) int32), one fused launch.  Refused: non-finite values, a row longer than 1 + 1e-3 (not a unit query: the fixed-point
+        range is [-1, 1]), another dim, and an index of dim > 2048, which only the fp32 files can serve"""
+        from . import ops
+        if self.dim > self.MAX_DIM_F32Q:
+            raise ValueError(f"fp32 queries against a code index need dim <= {self.MAX_DIM_F32Q}, this one has {self.dim}: use the fp32 "
+                             "index files (faiss.index + paths.json or index.faiss + ids.txt), i.e. the query without --codes")
+        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        t = (t[None, :] if t.ndim == 1 else t).to(torch.float32)
+        if t.ndim != 2 or t.shape[1] != self.dim:
+            raise ValueError(f"query vectors of shape {tuple(t.shape)} against an index of dim {self.dim}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("query vectors hold non-finite values")
+        longest = float(t.double().norm(dim=1).max()) if t.shape[0] else 0.0
+        if longest > self.MAX_QUERY_NORM:
+            raise ValueError(f"query of l2 norm {longest:.6g}: search_vectors takes unit vectors (norm <= {self.MAX_QUERY_NORM})")
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        k = max(1, min(int(k), len(self)))
+        s, i = ops.search_codes_f32q(t.to(db.device).contiguous(), db, r_db, k)
+        return s.cpu().numpy(), i.cpu().numpy()
+
     def neighbours(self, topk, chunk=4096):
         """k-NN graph of the index over itself, own id removed: yields (row, [(neighbour row, score)] of length <= topk), queries in
         chunks so that host and device memory stay bounded"""
@@ -253,6 +281,24 @@ def _query_codes(index_dir, c2df, topk):
     return {str(f): r for f, r in zip(files, res)} if src.is_dir() else res[0]
 
 
+def _query_vector(args):
+    """the query of `query-text` / `query-image` / `query-c2df` as a (1, D) fp32 unit vector"""
+    if args.cmd == "query-c2df":
+        return decode_clip_from_c2df(args.c2df)[0][None, :]
+    from . import weights as W
+    from .compress import load_state
+    from .config import CLIP_B32
+    if args.cmd == "query-image":
+        from .codec import ClipCodec
+        from .compress import load_image
+        csd = load_state(args.clip_ckpt, W.clip_spec, CLIP_B32, 4321)
+        return ClipCodec(csd, CLIP_B32, "cuda:0").image_to_unit_vec(load_image(args.image))[None, :]
+    from .clip import ClipTextHIP
+    toks = tokenize(args.text, CLIP_B32.ctx, args.token_ids)
+    tsd = load_state(args.clip_ckpt, W.clip_text_spec, CLIP_B32, 4321)
+    return encode_text(toks, ClipTextHIP(tsd, CLIP_B32, "cuda:0"))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / neighbours")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -267,6 +313,9 @@ def main(argv=None):
         if name == "query-c2df":
             p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused i8 kernel; "
                            "--c2df may then be a directory")
+        else:
+            p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused fp32-query "
+                           "kernel instead of the fp32 index files")
     p = sub.add_parser("build", help="index directory from a directory of .c2df containers")
     p.add_argument("--c2df_dir", type=Path, required=True)
     p.add_argument("--index_dir", type=Path, required=True)
@@ -292,24 +341,13 @@ def main(argv=None):
     if args.cmd == "query-c2df" and args.codes:
         print(json.dumps(_query_codes(args.index_dir, args.c2df, args.topk), ensure_ascii=False, indent=2))
         return 0
+    if args.codes:   # text / image vector against the u8 codes
+        ci = CodeIndex.load(args.index_dir)
+        sim, idx = ci.search_vectors(_query_vector(args), args.topk)
+        print(json.dumps([{"path": ci.ids[i], "score": float(v)} for i, v in zip(idx[0], sim[0]) if i != -1], ensure_ascii=False, indent=2))
+        return 0
     vecs, paths = load_index(args.index_dir)
-    if args.cmd == "query-c2df":
-        q = decode_clip_from_c2df(args.c2df)[0][None, :]
-    elif args.cmd == "query-image":
-        from . import weights as W
-        from .codec import ClipCodec
-        from .compress import load_image, load_state
-        from .config import CLIP_B32
-        csd = load_state(args.clip_ckpt, W.clip_spec, CLIP_B32, 4321)
-        q = ClipCodec(csd, CLIP_B32, "cuda:0").image_to_unit_vec(load_image(args.image))[None, :]
-    else:
-        from . import weights as W
-        from .clip import ClipTextHIP
-        from .compress import load_state
-        from .config import CLIP_B32
-        toks = tokenize(args.text, CLIP_B32.ctx, args.token_ids)
-        tsd = load_state(args.clip_ckpt, W.clip_text_spec, CLIP_B32, 4321)
-        q = encode_text(toks, ClipTextHIP(tsd, CLIP_B32, "cuda:0"))
+    q = _query_vector(args)
     print(json.dumps([{"path": p, "score": s} for p, s in do_search(q, vecs, paths, args.topk)], ensure_ascii=False, indent=2))
     return 0
 

@@ -61,7 +61,7 @@ def ndjson(obj):
 
 class ResidentService:
     def __init__(self, ckpt_path=None, clip_ckpt=None, device="cuda:0", small=False, index_dir=None, preview_cache=None,
-                 media_roots=None):
+                 media_roots=None, code_index=False):
         from . import weights as W
         from .codec import ClipCodec, Codec
         from .compress import load_state
@@ -82,7 +82,8 @@ class ResidentService:
         self.media_roots = [Path(p).resolve() for p in (media_roots or [os.getenv("MEDIA_ROOT", "./"), "./data", "./IO"])] + \
             [self.index_dir, self.index_dir.parent]
         self._lock = threading.Lock()
-        self._index = {}                     # index_dir -> (stamp, device matrix, ids)
+        self.code_index = bool(code_index)   # search codes.npy (u8, fused kernels) where an index directory has it
+        self._index = {}                     # index_dir -> (stamp, device matrix, ids, CodeIndex or None)
         self.build_seconds = time.perf_counter() - t0
 
     # ------------------------------------------------------------------ codec endpoints
@@ -212,24 +213,34 @@ class ResidentService:
 
     # ------------------------------------------------------------------ search endpoints
     def _load_index(self, index_dir):
-        from .search import load_index
+        """-> (device matrix, ids, CodeIndex or None): the u8 codes when the service was built with code_index=True and the
+        directory holds codes.npy + ids.txt, else the fp32 vectors"""
+        from .search import CodeIndex, load_index
         d = Path(index_dir or self.index_dir).resolve()
         stamp = tuple(sorted((f.name, f.stat().st_mtime_ns, f.stat().st_size) for f in d.iterdir())) if d.is_dir() else None
         hit = self._index.get(str(d))
         if hit is None or hit[0] != stamp:
-            vecs, ids = load_index(d)
-            hit = (stamp, torch.from_numpy(np.ascontiguousarray(vecs, dtype=np.float32)).to(self.device), ids)
+            if self.code_index and (d / "codes.npy").exists() and (d / "ids.txt").exists():
+                ci = CodeIndex.load(d).to(self.device)
+                hit = (stamp, ci._dev[0], ci.ids, ci)                  # resident: the u8 matrix and its reciprocal norms
+            else:
+                vecs, ids = load_index(d)
+                hit = (stamp, torch.from_numpy(np.ascontiguousarray(vecs, dtype=np.float32)).to(self.device), ids, None)
             self._index[str(d)] = hit                                  # the database stays resident in HBM between queries
-        return hit[1], hit[2]
+        return hit[1], hit[2], hit[3]
 
     def _search(self, q, topk, index_dir):
+        """q: (1, D) fp32 unit vector, or (1, D) u8 codes (the c2df stream against a code index)"""
         from . import ops
-        db, ids = self._load_index(index_dir)
+        db, ids, ci = self._load_index(index_dir)
         k = max(1, min(int(topk), db.shape[0]))
         with self._lock:
-            dq = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
-            s, i = ops.topk_rows(ops.gemm(dq, db, w_const=False), k)                   # exact inner product + top-k (IndexFlatIP.search)
-            s, i = s.cpu().numpy(), i.cpu().numpy()
+            if ci is not None:
+                s, i = ci.search(q, k) if np.asarray(q).dtype == np.uint8 else ci.search_vectors(q, k)
+            else:
+                dq = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
+                s, i = ops.topk_rows(ops.gemm(dq, db, w_const=False), k)               # exact inner product + top-k (IndexFlatIP.search)
+                s, i = s.cpu().numpy(), i.cpu().numpy()
         return [{"path": ids[j], "score": float(s[0, r])} for r, j in enumerate(i[0]) if j != -1]
 
     def _stream(self, start_meta, make_query, topk, index_dir):
@@ -277,7 +288,9 @@ class ResidentService:
     def search_c2df(self, filename, data, topk=10, index_dir=None):
         """POST /search/stream/c2df (webapp.py:289-317): needs no model -- the query is the embedded CLIP code"""
         def query():
-            from .search import embedded_clip_vector
+            from .search import embedded_clip_codes, embedded_clip_vector
+            if self._load_index(index_dir)[2] is not None:             # code index: the embedded u8 code is the query as it is
+                return embedded_clip_codes(data)[0][None, :]
             return embedded_clip_vector(data)[0][None, :]
 
         return self._stream({"query_type": "c2df", "filename": filename}, query, topk, index_dir)

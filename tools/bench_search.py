@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Time the fused u8 code search (ops.search_codes, csrc/search.hip) against the fp32 path it stands beside (ops.gemm +
-ops.topk_rows on the codes_to_unit database), device time only, uploads excluded for both.
+"""Time the fused searches over u8 codes (csrc/search.hip: ops.search_codes for u8 query codes, ops.search_codes_f32q for fp32
+text / image vectors) against the fp32 path they stand beside (ops.gemm + ops.topk_rows on the codes_to_unit database), device time
+only, uploads excluded for both.
 
 Protocol: seeded data made on the device, both paths warmed up, then timed with device events in one process, alternating, twice
 (the two repeats show the spread).  D = 512, k = 10, n in {1e4, 1e6}, nq in {1, 16, 1024}; plus the corpus self-search
 (`neighbours`) at n = 1e5, where the fp32 path would need a 40 GB score matrix in one piece and is timed in query chunks instead.
+fp32 queries (random unit vectors): the same n, nq in {1, 16, 256}; each database fragment feeds three MFMAs there, so the i8 share
+counts 3 n nq D multiply-accumulates.
 
 Per point: milliseconds per call; for nq <= 16 the database bytes the fused kernel has to read over its time, as a share of the
 6.3 TB/s this card's HBM delivers; for nq = 1024 its i8 multiply-accumulates over time as a share of the dense i8 MFMA peak
@@ -89,6 +92,40 @@ def point(n, nq, dim, k, db, r_db, db32, repeats=2):
     return rec
 
 
+def point_f32q(n, nq, dim, k, db, r_db, db32, repeats=2):
+    g = torch.Generator(device=DEV).manual_seed(2000 + nq)
+    q32 = torch.randn(nq, dim, generator=g, device=DEV)
+    q32 = (q32 / q32.norm(dim=1, keepdim=True)).contiguous()
+    fused = lambda: ops.search_codes_f32q(q32, db, r_db, k)                    # noqa: E731
+    parent = lambda: ops.topk_rows(ops.gemm(q32, db32, w_const=False), k)      # noqa: E731
+    for _ in range(2):
+        fused()
+    for _ in range(8):
+        parent()
+    ops.finalize_autotune()
+    torch.cuda.synchronize()
+    work = n * nq
+    iters = 50 if work <= 2e7 else (10 if work <= 2e8 else 3)
+    tf, tp = [], []
+    for _ in range(repeats):
+        tf.append(timed(fused, iters))
+        tp.append(timed(parent, iters))
+    s_f, i_f = fused()
+    s_p, i_p = parent()
+    rec = {"what": "fp32 queries", "n": n, "nq": nq, "D": dim, "k": k, "iters": iters, "fused_ms": tf, "parent_ms": tp,
+           "speedup": min(tp) / min(tf), "ids_equal_share": float((i_f == i_p).float().mean()),
+           "max_score_diff": float((s_f - s_p).abs().max())}
+    t = min(tf) * 1e-3
+    if nq <= 16:
+        rec["bound"] = "HBM"
+        rec["fused_share_of_hbm"] = n * dim / t / HBM_BYTES_PER_S
+    else:
+        t_mac, t_mem = 3 * n * nq * dim / I8_MAC_PER_S, n * dim / HBM_BYTES_PER_S
+        rec["bound"] = "i8 MFMA" if t_mac >= t_mem else "HBM"
+        rec["fused_share_of_i8_peak"] = 3 * n * nq * dim / t / I8_MAC_PER_S
+    return rec
+
+
 def neighbours_point(n, dim, k, chunk=4096, repeats=2):
     db = unit_codes(n, dim, 7)
     r = torch.from_numpy(code_rnorm(db.cpu().numpy())).to(DEV)
@@ -131,6 +168,8 @@ def main(argv=None):
         db32 = to_unit(db)
         for nq in (1, 16, 1024):
             print(json.dumps(point(n, nq, dim, k, db, r_db, db32)), flush=True)
+        for nq in (1, 16, 256):
+            print(json.dumps(point_f32q(n, nq, dim, k, db, r_db, db32)), flush=True)
         del db, r_db, db32
     print(json.dumps(neighbours_point(10 ** 4 if args.quick else 10 ** 5, dim, k)), flush=True)
     return 0
