@@ -372,6 +372,17 @@ int sgic_clip_preprocess_ragged_workspace(int B, const int32_t *h_geo, int S, si
 int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_stride, int ldx, int B, const int32_t *h_geo, int S,
                                 const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
                                 sgic_stream_t stream);
+/* CLIP preprocessing straight from the u8 canvas of the ingest: d_canvas (B, Hc, Wc, 3) interleaved RGB, image b its top-left H x W
+ * region with h_geo[6b .. 6b+5] = (H, W, OH, OW, top, left) as above (H <= Hc, W <= Wc; bytes of the canvas outside an image are
+ * never read) -> d_out (B, 3, S, S) fp32.  The bytes are resampled as they are -- bit-identical to Pillow's
+ * `Image.fromarray(u8).resize((OW, OH), BICUBIC)`, centre crop, / 255, (v - mean) / std -- where the fp32 entry points above first
+ * truncate `(x * 0.5 + 0.5) * 255` back to u8.  There is no fp32 image and no planar u8 copy: the horizontal pass reads the canvas
+ * and covers the S cropped columns of the source rows the vertical pass reads.  d_work: a device workspace (16-byte aligned) of at
+ * least the *bytes sgic_clip_preprocess_u8canvas_workspace returns (host-only, takes no stream); per image, in batch order: the four
+ * tables as above and the horizontal pass (3 x rows x S u8, rows: a bound of the row window), each 16-byte aligned. */
+int sgic_clip_preprocess_u8canvas_workspace(int B, const int32_t *h_geo, int S, size_t *bytes);
+int sgic_clip_preprocess_u8canvas(const uint8_t *d_canvas, int Hc, int Wc, int B, const int32_t *h_geo, int S, const float *mean3,
+                                  const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out, sgic_stream_t stream);
 
 /* Baseline JPEG decode of a batch of B equal-geometry files to RGB u8 HWC (B, H, W, 3) on the device -- the pixel decode inside
  * the reference's Test_Dataset (`Image.open(path).convert("RGB")`, compress.py:151-168), bit-exact with Pillow / libjpeg-turbo's

@@ -129,6 +129,20 @@ class ClipHIP:
              self.mean, self.std, ops._p(work), ctypes.c_size_t(nbytes.value), ops._p(out))
         return out
 
+    def preprocess_u8(self, canvas, hw):
+        """canvas (B,Hc,Wc,3) u8 on the device (what DeviceIngest.start leaves there), image b its top-left hw[b] region -> (B,3,S,S)
+        normalised.  The decoded bytes are resampled as they are (the reference's build-images hands the PIL image to the transform):
+        bit-identical to Pillow, where preprocess() first truncates (x*0.5+0.5)*255 like the reference's compress.py.  No fp32 image."""
+        if canvas.dim() != 4 or canvas.shape[3] != 3 or canvas.dtype != torch.uint8:
+            raise ValueError(f"canvas must be (B, Hc, Wc, 3) uint8, got {tuple(canvas.shape)} {canvas.dtype}")
+        B, Hc, Wc, _ = canvas.shape
+        hw = np.asarray(hw, dtype=np.int64).reshape(B, 2)
+        if (hw <= 0).any() or (hw[:, 0] > Hc).any() or (hw[:, 1] > Wc).any():
+            raise ValueError(f"extents {hw.tolist()} outside the {Hc}x{Wc} canvas")
+        S = self.cfg.image_size
+        geo = np.array([(h, w) + resize_geometry(h, w, S) for h, w in hw.tolist()], dtype=np.int32)
+        return ops.clip_preprocess_u8canvas(canvas.contiguous(), geo, S, self.mean, self.std)
+
     def tower(self, pre):
         """(B,3,S,S) normalised -> (unit fp32 (B,D), u8 codes (B,D))"""
         cfg = self.cfg
@@ -147,6 +161,10 @@ class ClipHIP:
 
     def encode(self, x, H=None, W=None, hw=None):
         return self.tower(self.preprocess(x, H, W, hw))
+
+    def encode_u8(self, canvas, hw):
+        """u8 canvas + extents (preprocess_u8) -> (unit fp32 (B,D), u8 codes (B,D))"""
+        return self.tower(self.preprocess_u8(canvas, hw))
 
 
 class ClipTextHIP:

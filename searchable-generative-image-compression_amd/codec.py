@@ -181,6 +181,11 @@ class ClipCodec:
         """(B,3,Hp,Wp) device batch -> (unit (B,D) device, u8 (B,D) device); hw: per-image extents (ClipHIP.preprocess)"""
         return self.model.encode(x, H, W, hw)
 
+    def u8_to_codes(self, canvas, hw):
+        """(B,Hc,Wc,3) u8 device canvas + (B,2) extents -> (unit (B,D) device, u8 (B,D) device): the decoded bytes as they are, no fp32
+        image (ClipHIP.preprocess_u8; search.py build-images)"""
+        return self.model.encode_u8(canvas, hw)
+
     def meta(self, dim):
         return {"model_id": self.model_name, "dim": int(dim), "quant": "u8_symmetric_-1_1", "codec": "zstd", "zstd_level": 19}
 

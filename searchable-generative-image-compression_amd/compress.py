@@ -71,11 +71,13 @@ def unique_stems(files):
     return [p for i, p in enumerate(files) if last[stem_of(p)] == i]
 
 
-def assemble_index(files, vecs, bit_dir, index_dir, dim):
+def assemble_index(files, vecs, bit_dir, index_dir, dim, write_codes=False):
     """Rank-0 index assembly (compress.py:295-306).  The reference walks `sorted(glob(clip_dir/*.npy))` -- i.e. the
     UNIQUE stems ordered by the string "<stem>.npy" -- and adds a vector for every stem whose .c2df exists, with the
     doc id `os.path.join(bit_dir, "<stem>.c2df")`.  `vecs[i]` belongs to `files[i]`; two inputs that share a stem
-    (a.jpg, a.png) collapse to one entry like their .npy files do (the later file in sorted order wins)."""
+    (a.jpg, a.png) collapse to one entry like their .npy files do (the later file in sorted order wins).
+    write_codes: also write index_dir/codes.npy, the u8 CLIP codes the indexed containers carry (read back from them), rows in the
+    order of ids.txt: the index directory then serves the code search (search.py --codes, neighbours) without a `build` pass."""
     from .faiss_io import FaissDB
     by_stem = {}
     for i, p in enumerate(files):
@@ -91,6 +93,10 @@ def assemble_index(files, vecs, bit_dir, index_dir, dim):
             db.add(vecs[by_stem[s]], doc_id)
             ids.append(doc_id)
     db.persist()
+    if write_codes:
+        from .search import embedded_clip_codes
+        # db.ids, not ids: an index directory that already held entries keeps them (FaissDB appends), and codes.npy covers every row
+        np.save(os.path.join(index_dir, "codes.npy"), np.stack([embedded_clip_codes(d)[0] for d in db.ids]))
     return ids
 
 
@@ -109,6 +115,8 @@ def main(argv=None):
     ap.add_argument("--gpu_progressive_jpeg", action="store_true",
                     help="decode progressive (and mixed baseline / progressive) JPEG batches on the GPU too (default: host; "
                          "also SGIC_GPU_JPEG_PROGRESSIVE=1)")
+    ap.add_argument("--write_codes", action="store_true",
+                    help="also write faiss/codes.npy: the u8 CLIP codes of the containers, rows in the order of ids.txt (search.py --codes)")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -263,7 +271,7 @@ def main(argv=None):
     if distributed:
         dist.all_reduce(rate, op=dist.ReduceOp.SUM)
     if rank == 0:
-        assemble_index(files, allv, bit_dir, index_dir, ccfg.embed_dim)
+        assemble_index(files, allv, bit_dir, index_dir, ccfg.embed_dim, write_codes=args.write_codes)
         print(json.dumps({"cli_images_per_s": round(float(rate.item()), 2), "images": len(files), "n_gpus": world,
                           "collectives": (dist.get_backend() if distributed else None),
                           "seconds_rank0": round(dt, 3), "batch_size": args.batch_size,

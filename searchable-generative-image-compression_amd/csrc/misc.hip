@@ -807,8 +807,9 @@ static int clip_ragged_image(const int32_t *q, int S, long long *off, ClipRagged
   return 0;
 }
 
-__global__ void clip_ragged_coeffs_kernel(ClipRaggedChunk ch, uint8_t *__restrict__ work) {
-  const ClipRaggedImg &m = ch.img[blockIdx.y];
+template <class Chunk>   // ClipRaggedChunk, or ClipU8Chunk of the u8-canvas path below: g[] and off[0..3] mean the same in both
+__global__ void clip_ragged_coeffs_kernel(Chunk ch, uint8_t *__restrict__ work) {
+  const auto &m = ch.img[blockIdx.y];
   const int H = m.g[0], W = m.g[1], OH = m.g[2], OW = m.g[3];
   int *bh = reinterpret_cast<int *>(work + m.off[0]), *kh = reinterpret_cast<int *>(work + m.off[1]);
   int *bv = reinterpret_cast<int *>(work + m.off[2]), *kv = reinterpret_cast<int *>(work + m.off[3]);
@@ -929,6 +930,203 @@ extern "C" int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, lo
     clip_ragged_resize_v_norm_kernel<<<dim3(gx(3L * S * S), n), 256, 0, st>>>(ch, S, d_work, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
                                                                             std3[2], d_out + (long)c0 * 3 * S * S);
     rc = sgic::check_launch("clip_ragged_resize_v_norm_kernel");
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// CLIP preprocessing straight from the u8 canvas of the ingest (B, Hc, Wc, 3 interleaved RGB; image b is the top-left H_b x W_b
+// region, the rest of the canvas holds stale bytes and is never read): the decoded bytes are resampled AS THEY ARE -- what
+// `preprocess(Image.open(path))` does in the reference's build-images.  No fp32 image, no planar u8 copy; tables and pixel
+// arithmetic are those of the ragged path above.  The horizontal pass covers the S columns the crop keeps and only the source rows
+// the vertical pass reads, bounds_v[top].xmin up to bounds_v[top + S - 1].xmin + count (both bounds are non-decreasing in the output
+// index): the intermediate is 3 x rows x S u8.  A workgroup takes one source row: it loads the segment of the row its output
+// columns read with 16-byte loads, de-interleaves it into three planes in LDS, and every lane resamples one output column of the
+// three channels from there.
+// ------------------------------------------------------------------------------------------------
+#define U8C_TILE_PX 4096   // source pixels of a row held in LDS at a time (three planes: 12 KiB)
+#define U8C_THREADS 256
+
+struct ClipU8Img {
+  int g[8];            // H, W, OH, OW, top, left, ksize_h, ksize_v
+  int rows_cap;        // rows of the intermediate: an upper bound of the row window, from the geometry alone
+  int tile;            // output columns a workgroup resamples from one LDS fill (<= U8C_THREADS)
+  long long off[5];    // workspace byte offsets: bounds_h, kk_h, bounds_v, kk_v, the horizontal-pass output (3 x rows_cap x S)
+};
+
+struct ClipU8Chunk {
+  ClipU8Img img[RAGGED_CHUNK];
+};
+
+// the window of n consecutive outputs of an in_size -> out_size resample spans fewer than (n - 1) * scale + 2 * support + 1 inputs
+// (first index > centre_0 - support - 0.5, end <= centre_{n-1} + support + 0.5; clamping to [0, in_size] only shrinks it)
+static double u8c_span_bound(int in_size, int out_size, int n) {
+  const double scale = (double)in_size / (double)out_size;
+  return (double)(n - 1) * scale + 4.0 * (scale > 1.0 ? scale : 1.0) + 1.0;
+}
+
+static int clip_u8canvas_image(const int32_t *q, int S, long long *off, ClipU8Img *m) {
+  const int H = q[0], W = q[1], OH = q[2], OW = q[3], top = q[4], left = q[5];
+  SGIC_REQUIRE(H > 0 && W > 0 && OH > 0 && OW > 0 && H <= 65535 && W <= 65535 && OH <= 65535 && OW <= 65535, "image geometry");
+  SGIC_REQUIRE(top >= 0 && left >= 0 && top + S <= OH && left + S <= OW, "crop window");
+  m->g[0] = H, m->g[1] = W, m->g[2] = OH, m->g[3] = OW, m->g[4] = top, m->g[5] = left;
+  m->g[6] = pil_ksize(W, OW), m->g[7] = pil_ksize(H, OH);
+  m->rows_cap = (int)std::min((double)H, std::floor(u8c_span_bound(H, OH, S)) + 2.0);
+  // the largest tile whose window is sure to fit one LDS fill; a window that does not fit (one output with more than U8C_TILE_PX
+  // taps) is resampled in several fills
+  const double per = (double)W / (double)OW, room = (double)U8C_TILE_PX - u8c_span_bound(W, OW, 1);
+  m->tile = room > 0.0 ? (int)std::min((double)std::min(S, U8C_THREADS), std::floor(room / per) + 1.0) : 1;
+  const long long size[5] = {8LL * OW, 4LL * OW * m->g[6], 8LL * OH, 4LL * OH * m->g[7], 3LL * m->rows_cap * S};
+  for (int k = 0; k < 5; k++) {
+    m->off[k] = *off;
+    *off += (size[k] + 15) & ~15LL;
+  }
+  return 0;
+}
+
+// nbytes of interleaved RGB starting at a pixel boundary -> px[c][i]: 16-byte loads over the aligned middle, single bytes for the
+// up to 15 bytes on either side, so that no byte outside [p, p + nbytes) is touched
+__device__ __forceinline__ void u8c_stage_row(const uint8_t *__restrict__ p, int nbytes, uint8_t (*px)[U8C_TILE_PX]) {
+  const int head = min(nbytes, (int)((16u - (unsigned)((uintptr_t)p & 15)) & 15u));
+  const int nvec = (nbytes - head) >> 4;
+  const int tail0 = head + (nvec << 4);
+  for (int i = threadIdx.x; i < head + nbytes - tail0; i += U8C_THREADS) {
+    const int o = i < head ? i : tail0 + (i - head);
+    px[o % 3][o / 3] = p[o];
+  }
+  for (int v = threadIdx.x; v < nvec; v += U8C_THREADS) {
+    const int o = head + (v << 4);
+    const uint4 q = *reinterpret_cast<const uint4 *>(p + o);
+    const unsigned w4[4] = {q.x, q.y, q.z, q.w};
+    int pix = o / 3, c = o - 3 * pix;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      px[c][pix] = (uint8_t)(w4[j >> 2] >> (8 * (j & 3)));
+      if (++c == 3) c = 0, pix++;
+    }
+  }
+}
+
+__global__ __launch_bounds__(U8C_THREADS) void clip_u8canvas_resize_h_kernel(const uint8_t *__restrict__ canvas, long img_stride, int Wc,
+                                                                             ClipU8Chunk ch, int S, uint8_t *__restrict__ work) {
+  __shared__ __attribute__((aligned(16))) uint8_t px[3][U8C_TILE_PX];
+  const ClipU8Img &m = ch.img[blockIdx.y];
+  const int W = m.g[1], top = m.g[4], left = m.g[5], ksize = m.g[6], tile = m.tile, rows_cap = m.rows_cap;
+  const int *bh = reinterpret_cast<const int *>(work + m.off[0]), *kh = reinterpret_cast<const int *>(work + m.off[1]);
+  const int *bv = reinterpret_cast<const int *>(work + m.off[2]);
+  const int r0 = bv[2 * top];
+  const int rows = min(bv[2 * (top + S - 1)] + bv[2 * (top + S - 1) + 1] - r0, rows_cap);
+  uint8_t *out = work + m.off[4];
+  const uint8_t *img = canvas + (long)blockIdx.y * img_stride;
+  const int tid = threadIdx.x;
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const uint8_t *row = img + (long)(r0 + r) * Wc * 3;
+    for (int t0 = 0; t0 < S; t0 += tile) {
+      const int nt = min(tile, S - t0);
+      const int last = left + t0 + nt - 1;
+      const int w0 = bh[2 * (left + t0)], w1 = min(bh[2 * last] + bh[2 * last + 1], W);
+      const bool active = tid < nt;
+      const int ox = left + t0 + (active ? tid : 0);
+      const int xmin = bh[2 * ox], xend = xmin + bh[2 * ox + 1];
+      const int *k = kh + (long)ox * ksize;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      for (int c0 = w0; c0 < w1; c0 += U8C_TILE_PX) {
+        const int n = min(U8C_TILE_PX, w1 - c0);
+        __syncthreads();   // the previous fill has been read
+        u8c_stage_row(row + 3L * c0, 3 * n, px);
+        __syncthreads();
+        if (active) {
+          const int lo = max(xmin, c0), hi = min(xend, c0 + n);
+          for (int x = lo; x < hi; x++) {
+            const int kv = k[x - xmin], i = x - c0;
+            a0 += (int)px[0][i] * kv;
+            a1 += (int)px[1][i] * kv;
+            a2 += (int)px[2][i] * kv;
+          }
+        }
+      }
+      if (active) {
+        a0 >>= 22, a1 >>= 22, a2 >>= 22;
+        uint8_t *o = out + (long)r * S + t0 + tid;
+        o[0] = (uint8_t)(a0 < 0 ? 0 : (a0 > 255 ? 255 : a0));
+        o[(long)rows_cap * S] = (uint8_t)(a1 < 0 ? 0 : (a1 > 255 ? 255 : a1));
+        o[2L * rows_cap * S] = (uint8_t)(a2 < 0 ? 0 : (a2 > 255 ? 255 : a2));
+      }
+    }
+  }
+}
+
+__global__ void clip_u8canvas_resize_v_norm_kernel(ClipU8Chunk ch, int S, const uint8_t *__restrict__ work, float m0, float m1, float m2,
+                                                   float s0, float s1, float s2, float *__restrict__ out) {
+  const ClipU8Img &m = ch.img[blockIdx.y];
+  const int top = m.g[4], ksize = m.g[7], rows_cap = m.rows_cap;
+  const int *bounds = reinterpret_cast<const int *>(work + m.off[2]), *kk = reinterpret_cast<const int *>(work + m.off[3]);
+  const uint8_t *in = work + m.off[4];
+  const int r0 = bounds[2 * top];
+  float *dst = out + (long)blockIdx.y * 3 * S * S;
+  const long total = 3L * S * S;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % S);
+    const long t = i / S;
+    const int yy = (int)(t % S);
+    const int c = (int)(t / S);
+    const int oy = yy + top;
+    const int ymin = bounds[2 * oy] - r0, cnt = min(bounds[2 * oy + 1], rows_cap - ymin);
+    const int *k = kk + (long)oy * ksize;
+    const uint8_t *p = in + ((long)c * rows_cap + ymin) * S + xx;
+    int ss = 1 << 21;
+    for (int y = 0; y < cnt; y++) ss += (int)p[(long)y * S] * k[y];
+    ss >>= 22;
+    const int u = ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+    dst[i] = ((float)u / 255.0f - mean) / sd;
+  }
+}
+
+extern "C" int sgic_clip_preprocess_u8canvas_workspace(int B, const int32_t *h_geo, int S, size_t *bytes) {
+  SGIC_REQUIRE(B > 0 && h_geo && S > 0 && bytes, "args");
+  long long off = 0;
+  ClipU8Img m;
+  for (int b = 0; b < B; b++) {
+    const int rc = clip_u8canvas_image(h_geo + 6 * b, S, &off, &m);
+    if (rc) return rc;
+  }
+  *bytes = (size_t)off;
+  return 0;
+}
+
+extern "C" int sgic_clip_preprocess_u8canvas(const uint8_t *d_canvas, int Hc, int Wc, int B, const int32_t *h_geo, int S,
+                                             const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
+                                             sgic_stream_t stream) {
+  SGIC_REQUIRE(d_canvas && h_geo && d_work && d_out && mean3 && std3 && B > 0 && S > 0 && Hc > 0 && Wc > 0, "args");
+  SGIC_REQUIRE((((uintptr_t)d_work) & 15) == 0, "workspace alignment");
+  hipStream_t st = to_stream(stream);
+  const long img_stride = 3L * Hc * Wc;
+  long long off = 0;
+  for (int c0 = 0; c0 < B; c0 += RAGGED_CHUNK) {
+    const int n = std::min(RAGGED_CHUNK, B - c0);
+    ClipU8Chunk ch{};
+    long mx_tab = 0, mx_rows = 0;
+    for (int j = 0; j < n; j++) {
+      ClipU8Img &m = ch.img[j];
+      const int rc = clip_u8canvas_image(h_geo + 6 * (c0 + j), S, &off, &m);
+      if (rc) return rc;
+      SGIC_REQUIRE((size_t)off <= work_bytes, "workspace too small (sgic_clip_preprocess_u8canvas_workspace)");
+      SGIC_REQUIRE(m.g[0] <= Hc && m.g[1] <= Wc, "extent outside the canvas");
+      mx_tab = std::max(mx_tab, (long)m.g[2] + m.g[3]);
+      mx_rows = std::max(mx_rows, (long)m.rows_cap);
+    }
+    clip_ragged_coeffs_kernel<<<dim3(cdiv((size_t)mx_tab, 64), n), 64, 0, st>>>(ch, d_work);
+    int rc = sgic::check_launch("clip_ragged_coeffs_kernel");
+    if (rc) return rc;
+    clip_u8canvas_resize_h_kernel<<<dim3((unsigned)std::min(mx_rows, 2048L), n), U8C_THREADS, 0, st>>>(d_canvas + (long)c0 * img_stride,
+                                                                                                     img_stride, Wc, ch, S, d_work);
+    rc = sgic::check_launch("clip_u8canvas_resize_h_kernel");
+    if (rc) return rc;
+    clip_u8canvas_resize_v_norm_kernel<<<dim3((unsigned)std::min((3L * S * S + 255) / 256, 1024L), n), 256, 0, st>>>(
+        ch, S, d_work, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], d_out + (long)c0 * 3 * S * S);
+    rc = sgic::check_launch("clip_u8canvas_resize_v_norm_kernel");
     if (rc) return rc;
   }
   return 0;

@@ -976,6 +976,22 @@ def u8canvas_to_f32chw_pad(x_u8, hw, OH, OW):
     return out
 
 
+def clip_preprocess_u8canvas(x_u8, geo, S, mean, std):
+    """(B,Hc,Wc,3) u8 canvas on the device, image b at its top left with geo[b] = (H, W, OH, OW, top, left) (clip.resize_geometry) ->
+    (B,3,S,S) fp32: Pillow's bicubic resize of the bytes as they are, centre crop, / 255, (v - mean) / std, bit for bit.  mean, std:
+    float32 numpy arrays of three"""
+    assert x_u8.dim() == 4 and x_u8.shape[3] == 3 and x_u8.dtype == torch.uint8 and x_u8.is_contiguous() and x_u8.is_cuda
+    B, Hc, Wc, _ = x_u8.shape
+    geo = np.ascontiguousarray(geo, dtype=np.int32).reshape(B, 6)
+    mean, std = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (mean, std))
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_clip_preprocess_u8canvas_workspace", B, geo, int(S), ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=x_u8.device)
+    out = torch.empty(B, 3, int(S), int(S), dtype=torch.float32, device=x_u8.device)
+    call("sgic_clip_preprocess_u8canvas", _p(x_u8), Hc, Wc, B, geo, int(S), mean, std, _p(work), ctypes.c_size_t(nbytes.value), _p(out))
+    return out
+
+
 def clip_resize_coeffs(in_size, out_size, device):
     """Pillow's bicubic tables of an in_size -> out_size resample built on the device (what clip.pil_coeffs computes on the host)
     -> (bounds int32 (out,2), kk int32 (out,ksize), ksize)"""

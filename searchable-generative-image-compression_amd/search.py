@@ -8,7 +8,10 @@ database^T) + a top-k kernel on the GPU.
 `build` makes an index directory from a directory of containers (the reference's `build.py build`); besides the fp32 index it
 writes the u8 codes themselves (codes.npy), which `--codes` (on all three query commands) and `neighbours` search with the fused
 i8 kernels (csrc/search.hip): integer inner products, no fp32 database and no score matrix on the device.  A u8 query code is used
-as it is; an fp32 text / image vector is taken to 2^-22 fixed point and searched as three i8 digit planes."""
+as it is; an fp32 text / image vector is taken to 2^-22 fixed point and searched as three i8 digit planes.
+`build-images` (the reference's `build.py build-images`) indexes a folder of ordinary images with the CLIP tower alone: no codec, no
+container.  The decoded bytes go to the tower as they are (clip.py preprocess_u8), and the index directory carries the same files
+as `build`, the tower's own u8 codes included."""
 import argparse
 import json
 import os
@@ -269,6 +272,169 @@ def build_index(c2df_dir, index_dir, log=print):
     return ci
 
 
+IMAGE_EXTS = ("jpg", "jpeg", "png", "webp", "bmp")     # the reference's default --exts (build.py:265)
+_ONE_TOWER = "ViT-B-32"
+
+
+def list_images(image_dir, exts=None):
+    """every file under image_dir (recursive) with one of the extensions, case-insensitive (build.py:173-181), SORTED: the
+    reference keeps rglob's order, which is the file system's"""
+    want = {"." + e.strip().lower().lstrip(".") for e in (exts or IMAGE_EXTS) if e.strip()}
+    return sorted(p for p in Path(image_dir).rglob("*") if p.is_file() and p.suffix.lower() in want)
+
+
+def select_images(files, limit=None, desired=None, random_pick=False, seed=None):
+    """build.py:218-224: target = desired if desired and desired > 0 else limit; with 0 < target <= len(files) a
+    random.Random(seed).sample of that many when random_pick, else the first target files; otherwise all of them"""
+    import random
+    files = list(files)
+    target = desired if (desired is not None and desired > 0) else limit
+    if target is not None and 0 < target <= len(files):
+        return random.Random(seed).sample(files, target) if random_pick else files[:target]
+    return files
+
+
+def build_index_from_images(image_dir, index_dir, clip_ckpt=None, small=False, batch_size=32, exts=None, limit=None, random_pick=False,
+                            seed=None, desired=None, device="cuda:0", log=print):
+    """`build-images`: a folder of ordinary images -> index directory, with the CLIP tower alone (no Codec is built, no codec weights are
+    loaded).  Files are listed sorted and selected as the reference does (select_images); a selected file whose size header cannot be
+    read is skipped with a line, one whose pixels fail to decode later ends the run with an error naming it (the reference skips
+    both; compress.py here does the same as this).  Batches come from the compress driver's ingest (ShardLoader, GPU JPEG decode, one
+    batch ahead); the u8 canvas goes straight to ClipCodec.u8_to_codes.  Writes what `build` writes: faiss.index + paths.json +
+    meta.json, index.faiss + ids.txt, and codes.npy -- the tower's own u8 output, row for row.  -> the record that is also printed."""
+    import time
+    from . import ops
+    from . import weights as W
+    from .codec import ClipCodec
+    from .compress import load_state
+    from .config import CLIP_B32, CLIP_TINY
+    from .faiss_io import write_index_flat_ip
+    from .ingest import DeviceIngest, ShardLoader, image_size
+    t_start = time.perf_counter()
+    image_dir, root = Path(image_dir), Path(index_dir)
+    listed = list_images(image_dir, exts)
+    if not listed:
+        raise RuntimeError(f"There is no image in {image_dir}")
+    picked = select_images(listed, limit, desired, random_pick, seed)
+    t_hdr = time.perf_counter()
+
+    def header(p):
+        try:
+            image_size(p)
+        except Exception as e:   # noqa: BLE001 -- not an image, truncated header, ...
+            return str(e)
+        return None
+
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=min(16, max(2, os.cpu_count() or 4))) as pool:      # the pool size of ShardLoader's own pass
+        why = list(pool.map(header, picked))
+    for p, e in zip(picked, why):
+        if e is not None:
+            log(f"[SKIP] {p.name}: {e}")
+    files = [str(p) for p, e in zip(picked, why) if e is None]
+    header_ms = (time.perf_counter() - t_hdr) * 1e3
+    if not files:
+        raise RuntimeError(f"no readable image among the {len(listed)} files of {image_dir}")
+    log(f"[INFO] Using {len(files)} images to build the index")
+
+    dev = torch.device(device)
+    torch.cuda.set_device(dev)
+    ccfg = CLIP_TINY if small else CLIP_B32
+    csd = load_state(clip_ckpt, W.clip_spec, ccfg, 4321)
+    if clip_ckpt and not any(k.startswith("clip.") for k in csd):
+        csd = {f"clip.{k}": v for k, v in csd.items()}
+    clipc = ClipCodec(csd, ccfg, dev)
+    D, n = ccfg.embed_dim, len(files)
+    unit, codes = np.zeros((n, D), dtype=np.float32), np.zeros((n, D), dtype=np.uint8)
+    ingest = DeviceIngest(dev)
+    host_ms, gpu_evs = {}, []
+    # pinned once: pinning is a device-synchronising allocation (a batch never holds more than batch_size images, ingest.plan_batches)
+    pins = [(torch.empty(max(1, batch_size), D, dtype=torch.float32).pin_memory(), torch.empty(max(1, batch_size), D, dtype=torch.uint8).pin_memory())
+            for _ in range(3)]
+
+    def collect(job):
+        """host side of one batch: its rows, once the device-to-host copies have landed"""
+        batch, copied, pu, pq, ev = job
+        copied.synchronize()
+        if batch.jpeg is not None:            # decoded on the GPU: a corrupt entropy-coded segment shows up as an error code
+            err = batch.jpeg.err_host.numpy()[:len(batch.paths)]
+            if err.any():
+                raise RuntimeError(f"corrupt JPEG data in {[p for p, c in zip(batch.paths, err) if c]} (codes {err[err != 0].tolist()})")
+        ev.synchronize()
+        batch.release()
+        unit[batch.indices] = pu.numpy()          # rows land at the files' positions, whatever the batch plan was
+        codes[batch.indices] = pq.numpy()
+
+    t_loop = time.perf_counter()      # the clock of compress.py's own rate: the loader's header pass and plan, every batch, the last sync
+    loader = ShardLoader(files, batch_size, pad_to=256)
+    try:
+        pending = None
+        it = iter(loader)
+        batch = next(it, None)
+        tok = ingest.start(batch) if batch is not None else None
+        while batch is not None:
+            t_a = time.perf_counter()
+            nxt = next(it, None)
+            t_b = time.perf_counter()
+            ntok = ingest.start(nxt) if nxt is not None else None      # one batch ahead, enqueued before this batch's kernels
+            d, copied = tok
+            cur = torch.cuda.current_stream()
+            cur.wait_event(copied)
+            d.record_stream(cur)
+            t_c = time.perf_counter()
+            ev0 = torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            u, q = clipc.u8_to_codes(d, batch.hw)
+            ev1 = torch.cuda.Event(enable_timing=True)
+            ev1.record()
+            gpu_evs.append((ev0, ev1))
+            slot = pins[len(gpu_evs) % len(pins)]       # two batches are in flight at most: this one and `pending`
+            pu, pq = slot[0][:u.shape[0]], slot[1][:q.shape[0]]
+            pu.copy_(u, non_blocking=True)
+            pq.copy_(q, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            t_d = time.perf_counter()
+            if pending is not None:
+                collect(pending)
+            t_e = time.perf_counter()
+            for k, v in (("wait_loader", t_b - t_a), ("ingest", t_c - t_b), ("submit", t_d - t_c), ("collect_incl_gpu_wait", t_e - t_d)):
+                host_ms[k] = host_ms.get(k, 0.0) + v * 1e3
+            pending = (batch, copied, pu, pq, ev)
+            batch, tok = nxt, ntok
+        if pending is not None:
+            collect(pending)
+    finally:
+        loader.close()
+    torch.cuda.synchronize()
+    loop_s = time.perf_counter() - t_loop
+    nb = max(1, len(gpu_evs))
+    gpu_ms = sum(a.elapsed_time(b) for a, b in gpu_evs[1:]) / (len(gpu_evs) - 1) if len(gpu_evs) > 1 else None   # first batch: autotune
+
+    ids = list(files)
+    root.mkdir(parents=True, exist_ok=True)
+    write_index_flat_ip(str(root / "faiss.index"), unit)
+    write_index_flat_ip(str(root / "index.faiss"), unit)
+    (root / "paths.json").write_text(json.dumps(ids, ensure_ascii=False, indent=2), encoding="utf-8")
+    (root / "ids.txt").write_text("\n".join(ids), encoding="utf-8")
+    (root / "meta.json").write_text(json.dumps({"dim": D, "model_id": clipc.model_name}, ensure_ascii=False, indent=2), encoding="utf-8")
+    np.save(root / "codes.npy", codes)
+    ops.save_tile_cache()
+    dt = time.perf_counter() - t_start
+    rec = {"cli_images_per_s": round(n / dt, 2) if dt > 0 else 0.0, "images": n, "seconds": round(dt, 3), "batch_size": batch_size,
+           "loop_images_per_s": round(n / loop_s, 2) if loop_s > 0 else 0.0, "loop_seconds": round(loop_s, 3),
+           "skip_header_pass_ms": round(header_ms, 2), "weights_and_tower_setup_ms": round((t_loop - t_hdr) * 1e3 - header_ms, 2),
+           "batches": len(gpu_evs), "host_ms_per_batch": {k: round(v / nb, 2) for k, v in host_ms.items()},
+           "gpu_ms_per_batch": None if gpu_ms is None else round(gpu_ms, 3),
+           "gpu_jpeg_batches": loader.gpu_batches, "gpu_scan_jpeg_batches": loader.gpu_scan_batches, "host_decoded_batches": loader.host_batches,
+           "note": "cli_images_per_s: files -> index, with listing, the skip pass over the headers, weights and the index files; "
+                   "loop_images_per_s: the loader's header pass and plan, JPEG/PNG decode, H2D, CLIP preprocessing + tower, D2H (the clock of "
+                   "compress.py's rate)"}
+    log(f"[OK] index of {n} images, dim {D}, in {root}")
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def _query_codes(index_dir, c2df, topk):
     """`query-c2df --codes`: a file -> result list; a directory -> {path: result list}, all queries in one fused call"""
     ci = CodeIndex.load(index_dir)
@@ -287,12 +453,13 @@ def _query_vector(args):
         return decode_clip_from_c2df(args.c2df)[0][None, :]
     from . import weights as W
     from .compress import load_state
-    from .config import CLIP_B32
+    from .config import CLIP_B32, CLIP_TINY
+    ccfg = CLIP_TINY if getattr(args, "small", False) else CLIP_B32
     if args.cmd == "query-image":
         from .codec import ClipCodec
         from .compress import load_image
-        csd = load_state(args.clip_ckpt, W.clip_spec, CLIP_B32, 4321)
-        return ClipCodec(csd, CLIP_B32, "cuda:0").image_to_unit_vec(load_image(args.image))[None, :]
+        csd = load_state(args.clip_ckpt, W.clip_spec, ccfg, 4321)
+        return ClipCodec(csd, ccfg, "cuda:0").image_to_unit_vec(load_image(args.image))[None, :]
     from .clip import ClipTextHIP
     toks = tokenize(args.text, CLIP_B32.ctx, args.token_ids)
     tsd = load_state(args.clip_ckpt, W.clip_text_spec, CLIP_B32, 4321)
@@ -300,7 +467,7 @@ def _query_vector(args):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / neighbours")
+    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours")
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name, arg in (("query-text", "--text"), ("query-image", "--image"), ("query-c2df", "--c2df")):
         p = sub.add_parser(name)
@@ -308,6 +475,8 @@ def main(argv=None):
         p.add_argument(arg, type=str, required=True)
         p.add_argument("--topk", type=int, default=10)
         p.add_argument("--clip_ckpt", type=str, default=None)
+        if name == "query-image":
+            p.add_argument("--small", action="store_true", help="TINY test tower (an index built with --small)")
         if name == "query-text":
             p.add_argument("--token_ids", type=str, default=None, help="comma-separated BPE ids (offline tokenizer bypass)")
         if name == "query-c2df":
@@ -319,6 +488,23 @@ def main(argv=None):
     p = sub.add_parser("build", help="index directory from a directory of .c2df containers")
     p.add_argument("--c2df_dir", type=Path, required=True)
     p.add_argument("--index_dir", type=Path, required=True)
+    p = sub.add_parser("build-images", help="index directory from a folder of images, with the CLIP tower alone")
+    p.add_argument("--image_dir", type=Path, required=True)
+    p.add_argument("--index_dir", type=Path, required=True)
+    p.add_argument("--model_id", type=str, default=None, help=f"only {_ONE_TOWER}[:pretrained] exists here")
+    p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--exts", type=str, default=",".join(IMAGE_EXTS))
+    p.add_argument("--limit", type=int, default=None, help="use only N images (ignored if --desired is also given)")
+    p.add_argument("--desired", type=int, default=None, help="target number of images")
+    p.add_argument("--random", action="store_true", help="random sample instead of the first N (needs --limit or --desired)")
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--clip_ckpt", type=str, default=None)
+    p.add_argument("--small", action="store_true", help="TINY test tower")
+    # the reference's downloader flags parse, and are refused: nothing here opens a socket
+    p.add_argument("--auto_download", action="store_true", help="refused: there is no downloader")
+    p.add_argument("--download_dir", type=Path, default=None, help="refused: there is no downloader")
+    p.add_argument("--download_size", type=str, default=None, help="refused: there is no downloader")
+    p.add_argument("--timeout", type=int, default=None, help="refused: there is no downloader")
     p = sub.add_parser("neighbours", help="k nearest neighbours of every vector of the code index, one JSON line each")
     p.add_argument("--index_dir", type=Path, required=True)
     p.add_argument("--topk", type=int, default=10)
@@ -326,6 +512,17 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.cmd == "build":
         build_index(args.c2df_dir, args.index_dir)
+        return 0
+    if args.cmd == "build-images":
+        used = [f for f in ("auto_download", "download_dir", "download_size", "timeout") if getattr(args, f) not in (None, False)]
+        if used:
+            ap.error("build-images: " + ", ".join("--" + f for f in used) + ": there is no downloader here, nothing in this tool "
+                     "reaches the network; put the images into --image_dir yourself")
+        if args.model_id is not None and args.model_id.split(":")[0] != _ONE_TOWER:
+            ap.error(f"build-images: --model_id {args.model_id}: the one CLIP tower that exists here is {_ONE_TOWER}[:pretrained]")
+        build_index_from_images(args.image_dir, args.index_dir, clip_ckpt=args.clip_ckpt, small=args.small, batch_size=args.batch_size,
+                                exts=[e for e in args.exts.split(",") if e.strip()], limit=args.limit, random_pick=args.random,
+                                seed=args.seed, desired=args.desired)
         return 0
     if args.cmd == "neighbours":
         ci = CodeIndex.load(args.index_dir)
