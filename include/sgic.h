@@ -174,6 +174,19 @@ int sgic_attention_f32(const float *d_q, int ldq, const float *d_k, int ldk, con
                        float *d_out, int ldo, int L, int nseq, int nheads, const int32_t *d_rowmap,
                        const float *d_bias, const int32_t *d_biasvar, float scale, const sgic_launch_opts *opts,
                        sgic_stream_t stream);
+/* The same attention for the query tokens q_tok0 .. q_tok0 + Lq - 1 of every sequence only (a last layer whose other rows nobody
+ * reads).  K / V keep the full row space (row s*L + t); query token t lives at row s*Lq + (t - q_tok0) of d_q and of d_out.
+ * q_tok0 % 32 == 0, and the window ends at L or on a multiple of 32: the kernel works on 32-row query blocks (plus the ragged
+ * rows of L % 32 in {1, 2}), and exactly the blocks inside the window run, each as in the full launch -- every output row is
+ * bitwise what sgic_attention_f32 writes for that token.  d_rowmap must be NULL. */
+int sgic_attention_window_f32(const float *d_q, int ldq, const float *d_k, int ldk, const float *d_v, int ldv,
+                              float *d_out, int ldo, int L, int nseq, int nheads, const int32_t *d_rowmap,
+                              const float *d_bias, const int32_t *d_biasvar, float scale, int q_tok0, int Lq,
+                              const sgic_launch_opts *opts, sgic_stream_t stream);
+/* nblocks runs of block_elems contiguous floats, run i copied from d_src + i*src_stride to d_dst + i*dst_stride (element
+ * strides): an exact device-to-device copy of the rows that sgic_attention_window_f32's caller keeps. */
+int sgic_copy_blocks_f32(const float *d_src, long src_stride, float *d_dst, long dst_stride, long block_elems, int nblocks,
+                         sgic_stream_t stream);
 
 /* im2col of non-overlapping PxP patches of an NCHW image with x*mul+add fused; patch rows in plain
  * (b,gy,gx) order or 16x16-tile-major (tile16) order (codec_sq_fixbpp.py:855,119; titok/blocks.py:98-100). */
@@ -264,6 +277,11 @@ int sgic_attention_split3_f32(const float *d_q, int ldq, const float *d_k, int l
                               uint16_t *d_out_planes, long rows, int L, int nseq, int nheads, const int32_t *d_rowmap,
                               const float *d_bias, const int32_t *d_biasvar, float scale, const sgic_launch_opts *opts,
                               sgic_stream_t stream);
+/* sgic_attention_window_f32 with the planes output of sgic_attention_split3_f32 (rows >= nseq*Lq). */
+int sgic_attention_window_split3_f32(const float *d_q, int ldq, const float *d_k, int ldk, const float *d_v, int ldv,
+                                     uint16_t *d_out_planes, long rows, int L, int nseq, int nheads, const int32_t *d_rowmap,
+                                     const float *d_bias, const int32_t *d_biasvar, float scale, int q_tok0, int Lq,
+                                     const sgic_launch_opts *opts, sgic_stream_t stream);
 /* nn.LayerNorm (call sites as sgic_layernorm_f32) whose only consumer is a split GEMM: the normalised rows are written
  * directly as slice-major bf16x3 planes [3][C / 32][M][32] (dense rows), so no fp32 copy and no separate split pass.  C % 256 == 0, C <= 2048. */
 int sgic_layernorm_split3_f32(const float *d_x, int ldx, int xseg, int xseg_stride, const float *d_gamma,

@@ -10,7 +10,7 @@ import torch
 from . import ops
 from ._lib import call
 from .config import ClipConfig
-from .encoder import RabW, rab_forward
+from .encoder import RabW, rab_forward, rab_forward_last
 
 _PREC = 22  # Pillow PRECISION_BITS = 32 - 8 - 2
 
@@ -65,8 +65,9 @@ def resize_geometry(H, W, S):
 
 
 class ClipHIP:
-    def __init__(self, sd, cfg: ClipConfig, device, p="clip.visual"):
+    def __init__(self, sd, cfg: ClipConfig, device, p="clip.visual", prune_last=True):
         self.cfg, self.device = cfg, device
+        self.prune_last = prune_last   # last layer: compute only the class-token rows (False: the full block, same bits)
         g = lambda k: sd[f"{p}.{k}"].to(device=device, dtype=torch.float32).contiguous()
         Wd = cfg.width
         self.conv_w = sd[f"{p}.conv1.weight"].reshape(Wd, -1).to(device).contiguous()
@@ -153,9 +154,18 @@ class ClipHIP:
         emb = ops.gemm(A, self.conv_w)
         X = ops.assemble_tokens(emb, self.cls, self.pos, None, None, B, g * g, 0, cfg.width)
         ops.layernorm(X, self.lnpre_w, self.lnpre_b, out=X)
-        for w in self.blocks:
-            rab_forward(X, w, L, B, cfg.heads)
-        pooled = ops.layernorm(X, self.lnpost_w, self.lnpost_b, M=B, x_seg=(1, L))
+        if self.prune_last and L > 32:
+            # only the class token is read: the last block runs its attention for query block 0 (tokens 0..31) and everything
+            # after it for token 0 alone.  L <= 32 is one query block already: rab_forward_last reads 32 rows per sequence of X,
+            # which such a sequence does not have, and there is nothing to prune before the out-projection
+            for w in self.blocks[:-1]:
+                rab_forward(X, w, L, B, cfg.heads)
+            pooled = rab_forward_last(X, self.blocks[-1], L, B, cfg.heads, 0, 32, keep=1)
+            ops.layernorm(pooled, self.lnpost_w, self.lnpost_b, out=pooled)
+        else:
+            for w in self.blocks:
+                rab_forward(X, w, L, B, cfg.heads)
+            pooled = ops.layernorm(X, self.lnpost_w, self.lnpost_b, M=B, x_seg=(1, L))
         z = ops.gemm(pooled, self.projT)
         return ops.l2norm_u8(z)
 

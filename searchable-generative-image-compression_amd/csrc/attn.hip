@@ -104,10 +104,18 @@ struct AttnArgs {
   int stagger_cycles, first_round;  // start-up stagger of co-resident workgroups (see attn_f32_kernel), 0 = off
   unsigned short *out_planes;       // optional: the output as slice-major bf16x3 planes [3][nheads*2][rows][32] (operand of the out-projection
   long plane_elems;                 // split GEMM, gemm_split.hip) instead of `out`; rows * nheads * 64
+  // Query window (Lq > 0, rowmap == null): q / out / out_planes hold Lq rows per sequence, query token t at row seq*Lq + (t - q_tok0);
+  // K / V keep the full row space.  Row-block slot i of a unit is row block rb0 + i (nq counts the window's blocks) and the ragged
+  // rows start at token rag_tok0, so every item that runs holds the tokens -- and computes the bits -- it holds in a full launch.
+  int q_tok0, Lq, rb0, rag_tok0;
 };
 
 __device__ __forceinline__ long at_row(const AttnArgs &a, int seq, int tok) {
   return a.rowmap ? (long)a.rowmap[(long)seq * a.L + tok] : (long)seq * a.L + tok;
+}
+// row of a QUERY token in q / out (at_row unless the launch is a query window)
+__device__ __forceinline__ long at_qrow(const AttnArgs &a, int seq, int tok) {
+  return a.Lq ? (long)seq * a.Lq + (tok - a.q_tok0) : at_row(a, seq, tok);
 }
 
 // One ragged query row on the vector pipe: scores for all L keys (lane = key mod 64), softmax across the wave, then
@@ -115,7 +123,7 @@ __device__ __forceinline__ long at_row(const AttnArgs &a, int seq, int tok) {
 // the same unit stream them at the same time); q and p live in a wave-private LDS slice.
 __device__ void attn_ragged_row(const AttnArgs &a, int unit, int tok, float *wl /* AT_RAG_SLICE floats */, int lane) {
   const int head = unit % a.nheads, seq = unit / a.nheads, hc = head * 64;
-  const long q_row = at_row(a, seq, tok);
+  const long q_row = at_qrow(a, seq, tok);
   float *ql = wl, *pl = wl + 64;
   ql[lane] = a.q[q_row * a.ldq + hc + lane] * a.scale;
   const float *bias_row = nullptr;
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(256, (NBUF * UP >= 4 || (S3 && UP > 1)) ? 2 : 3) vo
   int p = blockIdx.x;
   if (p < a.n_rag_wgs) {  // ---- ragged query rows on the VALU ----
     const int it = p * 4 + wave, n_units = a.nseq * a.nheads;
-    if (it < n_units * a.rag) attn_ragged_row(a, it / a.rag, a.nq * 32 + it % a.rag, smem + wave * AT_RAG_SLICE, lane);
+    if (it < n_units * a.rag) attn_ragged_row(a, it / a.rag, a.rag_tok0 + it % a.rag, smem + wave * AT_RAG_SLICE, lane);
     return;
   }
   p -= a.n_rag_wgs;
@@ -223,7 +231,7 @@ __global__ __launch_bounds__(256, (NBUF * UP >= 4 || (S3 && UP > 1)) ? 2 : 3) vo
   const int unit_i = item / a.nqp, rb_i = item - unit_i * a.nqp;
   const bool active = wave < a.ipw && item < a.n_items && rb_i < a.nq;   // wave-uniform (rb_i >= nq: a padding slot of mode 7)
   const int unit = active ? unit_i : uA;
-  const int rb = active ? rb_i : 0;
+  const int rb = a.rb0 + (active ? rb_i : 0);
   const int mine = (UP > 1 && unit != uA) ? 1 : 0;           // which staged region this wave reads
   const int head = unit % a.nheads, seq = unit / a.nheads;
 
@@ -231,7 +239,7 @@ __global__ __launch_bounds__(256, (NBUF * UP >= 4 || (S3 && UP > 1)) ? 2 : 3) vo
   const int q_tok = rb * 32 + lq;  // this lane's query token
   const bool q_ok = active && q_tok < a.L;
   const int q_tok_c = q_tok < a.L ? q_tok : a.L - 1;
-  const long q_row = at_row(a, seq, q_tok_c);
+  const long q_row = at_qrow(a, seq, q_tok_c);
   const int hc = head * 64;
 
   // Q^T fragment.  fp32 MFMA: lane (q, h) holds Q[q][(2c+h)*4 + t], c=0..7, t=0..3  (pairs with the K read below).
@@ -632,13 +640,13 @@ static inline void launch_attn(K kernel, unsigned grid, hipStream_t st, const At
 
 static int attention_any(const float *d_q, int ldq, const float *d_k, int ldk, const float *d_v, int ldv, float *d_out, int ldo,
                          uint16_t *d_planes, long plane_rows, int L, int nseq, int nheads, const int32_t *d_rowmap,
-                         const float *d_bias, const int32_t *d_biasvar, float scale, const sgic_launch_opts *opts,
-                         sgic_stream_t stream) {
+                         const float *d_bias, const int32_t *d_biasvar, float scale, int q_tok0, int Lq,
+                         const sgic_launch_opts *opts, sgic_stream_t stream) {
   SGIC_REQUIRE(d_q && d_k && d_v && (d_out || d_planes) && L > 0 && nseq > 0 && nheads > 0, "args");
   SGIC_REQUIRE((ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 && (ldo & 3) == 0, "row strides must be multiples of 4");
   SGIC_REQUIRE(ldq >= nheads * 64 && ldk >= nheads * 64 && ldv >= nheads * 64 && (d_planes || ldo >= nheads * 64), "head_dim is 64");
   SGIC_REQUIRE((((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) == 0 && ((uintptr_t)d_planes & 7) == 0, "16-byte alignment");
-  SGIC_REQUIRE(!d_planes || plane_rows >= (long)nseq * L, "plane rows");
+  SGIC_REQUIRE(!d_planes || plane_rows >= (long)nseq * (Lq ? Lq : L), "plane rows");
   SGIC_REQUIRE(!d_bias || (L & 3) == 0, "bias needs L % 4 == 0");
   const int mode_all = opts ? opts->attn_mode : 0;
   // attn_mode: low 3 bits: 0 = default (see below); odd = single LDS buffer (two barriers per tile), even = double-buffered LDS
@@ -654,8 +662,21 @@ static int attention_any(const float *d_q, int ldq, const float *d_k, int ldk, c
   const int mode = mode_all & 7;
   const long units = (long)nseq * nheads;
   const int rem = L % 32;
-  const int rag = (rem >= 1 && rem <= 2 && L >= 64 && L <= AT_RAG_MAXL) ? rem : 0;   // ragged query rows -> VALU path
-  const int nq = rag ? L / 32 : (L + 31) / 32;
+  int rag = (rem >= 1 && rem <= 2 && L >= 64 && L <= AT_RAG_MAXL) ? rem : 0;   // ragged query rows -> VALU path
+  int nq = rag ? L / 32 : (L + 31) / 32;
+  // Query window [q_tok0, q_tok0 + Lq): only the row blocks and ragged rows inside it run, each exactly as in the full launch.  The
+  // window starts on a row block and ends on one (or at L): a block's 32 rows share the AT_DEFER decisions, so a block is
+  // computed whole or not at all.
+  int rb0 = 0, rag_tok0 = nq * 32;
+  if (Lq) {
+    const int q_end = q_tok0 + Lq;
+    SGIC_REQUIRE(!d_rowmap, "a query window takes no row map");
+    SGIC_REQUIRE(q_tok0 >= 0 && (q_tok0 & 31) == 0 && Lq > 0 && q_tok0 < nq * 32, "window start: a row block of the sequence");
+    SGIC_REQUIRE(q_end >= L || (q_end & 31) == 0, "window end: a row-block boundary, or the end of the sequence");
+    rb0 = q_tok0 / 32;
+    rag = max(0, min(rag, q_end - rag_tok0));
+    nq = min(nq, (q_end + 31) / 32) - rb0;
+  }
   const bool three = mode == 7 && nq >= 2;
   const int ipw = three ? 3 : (nq == 1 ? 2 : 4);
   const int nqp = three ? (nq + 2) / 3 * 3 : nq;
@@ -668,7 +689,8 @@ static int attention_any(const float *d_q, int ldq, const float *d_k, int ldk, c
   const int n_rag_wgs = (int)((units * rag + 3) / 4);
   const bool up2 = (nqp % ipw) != 0;
   AttnArgs a{d_q, d_k, d_v, d_out, ldq, ldk, ldv, ldo, L, nseq, nheads, d_rowmap, d_bias, d_biasvar, scale,
-             nq, ipw, nqp, (int)n_items, n_wgs, group, rag, n_rag_wgs, 0, 0, d_planes, plane_rows * nheads * 64};
+             nq, ipw, nqp, (int)n_items, n_wgs, group, rag, n_rag_wgs, 0, 0, d_planes, plane_rows * nheads * 64,
+             q_tok0, Lq, rb0, rag_tok0};
   const unsigned grid = (unsigned)(grid_mfma + n_rag_wgs);
   hipStream_t st = to_stream(stream);
   // default (mode 0), from the round-2 measurements (tools/bench_attn.py, tools/micro/attn_stamps.hip): a single K/V buffer
@@ -704,7 +726,17 @@ extern "C" int sgic_attention_f32(const float *d_q, int ldq, const float *d_k, i
                                   sgic_stream_t stream) {
   SGIC_REQUIRE(d_out, "out");
   return attention_any(d_q, ldq, d_k, ldk, d_v, ldv, d_out, ldo, nullptr, 0, L, nseq, nheads, d_rowmap, d_bias, d_biasvar, scale,
-                       opts, stream);
+                       0, 0, opts, stream);
+}
+
+// sgic_attention_f32 for the query tokens q_tok0 .. q_tok0 + Lq - 1 of every sequence only (include/sgic.h)
+extern "C" int sgic_attention_window_f32(const float *d_q, int ldq, const float *d_k, int ldk, const float *d_v, int ldv,
+                                         float *d_out, int ldo, int L, int nseq, int nheads, const int32_t *d_rowmap,
+                                         const float *d_bias, const int32_t *d_biasvar, float scale, int q_tok0, int Lq,
+                                         const sgic_launch_opts *opts, sgic_stream_t stream) {
+  SGIC_REQUIRE(d_out && Lq > 0, "out / window");
+  return attention_any(d_q, ldq, d_k, ldk, d_v, ldv, d_out, ldo, nullptr, 0, L, nseq, nheads, d_rowmap, d_bias, d_biasvar, scale,
+                       q_tok0, Lq, opts, stream);
 }
 
 // the same attention with its output written directly as bf16x3 planes [3][rows][nheads*64] (rows >= nseq*L: the row space
@@ -715,5 +747,14 @@ extern "C" int sgic_attention_split3_f32(const float *d_q, int ldq, const float 
                                          const sgic_launch_opts *opts, sgic_stream_t stream) {
   SGIC_REQUIRE(d_out_planes, "planes");
   return attention_any(d_q, ldq, d_k, ldk, d_v, ldv, nullptr, 0, d_out_planes, rows, L, nseq, nheads, d_rowmap, d_bias, d_biasvar,
-                       scale, opts, stream);
+                       scale, 0, 0, opts, stream);
+}
+
+extern "C" int sgic_attention_window_split3_f32(const float *d_q, int ldq, const float *d_k, int ldk, const float *d_v, int ldv,
+                                                uint16_t *d_out_planes, long rows, int L, int nseq, int nheads,
+                                                const int32_t *d_rowmap, const float *d_bias, const int32_t *d_biasvar, float scale,
+                                                int q_tok0, int Lq, const sgic_launch_opts *opts, sgic_stream_t stream) {
+  SGIC_REQUIRE(d_out_planes && Lq > 0, "planes / window");
+  return attention_any(d_q, ldq, d_k, ldk, d_v, ldv, nullptr, 0, d_out_planes, rows, L, nseq, nheads, d_rowmap, d_bias, d_biasvar,
+                       scale, q_tok0, Lq, opts, stream);
 }

@@ -339,6 +339,17 @@ extern "C" int sgic_fake2d_transpose(const float *d_in, long in_seq_stride, floa
   return sgic::check_launch("fake2d_transpose_kernel");
 }
 
+// nblocks runs of block_elems contiguous floats, run i from d_src + i*src_stride to d_dst + i*dst_stride: an exact strided
+// device copy (the token rows a pruned last block keeps, out of every sequence of the residual stream).
+extern "C" int sgic_copy_blocks_f32(const float *d_src, long src_stride, float *d_dst, long dst_stride, long block_elems,
+                                    int nblocks, sgic_stream_t stream) {
+  SGIC_REQUIRE(d_src && d_dst && block_elems > 0 && nblocks > 0, "args");
+  SGIC_REQUIRE(src_stride >= block_elems && dst_stride >= block_elems, "strides");
+  SGIC_HIP(hipMemcpy2DAsync(d_dst, (size_t)dst_stride * 4, d_src, (size_t)src_stride * 4, (size_t)block_elems * 4, (size_t)nblocks,
+                            hipMemcpyDeviceToDevice, to_stream(stream)));
+  return SGIC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // TiTok VQ nearest code with l2-normalised tokens and codebook (titok/quantizer.py:46-61):
 // d = |z|^2 + |e|^2 - 2 z.e ; argmin (first minimum).  Codes strided over lanes.

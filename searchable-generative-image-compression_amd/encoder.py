@@ -49,6 +49,31 @@ def rab_forward(X, w: RabW, L, nseq, heads, bias=None):
     return X
 
 
+def rab_forward_last(X, w: RabW, L, nseq, heads, tok0, Lq, keep=None, bias=None):
+    """rab_forward for a block whose output is read only at tokens tok0 .. tok0+keep-1 of every sequence (keep defaults to Lq):
+    X [(nseq*L), D] is left untouched and the block's output for those tokens comes back dense, [(nseq*keep), D], bitwise what
+    rab_forward leaves in those rows.  Only K and V need every token; Q and the attention run for the window tok0 .. tok0+Lq-1
+    (whole 32-row query blocks, see ops.attention), everything after the attention for the kept rows."""
+    D = X.shape[1]
+    keep = Lq if keep is None else keep
+    assert 0 < keep <= Lq and tok0 + Lq <= L
+    h = ops.layernorm(X, w.ln1w, w.ln1b, to_gemm=True)
+    kv = ops.gemm(h, w.inw[D:], w.inb[D:])                               # K | V of every token
+    hq = ops.layernorm(X[tok0:], w.ln1w, w.ln1b, M=nseq * Lq, x_seg=(Lq, L), to_gemm=True)
+    q = ops.gemm(hq, w.inw[:D], w.inb[:D])                               # Q of the window, dense [(nseq*Lq), D]
+    Xq = ops.copy_row_blocks(X[tok0:], keep, L, nseq)                    # the residual stream of the kept rows
+    if keep == Lq:
+        att = ops.attention(q, kv[:, 0:D], kv[:, D:2 * D], hq, L, nseq, heads, bias=bias, to_gemm=True, window=(tok0, Lq))
+        ops.gemm(att, w.ow, w.ob, residual=Xq, out=Xq)
+    else:   # the out-projection gathers the kept rows through its row map, which reads fp32
+        att = ops.attention(q, kv[:, 0:D], kv[:, D:2 * D], None, L, nseq, heads, bias=bias, window=(tok0, Lq))
+        ops.gemm(att, w.ow, w.ob, residual=Xq, out=Xq, M=nseq * keep, a_seg=(keep, Lq))
+    h = ops.layernorm(Xq, w.ln2w, w.ln2b, to_gemm=True)
+    f = ops.gemm(h, w.fcw, w.fcb, act=ops.ACT_GELU, to_gemm=True)
+    ops.gemm(f, w.pjw, w.pjb, residual=Xq, out=Xq)
+    return Xq
+
+
 def rel_indices(win):
     idx = torch.tensor([[x, y] for x in range(win) for y in range(win)])
     return idx[None, :, :] - idx[:, None, :] + win - 1
@@ -178,8 +203,9 @@ def cross_forward(Fm, X, w: CrossW, N, Lt, P2):
 
 
 class HybridEncoderHIP:
-    def __init__(self, sd, cfg: CodecConfig, device, p="hybrid_codec.encoder"):
+    def __init__(self, sd, cfg: CodecConfig, device, p="hybrid_codec.encoder", prune_last=True):
         self.cfg, self.device = cfg, device
+        self.prune_last = prune_last   # last ViT layer: compute only the rows ln_post reads (False: the full block, same bits)
         g = lambda k: _dev(sd[f"{p}.{k}"], device)
         Wd, Fd = cfg.width, cfg.feat_dim
         self.pe_w = _dev(sd[f"{p}.patch_embed.weight"].reshape(Wd, -1), device)
@@ -227,7 +253,9 @@ class HybridEncoderHIP:
         if taps is not None:
             taps["feat_in"] = Fm.clone()
             taps["x_ln_pre"] = X.clone()
-        for i in range(cfg.layers):
+        last = cfg.layers - 1
+        prune = self.prune_last and taps is None and last not in self.cross and P2 % 32 == 0
+        for i in range(cfg.layers - 1 if prune else cfg.layers):
             rab_forward(X, self.layers[i], L, N, cfg.heads)
             if i in self.cross:
                 cross_forward(Fm, X, self.cross[i], N, 1 + P2 + T, P2)
@@ -238,7 +266,14 @@ class HybridEncoderHIP:
                 convnext_forward(Fm, c2, B, Hf, Wf)
             if taps is not None and i == 0:
                 taps["x_layer0"] = X.clone()
-        lat = ops.layernorm(X[1 + P2:], self.lnpost_w, self.lnpost_b, M=N * T, x_seg=(T, L))   # [(N*T), W]
+        if prune:
+            # Only the T latent tokens leave the ViT, so a last layer with no cross block behind it runs as rab_forward_last.  Its
+            # window starts at token P2, not 1 + P2: the attention kernel's 32 rows of a query block share their rescale decisions,
+            # so token P2 (one dead row in T + 1, 3 %) rides along to keep block P2/32 -- and every bit of it -- as it is in a full launch.
+            Xq = rab_forward_last(X, self.layers[last], L, N, cfg.heads, P2, T + 1)
+            lat = ops.layernorm(Xq[1:], self.lnpost_w, self.lnpost_b, M=N * T, x_seg=(T, T + 1))
+        else:
+            lat = ops.layernorm(X[1 + P2:], self.lnpost_w, self.lnpost_b, M=N * T, x_seg=(T, L))   # [(N*T), W]
         latT = ops.fake2d_transpose(lat, T * Wd, N, T, Wd)            # out[n][t][c] = flat_n[c*T + t]
         z = ops.gemm(latT, self.co_w, self.co_b)                       # [(N*T), token_size]
         for w in self.feat_out_swin:

@@ -550,10 +550,13 @@ def layernorm(x, gamma, beta, out=None, eps=1e-5, act=ACT_NONE, M=None, x_seg=(0
     return out
 
 
-def attention(q, k, v, out, L, nseq, nheads, rowmap=None, bias=None, biasvar=None, scale=0.125, mode=None, to_gemm=False, precision=None):
+def attention(q, k, v, out, L, nseq, nheads, rowmap=None, bias=None, biasvar=None, scale=0.125, mode=None, to_gemm=False, precision=None,
+              window=None):
     """q,k,v,out: 2-D row-strided views (rows x nheads*64).  mode: force attn_mode (tests / tools).
     to_gemm=True: the output feeds only the out-projection GEMM -> written as bf16x3 Planes over q's row space when the split
-    path is active (`out` may be None or a Planes object to reuse); otherwise into the fp32 `out` as always."""
+    path is active (`out` may be None or a Planes object to reuse); otherwise into the fp32 `out` as always.
+    window=(q_tok0, Lq): only the query tokens q_tok0 .. q_tok0+Lq-1 of every sequence (sgic_attention_window_f32): q and out
+    hold Lq rows per sequence, k and v all L; every row is bitwise what the full call gives for that token."""
     q, ldq = _rows(q)
     k, ldk = _rows(k)
     v, ldv = _rows(v)
@@ -568,6 +571,11 @@ def attention(q, k, v, out, L, nseq, nheads, rowmap=None, bias=None, biasvar=Non
         out, ldo = _rows(out)
     if rowmap is not None:
         assert rowmap.dtype == torch.int32 and rowmap.numel() == nseq * L and rowmap.is_contiguous()
+    q_tok0, Lq = window if window is not None else (0, 0)
+    if window is not None:
+        assert Lq > 0 and q.shape[0] >= nseq * Lq and (pl is not None or out.shape[0] >= nseq * Lq), (window, q.shape)
+    win = "_window" if window is not None else ""
+    wargs = (int(q_tok0), int(Lq)) if window is not None else ()
     if bias is not None:
         assert bias.dim() == 3 and bias.shape[1] == L and bias.shape[2] == L and bias.is_contiguous()
     if biasvar is not None:
@@ -577,18 +585,19 @@ def attention(q, k, v, out, L, nseq, nheads, rowmap=None, bias=None, biasvar=Non
 
     def launch(m):
         if pl is not None:
-            call("sgic_attention_split3_f32", _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(pl.t), ctypes.c_long(pl.rows), L, nseq, nheads,
-                 _p(rowmap), _p(bias), _p(biasvar), float(scale), launch_opts(0, m | s3, None))
+            call(f"sgic_attention{win}_split3_f32", _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(pl.t), ctypes.c_long(pl.rows), L, nseq, nheads,
+                 _p(rowmap), _p(bias), _p(biasvar), float(scale), *wargs, launch_opts(0, m | s3, None))
         else:
-            call("sgic_attention_f32", _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, L, nseq, nheads, _p(rowmap), _p(bias),
-                 _p(biasvar), float(scale), launch_opts(0, m | s3, None))
+            call(f"sgic_attention{win}_f32", _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, L, nseq, nheads, _p(rowmap), _p(bias),
+                 _p(biasvar), float(scale), *wargs, launch_opts(0, m | s3, None))
 
     # K/V ring depth (single buffer + more workgroups per CU vs double buffer + one barrier per tile) depends on L and
     # on how many workgroups the launch has -> tuned per shape like the GEMM tiles; results are identical.
     if mode is None:
         mode = 0
         if nseq * nheads * L >= 4096:
-            key = ("attn3" if s3 else "attn", nseq, L, nheads, int(bias is not None))
+            # a window launch has its own item list (a few row blocks per unit): its own entries, never a full launch's
+            key = ("attn3" if s3 else "attn", nseq, L, nheads, int(bias is not None)) + wargs
             mode = _lookup(key)
             if mode is None:
                 mode = 0
@@ -608,6 +617,18 @@ def attention(q, k, v, out, L, nseq, nheads, rowmap=None, bias=None, biasvar=Non
                     _remember(key, mode)
     launch(mode)
     return pl if pl is not None else out
+
+
+def copy_row_blocks(x, rows, stride_rows, nblocks, out=None):
+    """out[(i, r)] = x[i*stride_rows + r], r < rows, i < nblocks: an exact strided device copy (keeps -0.0, NaN payloads)"""
+    x, ldx = _rows(x)
+    C = x.shape[1]
+    assert ldx == C and stride_rows >= rows and x.shape[0] >= (nblocks - 1) * stride_rows + rows, (x.shape, rows, stride_rows, nblocks)
+    if out is None:
+        out = torch.empty(nblocks * rows, C, device=x.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.shape == (nblocks * rows, C)
+    call("sgic_copy_blocks_f32", _p(x), _cl(stride_rows * C), _p(out), _cl(rows * C), _cl(rows * C), nblocks)
+    return out
 
 
 def im2col_patch(x, P, mul=1.0, add=0.0, tile16=False, out=None):
