@@ -357,6 +357,19 @@ int sgic_search_codes_f32q_work_bytes(int nq, int n, int D, int k, int splits, i
 int sgic_search_codes_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, int k, int splits,
                            uint8_t *d_work, size_t work_bytes, float *d_out_scores, int32_t *d_out_idx, sgic_stream_t stream);
 
+/* Threshold (range) search over the same u8 codes (CodeIndex.range_search / duplicate_pairs): every pair (q, d) whose
+ *   score = (float32(N) * r_d) * r_q   (N, r as above: the bits sgic_search_codes_u8 reports)
+ * satisfies score >= threshold in fp32 is a hit.  Hits are appended, in no particular order, to d_out_q / d_out_d / d_out_score
+ * (`capacity` entries each) through the 64-bit counter *d_count, which the CALLER zeroes: the call adds the full number of hits to
+ * it and stores an entry only at a position < capacity, so the count is exact after an overflow and nothing past `capacity` is
+ * written (retry with `count` entries; the predicate is deterministic).  capacity = 0 with null arrays is a count-only call.
+ * self_join = 1: d_q is d_db, d_rq is d_rdb, nq == n; only pairs d > q are emitted and the database tiles wholly at or below a
+ * query tile's diagonal are not computed.  d_q / d_db 16-byte aligned, d_count 8-byte aligned; D % 64 == 0, D <= 4096; the
+ * threshold finite; `splits` as in sgic_search_codes_u8; anything else is SGIC_EINVAL.  No workspace. */
+int sgic_search_range_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D,
+                         float threshold, int self_join, int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q,
+                         int32_t *d_out_d, float *d_out_score, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

@@ -399,6 +399,129 @@ __global__ __launch_bounds__(256) void search_merge_kernel(const float *__restri
   }
 }
 
+// Threshold (range) search: search_codes_kernel's tiles and integer score, no top-k.  Every (query, database row) pair with
+//   score = (float(N) * r_d) * r_q >= T      (fp32; the bits sgic_search_codes_u8 reports)
+// is appended to one global list (q, d, score) through one 64-bit counter.  A wave that has hits in a step takes one atomic add for
+// all of them (ballots + lane ranks place the entries); a step without hits costs one wave-uniform branch.  The counter receives
+// every hit, an entry is stored only at a position < capacity: the count stays exact after an overflow and nothing is written past
+// capacity.  Query rows >= nq and database rows >= row_end are clamped for the loads and masked where entries are emitted.
+// self_join (q == db): only d > q is emitted, and the row loop starts at the first 64-row step that can hold a d > qbase, so
+// the tiles wholly at or below the diagonal are never computed; the diagonal tile is masked per element.
+template <int QF, int U>
+__global__ __launch_bounds__(256, 4) void search_range_kernel(const uint8_t *__restrict__ q, const float *__restrict__ r_q,
+                                                           const uint8_t *__restrict__ db, const float *__restrict__ r_db, int nq,
+                                                           int n, int D, int rows_per_split, float threshold, int self_join,
+                                                           unsigned long long capacity, unsigned long long *__restrict__ count,
+                                                           int *__restrict__ out_q, int *__restrict__ out_d,
+                                                           float *__restrict__ out_score) {
+  constexpr int QT = 16 * QF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int steps = D >> 6;
+  v4i *A = reinterpret_cast<v4i *>(smem);   // [QF][steps][64 lanes] fragments
+  int *sq = reinterpret_cast<int *>(smem + (size_t)QT * D);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+  int row0 = split * rows_per_split;
+  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
+  if (self_join) {   // row0 is a multiple of 64, so is the step that holds qbase + 1
+    const int first = (qbase + 1) & ~(kCandPerIter - 1);
+    row0 = row0 > first ? row0 : first;
+  }
+  if (row0 >= row_end) return;   // the whole split lies at or below the diagonal
+
+  if (tid < QT) sq[tid] = 0;
+  __syncthreads();
+  for (int i = tid; i < QF * steps * 64; i += 256) {   // one 16-byte fragment per (query fragment, step, lane)
+    const int ln = i & 63, t = i >> 6;
+    const int step = t % steps, f = t / steps;
+    const int row = f * 16 + (ln & 15);
+    int qi = qbase + row;
+    qi = qi < nq ? qi : nq - 1;
+    const uint4 v = *reinterpret_cast<const uint4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4));
+    atomicAdd(&sq[row], (int)sum_bytes16(v, 0u));
+    A[i] = to_i8x16(v);
+  }
+  __syncthreads();
+
+  int baseq[QF][4];
+  float rq[QF][4];
+  const int gq0 = qbase + 4 * (lane >> 4);   // this lane's query of (f, r) is gq0 + 16 f + r
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int gq = gq0 + 16 * f + r;
+      baseq[f][r] = 2 * (sq[f * 16 + 4 * (lane >> 4) + r] - 128 * D) + D;
+      rq[f][r] = r_q[gq < nq ? gq : nq - 1];
+    }
+
+  for (int base = row0; base < row_end; base += kCandPerIter) {
+    const int my = base + wave * 16 + (lane & 15);
+    const int myc = my < n ? my : n - 1;
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    v4i acc[QF];
+#pragma unroll
+    for (int f = 0; f < QF; f++) acc[f] = v4i{0, 0, 0, 0};
+    unsigned ssum = 0;
+    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
+      uint4 bv[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        ssum = sum_bytes16(bv[u], ssum);
+        const v4i b = to_i8x16(bv[u]);
+#pragma unroll
+        for (int f = 0; f < QF; f++)
+          acc[f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(f * steps + s0 + u) * 64 + lane], b, acc[f], 0, 0, 0);
+      }
+    }
+    ssum += __shfl_xor(ssum, 16);
+    ssum += __shfl_xor(ssum, 32);
+    const int sd2 = 2 * ((int)ssum - 128 * D);
+    const float rd = r_db[myc];
+    const int qlim = self_join ? my : nq;   // queries this lane may emit for: below nq, in a self-join (nq == n) below its own row
+    const bool valid = my < row_end;
+    unsigned hits = 0;   // bit 4 f + r
+#pragma unroll
+    for (int f = 0; f < QF; f++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const float score = ((float)(4 * acc[f][r] + baseq[f][r] + sd2) * rd) * rq[f][r];
+        const bool hit = valid && gq0 + 16 * f + r < qlim && score >= threshold;
+        hits |= hit ? 1u << (4 * f + r) : 0u;
+      }
+    if (__ballot(hits != 0) != 0ull) {   // rare: one atomic for all of this wave's hits of the step
+      unsigned before[QF * 4];           // entries of (f, r) start this far into the wave's block (wave-uniform)
+      unsigned total = 0;
+#pragma unroll
+      for (int m = 0; m < QF * 4; m++) {
+        before[m] = total;
+        total += (unsigned)__popcll(__ballot((hits >> m) & 1u));
+      }
+      unsigned long long start = 0;
+      if (lane == 0) start = atomicAdd(count, (unsigned long long)total);
+      start = __shfl(start, 0);
+#pragma unroll
+      for (int f = 0; f < QF; f++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int m = 4 * f + r;
+          const unsigned long long mask = __ballot((hits >> m) & 1u);
+          if ((hits >> m) & 1u) {
+            const unsigned long long pos = start + before[m] + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+            if (pos < capacity) {
+              out_q[pos] = gq0 + 16 * f + r;
+              out_d[pos] = my;
+              out_score[pos] = ((float)(4 * acc[f][r] + baseq[f][r] + sd2) * rd) * rq[f][r];   // the value tested above
+            }
+          }
+        }
+    }
+  }
+}
+
 struct Plan {
   int qf, qtiles, splits, rows_per_split;
   size_t lds, work_bytes;
@@ -406,6 +529,22 @@ struct Plan {
 
 size_t lds_bytes(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)D + (size_t)(k + kCandPerIter) * 8 + 12); }
 size_t lds_bytes_f32q(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)3 * D + (size_t)(k + kCandPerIter) * 8 + 16); }
+size_t lds_bytes_range(int qf, int D) { return (size_t)16 * qf * ((size_t)D + 4); }   // the query tile and its byte sums
+
+// contiguous ascending database splits of whole 64-row steps, none empty; splits <= 0: cover the chip a few times over
+void plan_splits(int n, int splits, Plan *p) {
+  if (splits <= 0) {
+    splits = (1024 + p->qtiles - 1) / p->qtiles;
+    const int most = (n + 255) / 256;
+    splits = splits < most ? splits : most;
+  }
+  const int tiles = (n + kCandPerIter - 1) / kCandPerIter;
+  splits = splits < tiles ? splits : tiles;
+  splits = splits < kMaxSplits ? splits : kMaxSplits;
+  const int per = (n + splits - 1) / splits;
+  p->rows_per_split = (per + kCandPerIter - 1) / kCandPerIter * kCandPerIter;
+  p->splits = (n + p->rows_per_split - 1) / p->rows_per_split;
+}
 
 int make_plan(int nq, int n, int D, int k, int splits, bool f32q, Plan *p) {
   SGIC_REQUIRE(nq > 0 && n > 0 && k > 0 && k <= n, "sizes");
@@ -418,19 +557,22 @@ int make_plan(int nq, int n, int D, int k, int splits, bool f32q, Plan *p) {
     p->qf = (nq > 16 && lds_bytes(4, D, k) <= (size_t)kLdsBigTile) ? 4 : 1;
   p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
   SGIC_REQUIRE(splits <= kMaxSplits, "splits");
-  if (splits <= 0) {   // cover the chip a few times over when there are few query tiles
-    splits = (1024 + p->qtiles - 1) / p->qtiles;
-    const int most = (n + 255) / 256;
-    splits = splits < most ? splits : most;
-  }
-  const int tiles = (n + kCandPerIter - 1) / kCandPerIter;
-  splits = splits < tiles ? splits : tiles;
-  splits = splits < kMaxSplits ? splits : kMaxSplits;
-  const int per = (n + splits - 1) / splits;
-  p->rows_per_split = (per + kCandPerIter - 1) / kCandPerIter * kCandPerIter;
-  p->splits = (n + p->rows_per_split - 1) / p->rows_per_split;   // no empty split
+  plan_splits(n, splits, p);
   p->lds = f32q ? lds_bytes_f32q(p->qf, D, k) : lds_bytes(p->qf, D, k);
   p->work_bytes = p->splits > 1 ? (size_t)nq * p->splits * k * 8 : 0;
+  return SGIC_OK;
+}
+
+// the plan of the threshold search: make_plan's tile choice with the smaller LDS formula (no candidate buffers), its splits
+int make_range_plan(int nq, int n, int D, int splits, Plan *p) {
+  SGIC_REQUIRE(nq > 0 && n > 0, "sizes");
+  SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "D must be a multiple of 64, at most 4096 (int32 exactness)");
+  SGIC_REQUIRE(splits <= kMaxSplits, "splits");
+  p->qf = (nq > 16 && lds_bytes_range(4, D) <= (size_t)kLdsBigTile) ? 4 : 1;
+  p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
+  plan_splits(n, splits, p);
+  p->lds = lds_bytes_range(p->qf, D);
+  p->work_bytes = 0;
   return SGIC_OK;
 }
 
@@ -462,7 +604,45 @@ int launch_search_f32q(const Plan &p, const float *q, const uint8_t *db, const f
   return sgic::check_launch("search_f32q_kernel");
 }
 
+template <int QF, int U>
+int launch_search_range(const Plan &p, const uint8_t *q, const float *r_q, const uint8_t *db, const float *r_db, int nq, int n, int D,
+                        float threshold, int self_join, unsigned long long capacity, unsigned long long *count, int *oq, int *od,
+                        float *os, hipStream_t st) {
+  static bool lds_raised = false;   // largest use: 16 queries, D = 4096 -> 64.06 KiB
+  if (p.lds > 60 * 1024 && !lds_raised) {
+    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_range_kernel<QF, U>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 128 * 1024));
+    lds_raised = true;
+  }
+  search_range_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, r_q, db, r_db, nq, n, D, p.rows_per_split, threshold,
+                                                                         self_join, capacity, count, oq, od, os);
+  return sgic::check_launch("search_range_kernel");
+}
+
 }  // namespace
+
+extern "C" int sgic_search_range_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
+                                    int D, float threshold, int self_join, int splits, long long capacity, uint64_t *d_count,
+                                    int32_t *d_out_q, int32_t *d_out_d, float *d_out_score, sgic_stream_t stream) {
+  Plan p;
+  const int rc = make_range_plan(nq, n, D, splits, &p);
+  if (rc != SGIC_OK) return rc;
+  SGIC_REQUIRE(d_q && d_rq && d_db && d_rdb && d_count, "null pointer");
+  SGIC_REQUIRE(capacity >= 0 && (capacity == 0 || (d_out_q && d_out_d && d_out_score)), "capacity > 0 needs the three output arrays");
+  SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db) % 16 == 0, "codes must be 16-byte aligned");
+  SGIC_REQUIRE((uintptr_t)d_count % 8 == 0, "the hit counter must be 8-byte aligned");
+  SGIC_REQUIRE(isfinite(threshold), "the threshold must be finite");
+  SGIC_REQUIRE(!self_join || nq == n, "self_join: the queries are the database (nq == n)");
+  hipStream_t st = to_stream(stream);
+  unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_count);
+  const unsigned long long cap = (unsigned long long)capacity;
+  const int sj = self_join ? 1 : 0;
+  const bool u8 = D % 512 == 0;   // eight 64-byte steps per round when D allows it, else one
+  return p.qf == 4 ? (u8 ? launch_search_range<4, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st)
+                         : launch_search_range<4, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st))
+                   : (u8 ? launch_search_range<1, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st)
+                         : launch_search_range<1, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st));
+}
 
 extern "C" int sgic_search_codes_u8_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes) {
   Plan p;

@@ -2,6 +2,7 @@
 CUDA tensors used purely as device-memory handles; all arithmetic happens in the HIP kernels."""
 import ctypes
 import json
+import math
 import os
 
 import numpy as np
@@ -1074,6 +1075,65 @@ def search_codes_f32q(q, db_codes, r_db, k, splits=None):
     call("sgic_search_codes_f32q", _p(q), _p(db_codes), _p(r_db), nq, n, D, int(k), want, _p(work), ctypes.c_size_t(nbytes.value), _p(os_),
          _p(oi))
     return os_, oi
+
+
+def search_codes_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join, splits, capacity, count, out_q, out_d, out_score):
+    """one call of sgic_search_range_u8 (include/sgic.h), nothing else: `count` (1,) int64 on the device is ADDED to (the caller
+    zeroes it), out_q / out_d int32 and out_score fp32 hold at least `capacity` entries each (None with capacity = 0: count only).
+    No synchronisation; hits arrive in no particular order."""
+    require_gpu()
+    for t, dt in ((q_codes, torch.uint8), (db_codes, torch.uint8), (r_q, torch.float32), (r_db, torch.float32), (count, torch.int64)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
+    nq, D = q_codes.shape
+    n, Dd = db_codes.shape
+    assert D == Dd and r_q.shape == (nq,) and r_db.shape == (n,) and count.numel() == 1
+    capacity = int(capacity)
+    for t, dt in ((out_q, torch.int32), (out_d, torch.int32), (out_score, torch.float32)):
+        assert (t is None and capacity == 0) or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= capacity)
+    call("sgic_search_range_u8", _p(q_codes), _p(r_q), _p(db_codes), _p(r_db), nq, n, D, float(threshold), bool(self_join),
+         0 if splits is None else int(splits), ctypes.c_longlong(capacity), _p(count), _p(out_q), _p(out_d), _p(out_score))
+
+
+def search_codes_range(q_codes, r_q, db_codes, r_db, threshold, self_join=False, capacity=None, splits=None, max_pairs=None):
+    """threshold (range) search over u8 codes (csrc/search.hip, search_range_kernel): every pair whose score -- the fp32 bits
+    search_codes reports -- is >= threshold.  Inputs as for search_codes.  self_join: the queries are the database (pass the same
+    tensors); only pairs d > q are returned and the tiles below the diagonal are not computed.
+    -> (q int32, d int32, score fp32, count), sorted by (q, d) ascending on the device, so the result does not depend on the
+    order in which the kernel's waves appended their hits.  The first launch has room for `capacity` hits (default: four per
+    row, at least 4096); a larger count allocates exactly `count` entries and launches once more -- the predicate is
+    deterministic, the second count equals the first.  max_pairs: a count above it raises ValueError before that allocation."""
+    threshold = float(threshold)
+    if not math.isfinite(threshold):
+        raise ValueError(f"range search needs a finite threshold, got {threshold}")
+    nq, n = q_codes.shape[0], db_codes.shape[0]
+    dev = db_codes.device
+    if capacity is None:
+        capacity = min(nq * n, max(4096, 4 * max(nq, n)))
+        if max_pairs is not None:
+            capacity = min(capacity, int(max_pairs))
+    capacity = int(capacity)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def launch(cap):
+        oq = torch.empty(cap, dtype=torch.int32, device=dev) if cap else None
+        od = torch.empty(cap, dtype=torch.int32, device=dev) if cap else None
+        os_ = torch.empty(cap, dtype=torch.float32, device=dev) if cap else None
+        count.zero_()
+        search_codes_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join, splits, cap, count, oq, od, os_)
+        return oq, od, os_, int(count.item())
+
+    oq, od, os_, total = launch(capacity)
+    if max_pairs is not None and total > int(max_pairs):
+        raise ValueError(f"{total} pairs score >= {threshold}, more than max_pairs = {int(max_pairs)}: raise the threshold or max_pairs")
+    if total > capacity:
+        del oq, od, os_
+        oq, od, os_, again = launch(total)
+        assert again == total, f"range search counted {total} hits, then {again}"
+    if total == 0:
+        return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev), 0)
+    key, order = torch.sort((oq[:total].to(torch.int64) << 32) | od[:total].to(torch.int64))
+    return (key >> 32).to(torch.int32), (key & 0xFFFFFFFF).to(torch.int32), os_[:total][order], total
 
 
 def jpeg_decode_batch(params, scan, tabs, segs, quant, B, H, W, total_blocks, plane_bytes, max_blocks, out=None, check=True):

@@ -9,6 +9,8 @@ database^T) + a top-k kernel on the GPU.
 writes the u8 codes themselves (codes.npy), which `--codes` (on all three query commands) and `neighbours` search with the fused
 i8 kernels (csrc/search.hip): integer inner products, no fp32 database and no score matrix on the device.  A u8 query code is used
 as it is; an fp32 text / image vector is taken to 2^-22 fixed point and searched as three i8 digit planes.
+`duplicates --threshold T` lists the groups of rows whose codes score >= T against each other (a threshold search over the same
+codes, each pair computed once), and `query-c2df --codes --min_score T` returns every hit above T instead of the top k.
 `build-images` (the reference's `build.py build-images`) indexes a folder of ordinary images with the CLIP tower alone: no codec, no
 container.  The decoded bytes go to the tower as they are (clip.py preprocess_u8), and the index directory carries the same files
 as `build`, the tower's own u8 codes included."""
@@ -143,6 +145,37 @@ def code_rnorm(codes, chunk=1 << 16):
     return r
 
 
+def finite_threshold(threshold, what="threshold"):
+    """a score threshold as a float; NaN and the infinities are refused here, before anything is loaded or launched"""
+    t = float(threshold)
+    if not np.isfinite(t):
+        raise ValueError(f"{what} must be a finite score, got {t}")
+    return t
+
+
+def duplicate_groups(i, j):
+    """connected components, with at least two members, of the graph whose edges are the pairs (i[e], j[e]): union-find on the
+    host -> [[row, ...], ...], members in index order, groups ordered by their first member"""
+    parent = {}
+
+    def find(a):
+        root = a
+        while parent.setdefault(root, root) != root:
+            root = parent[root]
+        while parent[a] != root:       # path compression
+            parent[a], a = root, parent[a]
+        return root
+
+    for a, b in zip(np.asarray(i).tolist(), np.asarray(j).tolist()):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)      # the root is the component's lowest row
+    groups = {}
+    for a in sorted(parent):
+        groups.setdefault(find(a), []).append(a)
+    return [g for _, g in sorted(groups.items()) if len(g) > 1]
+
+
 class CodeIndex:
     """an index of the u8 CLIP codes themselves: `codes` (n, D) u8, `ids` [n].  Searched with the fused i8 kernel
     (ops.search_codes) for u8 query codes and with its fp32-query sibling (ops.search_codes_f32q) for text / image vectors: scores
@@ -244,6 +277,43 @@ class CodeIndex:
         k = max(1, min(int(k), len(self)))
         s, i = ops.search_codes_f32q(t.to(db.device).contiguous(), db, r_db, k)
         return s.cpu().numpy(), i.cpu().numpy()
+
+    def range_search(self, q_codes, threshold, max_pairs=None):
+        """every database row whose score against a query is >= threshold (fp32, the bits `search` reports), the FAISS range_search
+        shape: q_codes (nq, D) u8 -> (lims (nq + 1,) int64, scores fp32, indices int32); query j owns lims[j]:lims[j + 1], database
+        index ascending.  One fused launch (ops.search_codes_range), no top-k and no limit on the hits per query"""
+        from . import ops
+        t = finite_threshold(threshold)
+        q = np.ascontiguousarray(np.atleast_2d(q_codes), dtype=np.uint8)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query codes of dim {q.shape[1]} against an index of dim {self.dim}")
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        hq, hd, hs, _ = ops.search_codes_range(torch.from_numpy(q).to(db.device), torch.from_numpy(code_rnorm(q)).to(db.device), db, r_db, t,
+                                               max_pairs=max_pairs)
+        lims = np.zeros(q.shape[0] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(hq.cpu().numpy(), minlength=q.shape[0]), out=lims[1:])
+        return lims, hs.cpu().numpy(), hd.cpu().numpy()
+
+    def duplicate_pairs(self, threshold, max_pairs=1 << 24):
+        """every pair of rows i < j of the index whose score is >= threshold -> (i int32, j int32, score fp32), sorted by (i, j).
+        The self-join mode of the range kernel: each pair is computed once, the half below the diagonal not at all.  More than
+        max_pairs pairs is a ValueError naming the count (a threshold that low describes the corpus, not its duplicates)"""
+        from . import ops
+        t = finite_threshold(threshold)
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        hi, hj, hs, _ = ops.search_codes_range(db, r_db, db, r_db, t, self_join=True, max_pairs=max_pairs)
+        return hi.cpu().numpy(), hj.cpu().numpy(), hs.cpu().numpy()
+
+    def duplicate_groups(self, threshold, max_pairs=1 << 24, with_pairs=False):
+        """the connected components (>= 2 rows) of the graph of duplicate_pairs(threshold): [[row, ...], ...], members in index
+        order, groups ordered by first member; with_pairs: -> (groups, (i, j, score))"""
+        i, j, s = self.duplicate_pairs(threshold, max_pairs)
+        groups = duplicate_groups(i, j)
+        return (groups, (i, j, s)) if with_pairs else groups
 
     def neighbours(self, topk, chunk=4096):
         """k-NN graph of the index over itself, own id removed: yields (row, [(neighbour row, score)] of length <= topk), queries in
@@ -435,15 +505,25 @@ def build_index_from_images(image_dir, index_dir, clip_ckpt=None, small=False, b
     return rec
 
 
-def _query_codes(index_dir, c2df, topk):
-    """`query-c2df --codes`: a file -> result list; a directory -> {path: result list}, all queries in one fused call"""
+def _query_codes(index_dir, c2df, topk, min_score=None):
+    """`query-c2df --codes`: a file -> result list; a directory -> {path: result list}, all queries in one fused call.  min_score:
+    every hit with score >= min_score instead of the top k, score descending, ties to the lower index"""
     ci = CodeIndex.load(index_dir)
     src = Path(c2df)
     files = sorted(src.glob("**/*.c2df")) if src.is_dir() else [src]
     if not files:
         raise RuntimeError(f"no .c2df under {src}")
-    s, idx = ci.search(np.stack([embedded_clip_codes(f)[0] for f in files]), topk)
-    res = [[{"path": ci.ids[i], "score": float(v)} for i, v in zip(idx[j], s[j])] for j in range(len(files))]
+    codes = np.stack([embedded_clip_codes(f)[0] for f in files])
+    if min_score is None:
+        s, idx = ci.search(codes, topk)
+        res = [[{"path": ci.ids[i], "score": float(v)} for i, v in zip(idx[j], s[j])] for j in range(len(files))]
+    else:
+        lims, s, idx = ci.range_search(codes, min_score)
+        res = []
+        for j in range(len(files)):
+            sj, ij = s[lims[j]:lims[j + 1]], idx[lims[j]:lims[j + 1]]
+            order = np.lexsort((ij, -sj))
+            res.append([{"path": ci.ids[i], "score": float(v)} for i, v in zip(ij[order], sj[order])])
     return {str(f): r for f, r in zip(files, res)} if src.is_dir() else res[0]
 
 
@@ -466,8 +546,37 @@ def _query_vector(args):
     return encode_text(toks, ClipTextHIP(tsd, CLIP_B32, "cuda:0"))
 
 
+def write_duplicates(index_dir, threshold, out=None, max_pairs=1 << 24):
+    """`duplicates`: the groups of rows of the code index linked by a score >= threshold, one JSON line per group:
+    {"paths": [...], "links": [{"a": path, "b": path, "score": s}, ...]}, links sorted by (row of a, row of b).  A last line on
+    stderr gives the counts.  -> (rows, pairs, groups, files in groups)"""
+    ci = CodeIndex.load(index_dir)
+    groups, (i, j, s) = ci.duplicate_groups(threshold, max_pairs, with_pairs=True)
+    group_of = {row: g for g, rows in enumerate(groups) for row in rows}
+    links = [[] for _ in groups]
+    for a, b, v in zip(i.tolist(), j.tolist(), s.tolist()):      # already sorted by (a, b)
+        links[group_of[a]].append({"a": ci.ids[a], "b": ci.ids[b], "score": v})
+    fh = open(out, "w", encoding="utf-8") if out else sys.stdout
+    try:
+        for rows, ln in zip(groups, links):
+            fh.write(json.dumps({"paths": [ci.ids[r] for r in rows], "links": ln}, ensure_ascii=False) + "\n")
+    finally:
+        if out:
+            fh.close()
+    counts = (len(ci), len(i), len(groups), sum(len(g) for g in groups))
+    print("[OK] %d rows, %d pairs with score >= %r, %d groups, %d files in groups" % (counts[0], counts[1], threshold, counts[2], counts[3]),
+          file=sys.stderr)
+    return counts
+
+
+_THRESHOLD_HELP = ("score threshold (cosine of the dequantised codes, fp32).  Measured on quantised unit codes at D = 512: a row scores "
+                   "1 +- 2^-23 against itself (so 1.0 can miss it), one code off by one step <= 0.99997, 64 codes off about 0.998, all 512 "
+                   "off about 0.985, unrelated rows < 0.2.  About 0.99999 selects identical codes only, 0.98-0.99 re-encodes of one "
+                   "picture")
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours")
+    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours / duplicates")
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name, arg in (("query-text", "--text"), ("query-image", "--image"), ("query-c2df", "--c2df")):
         p = sub.add_parser(name)
@@ -482,6 +591,8 @@ def main(argv=None):
         if name == "query-c2df":
             p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused i8 kernel; "
                            "--c2df may then be a directory")
+            p.add_argument("--min_score", type=float, default=None, help="with --codes: every hit with score >= MIN_SCORE instead of "
+                           "the top k (--topk is ignored then), score descending, ties to the lower index.  " + _THRESHOLD_HELP)
         else:
             p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused fp32-query "
                            "kernel instead of the fp32 index files")
@@ -509,7 +620,20 @@ def main(argv=None):
     p.add_argument("--index_dir", type=Path, required=True)
     p.add_argument("--topk", type=int, default=10)
     p.add_argument("--out", type=Path, default=None)
+    p = sub.add_parser("duplicates", help="groups of near-duplicate rows of the code index, one JSON line each")
+    p.add_argument("--index_dir", type=Path, required=True)
+    p.add_argument("--threshold", type=float, required=True, help=_THRESHOLD_HELP + ".  There is no default")
+    p.add_argument("--out", type=Path, default=None)
+    p.add_argument("--max_pairs", type=int, default=1 << 24, help="refuse (and name the count) when more pairs than this pass the threshold")
     args = ap.parse_args(argv)
+    for flag in ("threshold", "min_score"):      # refused before any file is read or kernel launched
+        if getattr(args, flag, None) is not None and not np.isfinite(getattr(args, flag)):
+            ap.error(f"--{flag} {getattr(args, flag)}: a finite score is needed")
+    if getattr(args, "min_score", None) is not None and not args.codes:
+        ap.error("--min_score needs --codes: only the u8 code index has a threshold search")
+    if args.cmd == "duplicates":
+        write_duplicates(args.index_dir, args.threshold, args.out, args.max_pairs)
+        return 0
     if args.cmd == "build":
         build_index(args.c2df_dir, args.index_dir)
         return 0
@@ -536,7 +660,7 @@ def main(argv=None):
                 out.close()
         return 0
     if args.cmd == "query-c2df" and args.codes:
-        print(json.dumps(_query_codes(args.index_dir, args.c2df, args.topk), ensure_ascii=False, indent=2))
+        print(json.dumps(_query_codes(args.index_dir, args.c2df, args.topk, args.min_score), ensure_ascii=False, indent=2))
         return 0
     if args.codes:   # text / image vector against the u8 codes
         ci = CodeIndex.load(args.index_dir)
