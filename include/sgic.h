@@ -370,6 +370,22 @@ int sgic_search_range_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d
                          float threshold, int self_join, int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q,
                          int32_t *d_out_d, float *d_out_score, sgic_stream_t stream);
 
+/* The threshold search with fp32 queries (text / image vectors, CodeIndex.range_search_vectors): d_q (nq, D) fp32 against the u8
+ * codes d_db (n, D) and their d_rdb.  The query goes to 2^-22 fixed point and three balanced base-256 digit planes exactly as in
+ * sgic_search_codes_f32q (Q, d0, d1, d2, S_p and the int64 M = 2 (65536 S_2 + 256 S_1 + S_0) + sum_j Q_j are those of its comment;
+ * a NaN coordinate gives 0), and a pair (q, d) is a hit iff
+ *   score = (float32(M) * r_d) * 2^-22 >= threshold   (fp32, in that order: the bits sgic_search_codes_f32q reports)
+ * No float add, root or division runs on the device.  Hits are appended, in no particular order, to d_out_q / d_out_d /
+ * d_out_score (`capacity` entries each) through the 64-bit counter *d_count, which the CALLER zeroes.  Overflow contract, as in
+ * sgic_search_range_u8: the call adds the full number of hits to the counter and stores an entry only at a position < capacity, so
+ * the count is exact after an overflow and nothing past `capacity` is written (retry with `count` entries; the predicate is
+ * deterministic).  capacity = 0 with null arrays is a count-only call.  There is no self-join.  d_q / d_db 16-byte aligned,
+ * d_count 8-byte aligned; D % 64 == 0, D <= 2048 (three query planes in LDS); the threshold finite; `splits` as in
+ * sgic_search_codes_u8; anything else is SGIC_EINVAL.  No workspace. */
+int sgic_search_range_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, float threshold,
+                           int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,
+                           float *d_out_score, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

@@ -522,6 +522,119 @@ __global__ __launch_bounds__(256, 4) void search_range_kernel(const uint8_t *__r
   }
 }
 
+// Threshold (range) search with fp32 queries: search_f32q_kernel's prologue (three digit planes and sum Q in LDS) in front of
+// search_range_kernel's row loop and append protocol.  A pair is a hit iff
+//   score = (float(M) * r_d) * 2^-22 >= T      (fp32; the bits sgic_search_codes_f32q reports)
+// LDS holds the planes and sum Q only, 16 QF (3 D + 8) bytes; there is no self-join (fp32 queries are not the database) and, as in
+// the top-k sibling, no byte sum of the database rows.
+template <int QF, int U>
+__global__ __launch_bounds__(256, 4) void search_range_f32q_kernel(const float *__restrict__ q, const uint8_t *__restrict__ db,
+                                                                const float *__restrict__ r_db, int nq, int n, int D,
+                                                                int rows_per_split, float threshold, unsigned long long capacity,
+                                                                unsigned long long *__restrict__ count, int *__restrict__ out_q,
+                                                                int *__restrict__ out_d, float *__restrict__ out_score) {
+  constexpr int QT = 16 * QF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int steps = D >> 6;
+  const int plane = QF * steps * 64;         // fragments per digit plane
+  v4i *A = reinterpret_cast<v4i *>(smem);   // [3 planes][QF][steps][64 lanes] fragments
+  unsigned long long *sq = reinterpret_cast<unsigned long long *>(smem + (size_t)3 * QT * D);   // sum Q per query
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+  const int row0 = split * rows_per_split;
+  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
+
+  if (tid < QT) sq[tid] = 0;
+  __syncthreads();
+  for (int i = tid; i < plane; i += 256) {   // sixteen coordinates -> one fragment in each plane per (query fragment, step, lane)
+    const int ln = i & 63, t = i >> 6;
+    const int step = t % steps, f = t / steps;
+    const int row = f * 16 + (ln & 15);
+    int qi = qbase + row;
+    qi = qi < nq ? qi : nq - 1;
+    v4i p0, p1, p2;
+    const int s = quantise16(reinterpret_cast<const float4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4)), p0, p1, p2);
+    atomicAdd(&sq[row], (unsigned long long)(long long)s);
+    A[i] = p0;
+    A[plane + i] = p1;
+    A[2 * plane + i] = p2;
+  }
+  __syncthreads();
+
+  long long sumq[QF][4];
+  const int gq0 = qbase + 4 * (lane >> 4);   // this lane's query of (f, r) is gq0 + 16 f + r
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) sumq[f][r] = (long long)sq[f * 16 + 4 * (lane >> 4) + r];
+
+  for (int base = row0; base < row_end; base += kCandPerIter) {
+    const int my = base + wave * 16 + (lane & 15);
+    const int myc = my < n ? my : n - 1;
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    v4i acc[3][QF];
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+      for (int f = 0; f < QF; f++) acc[p][f] = v4i{0, 0, 0, 0};
+    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
+      uint4 bv[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const v4i b = to_i8x16(bv[u]);
+#pragma unroll
+        for (int p = 0; p < 3; p++)
+#pragma unroll
+          for (int f = 0; f < QF; f++)
+            acc[p][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[p * plane + (f * steps + s0 + u) * 64 + lane], b, acc[p][f], 0, 0, 0);
+      }
+    }
+    const float rd = r_db[myc];
+    const bool valid = my < row_end;
+    float score[QF][4];
+    unsigned hits = 0;   // bit 4 f + r
+#pragma unroll
+    for (int f = 0; f < QF; f++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const long long M = 2 * (65536LL * acc[2][f][r] + 256LL * acc[1][f][r] + acc[0][f][r]) + sumq[f][r];
+        score[f][r] = ((float)M * rd) * (1.0f / kQScale);
+        const bool hit = valid && gq0 + 16 * f + r < nq && score[f][r] >= threshold;
+        hits |= hit ? 1u << (4 * f + r) : 0u;
+      }
+    if (__ballot(hits != 0) != 0ull) {   // rare: one atomic for all of this wave's hits of the step
+      unsigned before[QF * 4];           // entries of (f, r) start this far into the wave's block (wave-uniform)
+      unsigned total = 0;
+#pragma unroll
+      for (int m = 0; m < QF * 4; m++) {
+        before[m] = total;
+        total += (unsigned)__popcll(__ballot((hits >> m) & 1u));
+      }
+      unsigned long long start = 0;
+      if (lane == 0) start = atomicAdd(count, (unsigned long long)total);
+      start = __shfl(start, 0);
+#pragma unroll
+      for (int f = 0; f < QF; f++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int m = 4 * f + r;
+          const unsigned long long mask = __ballot((hits >> m) & 1u);
+          if ((hits >> m) & 1u) {
+            const unsigned long long pos = start + before[m] + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+            if (pos < capacity) {
+              out_q[pos] = gq0 + 16 * f + r;
+              out_d[pos] = my;
+              out_score[pos] = score[f][r];   // the value tested above
+            }
+          }
+        }
+    }
+  }
+}
+
 struct Plan {
   int qf, qtiles, splits, rows_per_split;
   size_t lds, work_bytes;
@@ -530,6 +643,7 @@ struct Plan {
 size_t lds_bytes(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)D + (size_t)(k + kCandPerIter) * 8 + 12); }
 size_t lds_bytes_f32q(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)3 * D + (size_t)(k + kCandPerIter) * 8 + 16); }
 size_t lds_bytes_range(int qf, int D) { return (size_t)16 * qf * ((size_t)D + 4); }   // the query tile and its byte sums
+size_t lds_bytes_range_f32q(int qf, int D) { return (size_t)16 * qf * ((size_t)3 * D + 8); }   // three digit planes and sum Q
 
 // contiguous ascending database splits of whole 64-row steps, none empty; splits <= 0: cover the chip a few times over
 void plan_splits(int n, int splits, Plan *p) {
@@ -563,15 +677,19 @@ int make_plan(int nq, int n, int D, int k, int splits, bool f32q, Plan *p) {
   return SGIC_OK;
 }
 
-// the plan of the threshold search: make_plan's tile choice with the smaller LDS formula (no candidate buffers), its splits
-int make_range_plan(int nq, int n, int D, int splits, Plan *p) {
+// the plan of the threshold searches: make_plan's tile choice with the smaller LDS formulas (no candidate buffers), its splits
+int make_range_plan(int nq, int n, int D, int splits, bool f32q, Plan *p) {
   SGIC_REQUIRE(nq > 0 && n > 0, "sizes");
   SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "D must be a multiple of 64, at most 4096 (int32 exactness)");
+  SGIC_REQUIRE(!f32q || D <= kMaxDimF32Q, "fp32 queries: D at most 2048 (three query digit planes have to fit the LDS)");
   SGIC_REQUIRE(splits <= kMaxSplits, "splits");
-  p->qf = (nq > 16 && lds_bytes_range(4, D) <= (size_t)kLdsBigTile) ? 4 : 1;
+  if (f32q)   // three planes: the wide tile is 32 queries, up to D = 832
+    p->qf = (nq > 16 && lds_bytes_range_f32q(2, D) <= (size_t)kLdsBigTile) ? 2 : 1;
+  else
+    p->qf = (nq > 16 && lds_bytes_range(4, D) <= (size_t)kLdsBigTile) ? 4 : 1;
   p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
   plan_splits(n, splits, p);
-  p->lds = lds_bytes_range(p->qf, D);
+  p->lds = f32q ? lds_bytes_range_f32q(p->qf, D) : lds_bytes_range(p->qf, D);
   p->work_bytes = 0;
   return SGIC_OK;
 }
@@ -619,13 +737,48 @@ int launch_search_range(const Plan &p, const uint8_t *q, const float *r_q, const
   return sgic::check_launch("search_range_kernel");
 }
 
+template <int QF, int U>
+int launch_search_range_f32q(const Plan &p, const float *q, const uint8_t *db, const float *r_db, int nq, int n, int D, float threshold,
+                             unsigned long long capacity, unsigned long long *count, int *oq, int *od, float *os, hipStream_t st) {
+  static bool lds_raised = false;   // largest use: 16 queries, D = 2048 -> 96.1 KiB
+  if (p.lds > 60 * 1024 && !lds_raised) {
+    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_range_f32q_kernel<QF, U>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    lds_raised = true;
+  }
+  search_range_f32q_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, db, r_db, nq, n, D, p.rows_per_split, threshold,
+                                                                              capacity, count, oq, od, os);
+  return sgic::check_launch("search_range_f32q_kernel");
+}
+
 }  // namespace
+
+extern "C" int sgic_search_range_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, float threshold,
+                                      int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,
+                                      float *d_out_score, sgic_stream_t stream) {
+  Plan p;
+  const int rc = make_range_plan(nq, n, D, splits, true, &p);
+  if (rc != SGIC_OK) return rc;
+  SGIC_REQUIRE(d_q && d_db && d_rdb && d_count, "null pointer");
+  SGIC_REQUIRE(capacity >= 0 && (capacity == 0 || (d_out_q && d_out_d && d_out_score)), "capacity > 0 needs the three output arrays");
+  SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db) % 16 == 0, "queries and codes must be 16-byte aligned");
+  SGIC_REQUIRE((uintptr_t)d_count % 8 == 0, "the hit counter must be 8-byte aligned");
+  SGIC_REQUIRE(isfinite(threshold), "the threshold must be finite");
+  hipStream_t st = to_stream(stream);
+  unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_count);
+  const unsigned long long cap = (unsigned long long)capacity;
+  const bool u8 = D % 512 == 0;   // eight 64-byte steps per round when D allows it, else one
+  return p.qf == 2 ? (u8 ? launch_search_range_f32q<2, 8>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st)
+                         : launch_search_range_f32q<2, 1>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st))
+                   : (u8 ? launch_search_range_f32q<1, 8>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st)
+                         : launch_search_range_f32q<1, 1>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st));
+}
 
 extern "C" int sgic_search_range_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
                                     int D, float threshold, int self_join, int splits, long long capacity, uint64_t *d_count,
                                     int32_t *d_out_q, int32_t *d_out_d, float *d_out_score, sgic_stream_t stream) {
   Plan p;
-  const int rc = make_range_plan(nq, n, D, splits, &p);
+  const int rc = make_range_plan(nq, n, D, splits, false, &p);
   if (rc != SGIC_OK) return rc;
   SGIC_REQUIRE(d_q && d_rq && d_db && d_rdb && d_count, "null pointer");
   SGIC_REQUIRE(capacity >= 0 && (capacity == 0 || (d_out_q && d_out_d && d_out_score)), "capacity > 0 needs the three output arrays");

@@ -1094,19 +1094,31 @@ def search_codes_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join
          0 if splits is None else int(splits), ctypes.c_longlong(capacity), _p(count), _p(out_q), _p(out_d), _p(out_score))
 
 
-def search_codes_range(q_codes, r_q, db_codes, r_db, threshold, self_join=False, capacity=None, splits=None, max_pairs=None):
-    """threshold (range) search over u8 codes (csrc/search.hip, search_range_kernel): every pair whose score -- the fp32 bits
-    search_codes reports -- is >= threshold.  Inputs as for search_codes.  self_join: the queries are the database (pass the same
-    tensors); only pairs d > q are returned and the tiles below the diagonal are not computed.
-    -> (q int32, d int32, score fp32, count), sorted by (q, d) ascending on the device, so the result does not depend on the
-    order in which the kernel's waves appended their hits.  The first launch has room for `capacity` hits (default: four per
-    row, at least 4096); a larger count allocates exactly `count` entries and launches once more -- the predicate is
-    deterministic, the second count equals the first.  max_pairs: a count above it raises ValueError before that allocation."""
+def search_codes_range_f32q_launch(q, db_codes, r_db, threshold, splits, capacity, count, out_q, out_d, out_score):
+    """one call of sgic_search_range_f32q (include/sgic.h), nothing else: q (nq, D) fp32; `count`, the output arrays and
+    `capacity` as in search_codes_range_launch (the counter is ADDED to).  No synchronisation; hits arrive in no particular order."""
+    require_gpu()
+    for t, dt in ((q, torch.float32), (db_codes, torch.uint8), (r_db, torch.float32), (count, torch.int64)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
+    nq, D = q.shape
+    n, Dd = db_codes.shape
+    assert D == Dd and r_db.shape == (n,) and count.numel() == 1
+    capacity = int(capacity)
+    for t, dt in ((out_q, torch.int32), (out_d, torch.int32), (out_score, torch.float32)):
+        assert (t is None and capacity == 0) or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= capacity)
+    call("sgic_search_range_f32q", _p(q), _p(db_codes), _p(r_db), nq, n, D, float(threshold), 0 if splits is None else int(splits),
+         ctypes.c_longlong(capacity), _p(count), _p(out_q), _p(out_d), _p(out_score))
+
+
+def _range_collect(launch_into, nq, n, dev, threshold, capacity, max_pairs):
+    """the host side both threshold searches share.  launch_into(cap, count, oq, od, os_) makes one launch into arrays of `cap`
+    entries (None with cap = 0).  The first launch has room for `capacity` hits (default: four per row, at least 4096); a larger
+    count allocates exactly `count` entries and launches once more -- the predicate is deterministic, the second count equals the
+    first.  max_pairs: a count above it raises ValueError before that allocation.  -> (q int32, d int32, score fp32, count),
+    sorted by (q, d) on the device, so the result does not depend on the order in which the waves appended their hits"""
     threshold = float(threshold)
     if not math.isfinite(threshold):
         raise ValueError(f"range search needs a finite threshold, got {threshold}")
-    nq, n = q_codes.shape[0], db_codes.shape[0]
-    dev = db_codes.device
     if capacity is None:
         capacity = min(nq * n, max(4096, 4 * max(nq, n)))
         if max_pairs is not None:
@@ -1119,7 +1131,7 @@ def search_codes_range(q_codes, r_q, db_codes, r_db, threshold, self_join=False,
         od = torch.empty(cap, dtype=torch.int32, device=dev) if cap else None
         os_ = torch.empty(cap, dtype=torch.float32, device=dev) if cap else None
         count.zero_()
-        search_codes_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join, splits, cap, count, oq, od, os_)
+        launch_into(cap, count, oq, od, os_)
         return oq, od, os_, int(count.item())
 
     oq, od, os_, total = launch(capacity)
@@ -1134,6 +1146,29 @@ def search_codes_range(q_codes, r_q, db_codes, r_db, threshold, self_join=False,
                 torch.empty(0, dtype=torch.float32, device=dev), 0)
     key, order = torch.sort((oq[:total].to(torch.int64) << 32) | od[:total].to(torch.int64))
     return (key >> 32).to(torch.int32), (key & 0xFFFFFFFF).to(torch.int32), os_[:total][order], total
+
+
+def search_codes_range(q_codes, r_q, db_codes, r_db, threshold, self_join=False, capacity=None, splits=None, max_pairs=None):
+    """threshold (range) search over u8 codes (csrc/search.hip, search_range_kernel): every pair whose score -- the fp32 bits
+    search_codes reports -- is >= threshold.  Inputs as for search_codes.  self_join: the queries are the database (pass the same
+    tensors); only pairs d > q are returned and the tiles below the diagonal are not computed.
+    -> (q int32, d int32, score fp32, count), sorted by (q, d) ascending on the device; capacity, the second launch after an
+    overflow and max_pairs are _range_collect's."""
+    def launch_into(cap, count, oq, od, os_):
+        search_codes_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join, splits, cap, count, oq, od, os_)
+
+    return _range_collect(launch_into, q_codes.shape[0], db_codes.shape[0], db_codes.device, threshold, capacity, max_pairs)
+
+
+def search_codes_range_f32q(q, db_codes, r_db, threshold, capacity=None, splits=None, max_pairs=None):
+    """threshold (range) search of fp32 queries over u8 codes (csrc/search.hip, search_range_f32q_kernel): every pair whose score
+    -- the fp32 bits search_codes_f32q reports -- is >= threshold.  Inputs as for search_codes_f32q (D % 64 == 0, D <= 2048).
+    -> (q int32, d int32, score fp32, count), sorted by (q, d) ascending on the device; capacity, the second launch after an
+    overflow and max_pairs are _range_collect's."""
+    def launch_into(cap, count, oq, od, os_):
+        search_codes_range_f32q_launch(q, db_codes, r_db, threshold, splits, cap, count, oq, od, os_)
+
+    return _range_collect(launch_into, q.shape[0], db_codes.shape[0], db_codes.device, threshold, capacity, max_pairs)
 
 
 def jpeg_decode_batch(params, scan, tabs, segs, quant, B, H, W, total_blocks, plane_bytes, max_blocks, out=None, check=True):

@@ -10,7 +10,9 @@ writes the u8 codes themselves (codes.npy), which `--codes` (on all three query 
 i8 kernels (csrc/search.hip): integer inner products, no fp32 database and no score matrix on the device.  A u8 query code is used
 as it is; an fp32 text / image vector is taken to 2^-22 fixed point and searched as three i8 digit planes.
 `duplicates --threshold T` lists the groups of rows whose codes score >= T against each other (a threshold search over the same
-codes, each pair computed once), and `query-c2df --codes --min_score T` returns every hit above T instead of the top k.
+codes, each pair computed once), and `--codes --min_score T` on any of the three query commands returns every hit with score >= T
+instead of the top k (`--max_pairs` bounds their number): u8 queries through the range kernel, text / image vectors through its
+fp32-query sibling.
 `build-images` (the reference's `build.py build-images`) indexes a folder of ordinary images with the CLIP tower alone: no codec, no
 container.  The decoded bytes go to the tower as they are (clip.py preprocess_u8), and the index directory carries the same files
 as `build`, the tower's own u8 codes included."""
@@ -254,11 +256,9 @@ class CodeIndex:
         s, i = ops.search_codes(torch.from_numpy(q).to(db.device), torch.from_numpy(code_rnorm(q)).to(db.device), db, r_db, k)
         return s.cpu().numpy(), i.cpu().numpy()
 
-    def search_vectors(self, q, k):
-        """q (nq, D) fp32 unit vectors (text / image queries), numpy or a tensor on either side -> (scores (nq,k) fp32, indices
-        (nq,k) int32), one fused launch.  Refused: non-finite values, a row longer than 1 + 1e-3 (not a unit query: the fixed-point
-        range is [-1, 1]), another dim, and an index of dim > 2048, which only the fp32 files can serve"""
-        from . import ops
+    def _unit_queries(self, q, what):
+        """the input checks of the fp32-query searches, all before anything is loaded or launched -> (nq, D) fp32 tensor, on
+        whichever side it came from"""
         if self.dim > self.MAX_DIM_F32Q:
             raise ValueError(f"fp32 queries against a code index need dim <= {self.MAX_DIM_F32Q}, this one has {self.dim}: use the fp32 "
                              "index files (faiss.index + paths.json or index.faiss + ids.txt), i.e. the query without --codes")
@@ -270,13 +270,38 @@ class CodeIndex:
             raise ValueError("query vectors hold non-finite values")
         longest = float(t.double().norm(dim=1).max()) if t.shape[0] else 0.0
         if longest > self.MAX_QUERY_NORM:
-            raise ValueError(f"query of l2 norm {longest:.6g}: search_vectors takes unit vectors (norm <= {self.MAX_QUERY_NORM})")
+            raise ValueError(f"query of l2 norm {longest:.6g}: {what} takes unit vectors (norm <= {self.MAX_QUERY_NORM})")
+        return t
+
+    def search_vectors(self, q, k):
+        """q (nq, D) fp32 unit vectors (text / image queries), numpy or a tensor on either side -> (scores (nq,k) fp32, indices
+        (nq,k) int32), one fused launch.  Refused: non-finite values, a row longer than 1 + 1e-3 (not a unit query: the fixed-point
+        range is [-1, 1]), another dim, and an index of dim > 2048, which only the fp32 files can serve"""
+        from . import ops
+        t = self._unit_queries(q, "search_vectors")
         if self._dev is None:
             self.to()
         db, r_db = self._dev
         k = max(1, min(int(k), len(self)))
         s, i = ops.search_codes_f32q(t.to(db.device).contiguous(), db, r_db, k)
         return s.cpu().numpy(), i.cpu().numpy()
+
+    def range_search_vectors(self, q, threshold, max_pairs=None):
+        """every database row whose score against an fp32 unit query is >= threshold (fp32, the bits `search_vectors` reports), the
+        FAISS range_search shape: q as for search_vectors -> (lims (nq + 1,) int64, scores fp32, indices int32); query j owns
+        lims[j]:lims[j + 1], database index ascending.  One fused launch (ops.search_codes_range_f32q), no top-k and no limit on
+        the hits per query.  Refused, before anything is loaded or launched: what search_vectors refuses and a non-finite threshold;
+        more than max_pairs hits is a ValueError naming the count"""
+        from . import ops
+        thr = finite_threshold(threshold)
+        t = self._unit_queries(q, "range_search_vectors")
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        hq, hd, hs, _ = ops.search_codes_range_f32q(t.to(db.device).contiguous(), db, r_db, thr, max_pairs=max_pairs)
+        lims = np.zeros(t.shape[0] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(hq.cpu().numpy(), minlength=t.shape[0]), out=lims[1:])
+        return lims, hs.cpu().numpy(), hd.cpu().numpy()
 
     def range_search(self, q_codes, threshold, max_pairs=None):
         """every database row whose score against a query is >= threshold (fp32, the bits `search` reports), the FAISS range_search
@@ -505,9 +530,17 @@ def build_index_from_images(image_dir, index_dir, clip_ckpt=None, small=False, b
     return rec
 
 
-def _query_codes(index_dir, c2df, topk, min_score=None):
+def _hits_by_score(ci, lims, s, idx, j):
+    """query j's share of a range_search result as the CLI prints it: score descending, ties to the lower index"""
+    sj, ij = s[lims[j]:lims[j + 1]], idx[lims[j]:lims[j + 1]]
+    order = np.lexsort((ij, -sj))
+    return [{"path": ci.ids[i], "score": float(v)} for i, v in zip(ij[order], sj[order])]
+
+
+def _query_codes(index_dir, c2df, topk, min_score=None, max_pairs=None):
     """`query-c2df --codes`: a file -> result list; a directory -> {path: result list}, all queries in one fused call.  min_score:
-    every hit with score >= min_score instead of the top k, score descending, ties to the lower index"""
+    every hit with score >= min_score instead of the top k, score descending, ties to the lower index; more than max_pairs of them
+    is a ValueError naming the count"""
     ci = CodeIndex.load(index_dir)
     src = Path(c2df)
     files = sorted(src.glob("**/*.c2df")) if src.is_dir() else [src]
@@ -518,12 +551,8 @@ def _query_codes(index_dir, c2df, topk, min_score=None):
         s, idx = ci.search(codes, topk)
         res = [[{"path": ci.ids[i], "score": float(v)} for i, v in zip(idx[j], s[j])] for j in range(len(files))]
     else:
-        lims, s, idx = ci.range_search(codes, min_score)
-        res = []
-        for j in range(len(files)):
-            sj, ij = s[lims[j]:lims[j + 1]], idx[lims[j]:lims[j + 1]]
-            order = np.lexsort((ij, -sj))
-            res.append([{"path": ci.ids[i], "score": float(v)} for i, v in zip(ij[order], sj[order])])
+        lims, s, idx = ci.range_search(codes, min_score, max_pairs=max_pairs)
+        res = [_hits_by_score(ci, lims, s, idx, j) for j in range(len(files))]
     return {str(f): r for f, r in zip(files, res)} if src.is_dir() else res[0]
 
 
@@ -541,9 +570,9 @@ def _query_vector(args):
         csd = load_state(args.clip_ckpt, W.clip_spec, ccfg, 4321)
         return ClipCodec(csd, ccfg, "cuda:0").image_to_unit_vec(load_image(args.image))[None, :]
     from .clip import ClipTextHIP
-    toks = tokenize(args.text, CLIP_B32.ctx, args.token_ids)
-    tsd = load_state(args.clip_ckpt, W.clip_text_spec, CLIP_B32, 4321)
-    return encode_text(toks, ClipTextHIP(tsd, CLIP_B32, "cuda:0"))
+    toks = tokenize(args.text, ccfg.ctx, args.token_ids)
+    tsd = load_state(args.clip_ckpt, W.clip_text_spec, ccfg, 4321)
+    return encode_text(toks, ClipTextHIP(tsd, ccfg, "cuda:0"))
 
 
 def write_duplicates(index_dir, threshold, out=None, max_pairs=1 << 24):
@@ -575,6 +604,18 @@ _THRESHOLD_HELP = ("score threshold (cosine of the dequantised codes, fp32).  Me
                    "picture")
 
 
+_VECTOR_THRESHOLD_HELP = ("with --codes: every hit with score >= MIN_SCORE instead of the top k (--topk is ignored then), score "
+                          "descending, ties to the lower index.  The score is the cosine between the query vector and the dequantised "
+                          "code, fp32.  ")
+_TEXT_THRESHOLD_HELP = (_VECTOR_THRESHOLD_HELP + "Which scores text queries reach against image codes has not been measured here: there "
+                        "is no recommended value, look at the top-k scores of a few queries of your own first")
+_IMAGE_THRESHOLD_HELP = (_VECTOR_THRESHOLD_HELP + "Measured on the u8 codes at D = 512, and valid for an image query only where its "
+                         "vector is (nearly) the dequantised code of an indexed picture: identical codes score 1 +- 2^-23 (about 0.99999 "
+                         "selects them), re-encodes of one picture 0.98-0.99.  Scores of merely similar pictures have not been measured "
+                         "here")
+_MAX_PAIRS_HELP = "with --min_score: refuse (and name the count) when more hits than this pass the threshold"
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours / duplicates")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -587,6 +628,8 @@ def main(argv=None):
         if name == "query-image":
             p.add_argument("--small", action="store_true", help="TINY test tower (an index built with --small)")
         if name == "query-text":
+            p.add_argument("--small", action="store_true", help="TINY test text tower (an index built with --small); needs --token_ids "
+                           "within its vocabulary and context")
             p.add_argument("--token_ids", type=str, default=None, help="comma-separated BPE ids (offline tokenizer bypass)")
         if name == "query-c2df":
             p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused i8 kernel; "
@@ -596,6 +639,8 @@ def main(argv=None):
         else:
             p.add_argument("--codes", action="store_true", help="search the u8 code index (codes.npy) with the fused fp32-query "
                            "kernel instead of the fp32 index files")
+            p.add_argument("--min_score", type=float, default=None, help=_TEXT_THRESHOLD_HELP if name == "query-text" else _IMAGE_THRESHOLD_HELP)
+        p.add_argument("--max_pairs", type=int, default=1 << 24, help=_MAX_PAIRS_HELP)
     p = sub.add_parser("build", help="index directory from a directory of .c2df containers")
     p.add_argument("--c2df_dir", type=Path, required=True)
     p.add_argument("--index_dir", type=Path, required=True)
@@ -660,10 +705,14 @@ def main(argv=None):
                 out.close()
         return 0
     if args.cmd == "query-c2df" and args.codes:
-        print(json.dumps(_query_codes(args.index_dir, args.c2df, args.topk, args.min_score), ensure_ascii=False, indent=2))
+        print(json.dumps(_query_codes(args.index_dir, args.c2df, args.topk, args.min_score, args.max_pairs), ensure_ascii=False, indent=2))
         return 0
     if args.codes:   # text / image vector against the u8 codes
         ci = CodeIndex.load(args.index_dir)
+        if args.min_score is not None:      # every hit above the threshold, in the shape of `query-c2df --codes --min_score`
+            lims, sim, idx = ci.range_search_vectors(_query_vector(args), args.min_score, max_pairs=args.max_pairs)
+            print(json.dumps(_hits_by_score(ci, lims, sim, idx, 0), ensure_ascii=False, indent=2))
+            return 0
         sim, idx = ci.search_vectors(_query_vector(args), args.topk)
         print(json.dumps([{"path": ci.ids[i], "score": float(v)} for i, v in zip(idx[0], sim[0]) if i != -1], ensure_ascii=False, indent=2))
         return 0

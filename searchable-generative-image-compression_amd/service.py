@@ -60,6 +60,8 @@ def ndjson(obj):
 
 
 class ResidentService:
+    MAX_RANGE_HITS = 1 << 20     # a threshold search (min_score) that finds more is reported as an error naming the count
+
     def __init__(self, ckpt_path=None, clip_ckpt=None, device="cuda:0", small=False, index_dir=None, preview_cache=None,
                  media_roots=None, code_index=False):
         from . import weights as W
@@ -243,13 +245,43 @@ class ResidentService:
                 s, i = s.cpu().numpy(), i.cpu().numpy()
         return [{"path": ids[j], "score": float(s[0, r])} for r, j in enumerate(i[0]) if j != -1]
 
-    def _stream(self, start_meta, make_query, topk, index_dir):
-        """the NDJSON protocol shared by the three search endpoints (webapp.py:236-255)"""
+    def _code_index(self, index_dir):
+        """the resident CodeIndex and its ids, or the error of a threshold search where there is none"""
+        _, ids, ci = self._load_index(index_dir)
+        if ci is None:
+            raise ValueError("min_score needs the u8 code index: a service built with code_index=True and an index directory "
+                             "that holds codes.npy + ids.txt")
+        return ci, ids
+
+    def _search_range(self, make_query, min_score, index_dir):
+        """every row of the resident code index with score >= min_score, score descending, ties to the lower index; the query as
+        for _search.  Refused before the query is made: a non-finite value, no code index; afterwards more than MAX_RANGE_HITS hits"""
+        from .search import finite_threshold
+        t = finite_threshold(min_score, "min_score")
+        ci, ids = self._code_index(index_dir)
+        q = make_query()
+        with self._lock:
+            fn = ci.range_search if np.asarray(q).dtype == np.uint8 else ci.range_search_vectors
+            _, s, i = fn(q, t, max_pairs=self.MAX_RANGE_HITS)
+        return [{"path": ids[int(i[r])], "score": float(s[r])} for r in np.lexsort((i, -s))]
+
+    def _stream(self, start_meta, make_query, topk, index_dir, min_score=None):
+        """the NDJSON protocol shared by the three search endpoints (webapp.py:236-255); min_score: a threshold search instead
+        of the top k, named in the start line"""
         t0 = time.perf_counter()
         ms = lambda: int((time.perf_counter() - t0) * 1000)   # noqa: E731
-        yield ndjson(dict({"type": "meta", "stage": "start"}, **start_meta, topk=int(topk)))
+        start = dict({"type": "meta", "stage": "start"}, **start_meta, topk=int(topk))
+        if min_score is not None:      # as given when it is not a finite number (the error line follows): NaN is not JSON
+            try:
+                start["min_score"] = float(min_score) if np.isfinite(float(min_score)) else str(min_score)
+            except (TypeError, ValueError):
+                start["min_score"] = str(min_score)
+        yield ndjson(start)
         try:
-            items = self._search(make_query(), topk, index_dir)
+            if min_score is None:
+                items = self._search(make_query(), topk, index_dir)
+            else:
+                items = self._search_range(make_query, min_score, index_dir)
             yield ndjson({"type": "meta", "stage": "searched", "count": len(items), "elapsed_ms": ms()})
             for it in items:
                 yield ndjson({"type": "item", "path": it["path"], "score": float(it["score"]),
@@ -259,7 +291,8 @@ class ResidentService:
             yield ndjson({"type": "error", "detail": str(e)})
 
     def search_text(self, body):
-        """POST /search/stream/text (webapp.py:228-257); body = {"text", "topk", "index_dir"[, "token_ids"]}"""
+        """POST /search/stream/text (webapp.py:228-257); body = {"text", "topk", "index_dir"[, "token_ids"][, "min_score"]};
+        min_score: every hit with score >= it instead of the top k"""
         text = (body.get("text") or "").strip()
         topk = int(body.get("topk") or 10)
         if not text:
@@ -274,26 +307,27 @@ class ResidentService:
                     self._text = ClipTextHIP(self._csd, self.ccfg, self.device)
                 return encode_text(toks, self._text)
 
-        return self._stream({"query_type": "text", "query": text}, query, topk, body.get("index_dir"))
+        return self._stream({"query_type": "text", "query": text}, query, topk, body.get("index_dir"), body.get("min_score"))
 
-    def search_image(self, filename, data, topk=10, index_dir=None):
-        """POST /search/stream/image (webapp.py:259-287)"""
+    def search_image(self, filename, data, topk=10, index_dir=None, min_score=None):
+        """POST /search/stream/image (webapp.py:259-287); min_score: every hit with score >= it instead of the top k"""
         def query():
             img = self._image_from_bytes(data)
             with self._lock:
                 return self.clipc.image_to_unit_vec(img)[None, :]
 
-        return self._stream({"query_type": "image", "filename": filename}, query, topk, index_dir)
+        return self._stream({"query_type": "image", "filename": filename}, query, topk, index_dir, min_score)
 
-    def search_c2df(self, filename, data, topk=10, index_dir=None):
-        """POST /search/stream/c2df (webapp.py:289-317): needs no model -- the query is the embedded CLIP code"""
+    def search_c2df(self, filename, data, topk=10, index_dir=None, min_score=None):
+        """POST /search/stream/c2df (webapp.py:289-317): needs no model -- the query is the embedded CLIP code; min_score: every hit
+        with score >= it instead of the top k"""
         def query():
             from .search import embedded_clip_codes, embedded_clip_vector
             if self._load_index(index_dir)[2] is not None:             # code index: the embedded u8 code is the query as it is
                 return embedded_clip_codes(data)[0][None, :]
             return embedded_clip_vector(data)[0][None, :]
 
-        return self._stream({"query_type": "c2df", "filename": filename}, query, topk, index_dir)
+        return self._stream({"query_type": "c2df", "filename": filename}, query, topk, index_dir, min_score)
 
 
 # ---------------------------------------------------------------------- optional stdlib transport
@@ -349,7 +383,8 @@ def http_handler(service):
                     return self._send_stream(service.search_text(body))
                 if method == "POST" and u.path in ("/search/stream/image", "/search/stream/c2df"):
                     fn = service.search_image if u.path.endswith("image") else service.search_c2df
-                    return self._send_stream(fn(*self._upload(), topk=int(qs.get("topk", 10)), index_dir=qs.get("index_dir")))
+                    return self._send_stream(fn(*self._upload(), topk=int(qs.get("topk", 10)), index_dir=qs.get("index_dir"),
+                                                min_score=qs.get("min_score")))
                 raise ServiceError(404, "Not Found")
             except ServiceError as e:
                 self._send(Response(json.dumps({"detail": e.detail}).encode(), "application/json", status=e.status))

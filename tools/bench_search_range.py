@@ -15,7 +15,16 @@ the run.
           search's own two repeats show.  Both read n D bytes once: the share of 6.3 TB/s is given for each.
   dense   T = -2, nq = 64, n = 1e5: every pair is a hit, 6.4e6 entries; output-bound, no pass mark.
 
-    python tools/bench_search_range.py [--quick] [--out profiles/search_range.txt]"""
+--vectors runs the fp32-query points instead (search_range_f32q_kernel: ops.search_codes_range_f32q), same protocol:
+
+  vrange  search_codes_range_f32q at n = 1e6, nq in {1, 16}; the queries are the dequantised unit vectors of corpus rows that have
+          a planted near-duplicate, so a handful of hits exist.  Counterpart: search_codes_f32q with k = 10 on the same inputs, what
+          top-k-and-filter costs.  Whole wrapper and "counter reset + kernel alone", as for `range`.  Required: not slower than the
+          counterpart beyond the counterpart's own repeat-to-repeat spread.
+  vdense  T = -2, nq = 32, n = 1e5: 3.2e6 entries; output-bound, no pass mark.
+
+    python tools/bench_search_range.py [--quick] [--out profiles/search_range.txt]
+    python tools/bench_search_range.py --vectors [--quick] [--out profiles/search_range_f32q.txt]"""
 import argparse
 import json
 import os
@@ -135,6 +144,64 @@ def point_dense(n, nq):
             "note": "range_ms: the default capacity overflows, so the wrapper launches twice, then sorts 6.4e6 keys"}
 
 
+def unit_queries(db, rows):
+    """the dequantised unit vectors of corpus rows (search.codes_to_unit's arithmetic, on the device) -> (len(rows), D) fp32"""
+    v = (db[rows].float() / 255.0) * 2.0 - 1.0
+    return (v / v.norm(dim=1, keepdim=True)).contiguous()
+
+
+def point_vrange(n, nq):
+    import torch
+    from sgic_amd import ops
+    db, r = corpus(n, 42)
+    q = unit_queries(db, torch.arange(nq, device=DEV) * 100)     # corpus rows that each have a planted near-duplicate
+    cap = 4096
+    count = torch.zeros(1, dtype=torch.int64, device=DEV)
+    oq, od = torch.empty(cap, dtype=torch.int32, device=DEV), torch.empty(cap, dtype=torch.int32, device=DEV)
+    os_ = torch.empty(cap, dtype=torch.float32, device=DEV)
+
+    def kernel():
+        count.zero_()
+        ops.search_codes_range_f32q_launch(q, db, r, THRESHOLD, None, cap, count, oq, od, os_)
+
+    wrapper = lambda: ops.search_codes_range_f32q(q, db, r, THRESHOLD)     # noqa: E731
+    topk = lambda: ops.search_codes_f32q(q, db, r, 10)                     # noqa: E731
+    hits = wrapper()[3]
+    for fn in (kernel, topk, wrapper, topk):
+        fn()
+    tw, tk, tt = alternate((wrapper, kernel, topk), 10)
+    spread = max(tt) - min(tt)
+    share = lambda ms: n * DIM / (ms * 1e-3) / HBM_BYTES_PER_S   # noqa: E731
+    return {"what": "search_codes_range_f32q vs search_codes_f32q k = 10", "n": n, "nq": nq, "D": DIM, "T": THRESHOLD, "hits": hits,
+            "iters": 10, "range_ms": tw, "range_kernel_ms": tk, "topk_ms": tt, "topk_spread_ms": spread,
+            "range_share_of_hbm": share(min(tw)), "range_kernel_share_of_hbm": share(min(tk)), "topk_share_of_hbm": share(min(tt)),
+            "required": "range not slower than the top-k search beyond its own spread: min(range) <= min(topk) + spread",
+            "met_wrapper": bool(min(tw) <= min(tt) + spread), "met_kernel": bool(min(tk) <= min(tt) + spread)}
+
+
+def point_vdense(n, nq):
+    import torch
+    from sgic_amd import ops
+    db, r = corpus(n, 9)
+    q = unit_queries(db, torch.arange(nq, device=DEV))
+    cap = nq * n
+    count = torch.zeros(1, dtype=torch.int64, device=DEV)
+    oq, od = torch.empty(cap, dtype=torch.int32, device=DEV), torch.empty(cap, dtype=torch.int32, device=DEV)
+    os_ = torch.empty(cap, dtype=torch.float32, device=DEV)
+
+    def kernel():
+        count.zero_()
+        ops.search_codes_range_f32q_launch(q, db, r, -2.0, None, cap, count, oq, od, os_)
+
+    wrapper = lambda: ops.search_codes_range_f32q(q, db, r, -2.0)          # noqa: E731
+    assert wrapper()[3] == cap
+    kernel()
+    tw, tk = alternate((wrapper, kernel), 3)
+    return {"what": "fp32 queries, dense emission, T = -2 (output-bound, no pass mark)", "n": n, "nq": nq, "D": DIM, "entries": cap,
+            "range_ms": tw, "range_kernel_ms": tk, "kernel_output_GB_per_s": cap * 12 / (min(tk) * 1e-3) / 1e9,
+            "note": "range_ms: the default capacity overflows, so the wrapper launches twice, then sorts the keys"}
+
+
 def run_point(spec):
     import torch
     sys.path.insert(0, ROOT)
@@ -142,7 +209,7 @@ def run_point(spec):
     if not torch.cuda.is_available():
         raise SystemExit("bench_search_range needs the GPU: there is nothing to time without one")
     kind, args = spec.split(":")[0], [int(a) for a in spec.split(":")[1:]]
-    rec = {"dup": point_dup, "range": point_range, "dense": point_dense}[kind](*args)
+    rec = {"dup": point_dup, "range": point_range, "dense": point_dense, "vrange": point_vrange, "vdense": point_vdense}[kind](*args)
     rec["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(rec), flush=True)
     return 0
@@ -151,7 +218,8 @@ def run_point(spec):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small sizes only (a rehearsal of the protocol, not a measurement)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "search_range.txt"))
+    ap.add_argument("--vectors", action="store_true", help="the fp32-query points (vrange, vdense) instead of the u8 ones")
+    ap.add_argument("--out", default=None, help="default: profiles/search_range.txt, with --vectors profiles/search_range_f32q.txt")
     ap.add_argument("--point", default=None, help="run one point in this process (what the parent starts, under its time limit)")
     ap.add_argument("--limit", type=int, default=240, help="seconds each point may take")
     args = ap.parse_args(argv)
@@ -159,6 +227,10 @@ def main(argv=None):
         return run_point(args.point)
     s = 100 if args.quick else 1
     points = [f"dup:{100000 // s}", f"range:{1000000 // s}:1", f"range:{1000000 // s}:16", f"dense:{100000 // s}:64"]
+    if args.vectors:
+        points = [f"vrange:{1000000 // s}:1", f"vrange:{1000000 // s}:16", f"vdense:{100000 // s}:32"]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "search_range_f32q.txt" if args.vectors else "search_range.txt")
     lines = [f"# tools/bench_search_range.py; D={DIM} T={THRESHOLD}; ms per call, two repeats each, the new call and its counterpart "
              "alternating in one process per point"]
     for p in points:
