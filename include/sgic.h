@@ -386,6 +386,29 @@ int sgic_search_range_f32q(const float *d_q, const uint8_t *d_db, const float *d
                            int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,
                            float *d_out_score, sgic_stream_t stream);
 
+/* Clustering over the same u8 codes (CodeIndex.assign / kmeans): for every database row the best of K fp32 centroids.  d_cent
+ * (K, D) fp32 rows of norm <= 1 and d_db (n, D) u8, both 16-byte aligned.  The centroid goes to 2^-22 fixed point and three balanced
+ * base-256 digit planes exactly as the query of sgic_search_codes_f32q (Q, d0, d1, d2, S_p and the int64
+ * M = 2 (65536 S_2 + 256 S_1 + S_0) + sum_j Q_j are those of its comment; a NaN coordinate gives 0).  For every row d:
+ *   d_out_c[d] = the centroid with the largest M(c, d), equal M -> the lower centroid index;   d_out_M[d] = that M.
+ * r_d > 0 is common to all centroids of a row, so the order of M is the order of the scores; the device runs no float compare, add,
+ * root or division, and the caller derives score = (float32(M) * r_d) * 2^-22, the bits sgic_search_codes_f32q reports for that
+ * (vector, row) pair.  A pre-pass writes the planes in MFMA fragment order and sum Q per centroid into d_work (16-byte aligned;
+ * sgic_assign_codes_f32c_work_bytes, host-only, takes no stream: 16 ceil(K / 16) (3 D + 8) bytes).  D % 64 == 0, D <= 2048,
+ * 1 <= K <= 65536, n >= 1; anything else, a null or misaligned pointer or a workspace that is too small is SGIC_EINVAL. */
+int sgic_assign_codes_f32c_work_bytes(int K, int D, size_t *bytes);
+int sgic_assign_codes_f32c(const float *d_cent, const uint8_t *d_db, int K, int n, int D, uint8_t *d_work, size_t work_bytes,
+                           int32_t *d_out_c, int64_t *d_out_M, sgic_stream_t stream);
+
+/* The exact integer sums of a partition of the codes: d_sums[c][j] += sum over the rows d of cluster c of (2 d_db[d][j] - 255),
+ * d_counts[c] += the number of those rows (both int64; the CALLER zeroes them).  The caller passes the partition sorted by cluster:
+ * d_order (n) int64, a permutation of the rows, and d_sorted_assign (n) int32, the cluster of row d_order[i], ascending.  A cluster
+ * id outside [0, K) or a row outside [0, n) is skipped, never written.  Integer adds only (int32 registers, LDS, one 64-bit
+ * atomic add per coordinate and run): the result is exact and does not depend on the schedule.  D % 16 == 0, D <= 4096; d_db
+ * 16-byte aligned; anything else is SGIC_EINVAL. */
+int sgic_cluster_sums_u8(const uint8_t *d_db, const int64_t *d_order, const int32_t *d_sorted_assign, int n, int D, int K,
+                         int64_t *d_sums, int64_t *d_counts, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

@@ -872,3 +872,300 @@ extern "C" int sgic_search_codes_f32q(const float *d_q, const uint8_t *d_db, con
   }
   return SGIC_OK;
 }
+
+// Clustering over the same codes (CodeIndex.assign / kmeans): for every database row the best of K fp32 centroids, and the exact
+// integer sums of a partition.
+//
+// sgic_assign_codes_f32c.  M(c, d) is search_f32q_kernel's integer: the centroid goes through quantise16 into three balanced
+// base-256 digit planes, S_p = sum d_p (c_d - 128) comes from the i8 MFMA, M = 2 (65536 S_2 + 256 S_1 + S_0) + sum Q in int64.
+// r_d > 0 is common to all centroids of a row, so the argmax runs on M itself: larger M, equal M -> lower centroid index.  No float
+// compare, add, root or division; the caller derives the score (float32(M) * r_d) * 2^-22.
+//   assign_prepare_kernel   one workgroup per tile of 16 centroids: the three planes in MFMA fragment order ([tile][plane][step][lane]
+//                           16-byte fragments, lane l: centroid l & 15, coordinates 64 step + 16 (l >> 4) ..+15) and sum Q (int64) per
+//                           centroid, into the workspace.  Slots >= K repeat centroid K - 1 and are masked by index below.
+//   assign_codes_kernel     a workgroup of four waves owns 256 database rows, a wave four 16-row tiles.  REG (D = 512): a wave keeps
+//                           its tiles' 32 fragments in registers for the whole kernel, so the codes are read from HBM once however
+//                           large K is; otherwise the fragments are re-read (L2) per centroid tile.  Centroid tiles are staged in
+//                           LDS `ct` at a time by straight 16-byte copies; one LDS fragment read feeds four MFMAs.  In C, rows are
+//                           centroids (4 (l >> 4) + reg), columns database rows (l & 15): a lane sees its centroids in ascending
+//                           order and keeps the best with a strict >; two cross-lane steps (xor 16, 32) with the full comparator
+//                           finish a row.  Rows >= n are clamped for the loads and masked for the stores.  No atomics.
+//
+// sgic_cluster_sums_u8.  The caller sorts the rows by cluster (stable) and passes the order and the sorted cluster ids.  A workgroup
+// takes 1024 consecutive sorted positions and walks them run by run (a run: one cluster's members inside the slice; its end is found
+// by bisection of the sorted ids).  Thread (m, chunk) gathers the 16-byte chunk `chunk` of members m, m + ML, ... and adds the bytes
+// in int32 registers (255 * 1024 < 2^31); the member lanes are summed through LDS and each coordinate takes one 64-bit atomicAdd of
+// 2 sum c - 255 members.  Integer adds commute, so the result does not depend on the schedule.
+namespace {
+
+constexpr int kAssignR = 4;                      // 16-row database tiles per wave
+constexpr int kAssignRows = 4 * 16 * kAssignR;   // database rows per workgroup
+constexpr int kAssignMaxK = 65536;
+constexpr int kAssignMaxCt = 8;                  // centroid tiles staged per round, at most
+constexpr int kAssignStage = 6;                  // 16-byte fragments a thread has in flight while staging (one D = 512 tile: 6 per thread)
+constexpr int kSumsSlice = 1024;                 // sorted positions per workgroup
+constexpr int kSumsMaxDim = 4096;                // 256 threads x 16 bytes
+
+__global__ __launch_bounds__(256) void assign_prepare_kernel(const float *__restrict__ cent, int K, int D, v4i *__restrict__ planes,
+                                                             long long *__restrict__ sumq) {
+  __shared__ unsigned long long sq[16];
+  const int tid = threadIdx.x, tile = blockIdx.x;
+  const int frags = (D >> 6) * 64;   // fragments per plane of one tile
+  if (tid < 16) sq[tid] = 0;
+  __syncthreads();
+  v4i *dst = planes + (size_t)tile * 3 * frags;
+  for (int i = tid; i < frags; i += 256) {   // sixteen coordinates -> one fragment in each plane per (step, lane)
+    const int ln = i & 63, step = i >> 6;
+    int ci = tile * 16 + (ln & 15);
+    ci = ci < K ? ci : K - 1;
+    v4i p0, p1, p2;
+    const int s = quantise16(reinterpret_cast<const float4 *>(cent + (size_t)ci * D + 64 * step + 16 * (ln >> 4)), p0, p1, p2);
+    atomicAdd(&sq[ln & 15], (unsigned long long)(long long)s);
+    dst[i] = p0;
+    dst[frags + i] = p1;
+    dst[2 * frags + i] = p2;
+  }
+  __syncthreads();
+  if (tid < 16) sumq[tile * 16 + tid] = (long long)sq[tid];
+}
+
+template <bool REG>
+__global__ __launch_bounds__(256, 2) void assign_codes_kernel(const v4i *__restrict__ planes, const long long *__restrict__ sumq,
+                                                              const uint8_t *__restrict__ db, int K, int n, int D, int ct,
+                                                              int *__restrict__ out_c, long long *__restrict__ out_M) {
+  constexpr int R = kAssignR;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int steps = REG ? 8 : D >> 6;
+  const int tiles = (K + 15) >> 4;
+  const int tfrag = 3 * steps * 64;          // fragments per centroid tile
+  v4i *A = reinterpret_cast<v4i *>(smem);   // [ct][3 planes][steps][64 lanes] fragments
+  long long *sq = reinterpret_cast<long long *>(smem + (size_t)ct * tfrag * 16);   // [ct][16] sum Q
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long row0 = (long long)blockIdx.x * kAssignRows + wave * (16 * R) + (lane & 15);   // this lane's row of tile r: row0 + 16 r
+  const uint4 *bp[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const long long row = row0 + 16 * r;
+    bp[r] = reinterpret_cast<const uint4 *>(db + (size_t)(row < n ? row : n - 1) * D) + (lane >> 4);
+  }
+  v4i b[R][REG ? 8 : 1];
+  if (REG) {
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+      for (int s = 0; s < 8; s++) b[r][s] = to_i8x16(bp[r][s * 4]);
+  }
+  long long best[R];
+  int bidx[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    best[r] = (long long)0x8000000000000000ull;   // below every M; a lane without a live centroid keeps it and loses the reduction
+    bidx[r] = 0x7fffffff;
+  }
+
+  for (int t0 = 0; t0 < tiles; t0 += ct) {
+    const int nt = tiles - t0 < ct ? tiles - t0 : ct;
+    __syncthreads();   // the previous round's fragments have been read
+    const v4i *src = planes + (size_t)t0 * tfrag;
+    for (int i0 = tid; i0 < nt * tfrag; i0 += 256 * kAssignStage) {   // kAssignStage loads in flight, then their LDS writes
+      v4i f[kAssignStage];
+#pragma unroll
+      for (int u = 0; u < kAssignStage; u++) {
+        const int i = i0 + 256 * u;
+        f[u] = src[i < nt * tfrag ? i : i0];
+      }
+#pragma unroll
+      for (int u = 0; u < kAssignStage; u++) {
+        const int i = i0 + 256 * u;
+        if (i < nt * tfrag) A[i] = f[u];
+      }
+    }
+    if (tid < nt * 16) sq[tid] = sumq[t0 * 16 + tid];
+    __syncthreads();
+    for (int c = 0; c < nt; c++) {
+      v4i acc[R][3];
+#pragma unroll
+      for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int p = 0; p < 3; p++) acc[r][p] = v4i{0, 0, 0, 0};
+      const v4i *Ac = A + c * tfrag + lane;
+      if (REG) {
+#pragma unroll
+        for (int s = 0; s < 8; s++)
+#pragma unroll
+          for (int p = 0; p < 3; p++) {
+            const v4i a = Ac[(p * 8 + s) * 64];
+#pragma unroll
+            for (int r = 0; r < R; r++) acc[r][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[r][s], acc[r][p], 0, 0, 0);
+          }
+      } else {
+        for (int s = 0; s < steps; s++) {
+#pragma unroll
+          for (int r = 0; r < R; r++) b[r][0] = to_i8x16(bp[r][s * 4]);
+#pragma unroll
+          for (int p = 0; p < 3; p++) {
+            const v4i a = Ac[(p * steps + s) * 64];
+#pragma unroll
+            for (int r = 0; r < R; r++) acc[r][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[r][0], acc[r][p], 0, 0, 0);
+          }
+        }
+      }
+      const int c0 = (t0 + c) * 16 + 4 * (lane >> 4);   // this lane's centroids of the tile: c0 + j, ascending
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const long long sj = sq[c * 16 + 4 * (lane >> 4) + j];
+        if (c0 + j < K) {   // pad slots never win: masked by index, not by value
+#pragma unroll
+          for (int r = 0; r < R; r++) {
+            const long long M = 2 * (65536LL * acc[r][2][j] + 256LL * acc[r][1][j] + acc[r][0][j]) + sj;
+            if (M > best[r]) {
+              best[r] = M;
+              bidx[r] = c0 + j;
+            }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+#pragma unroll
+    for (int m = 16; m <= 32; m <<= 1) {   // the four lane groups of a column: larger M, else lower index
+      const long long om = __shfl_xor(best[r], m);
+      const int oi = __shfl_xor(bidx[r], m);
+      if (om > best[r] || (om == best[r] && oi < bidx[r])) {
+        best[r] = om;
+        bidx[r] = oi;
+      }
+    }
+    const long long row = row0 + 16 * r;
+    if (lane < 16 && row < n) {
+      out_c[row] = bidx[r];
+      out_M[row] = best[r];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cluster_sums_kernel(const uint8_t *__restrict__ codes, const long long *__restrict__ order,
+                                                           const int *__restrict__ sorted_assign, int n, int D, int K,
+                                                           unsigned long long *__restrict__ sums, unsigned long long *__restrict__ counts) {
+  __shared__ __attribute__((aligned(16))) int red[256 * 16];   // [member lane][D]
+  const int tid = threadIdx.x;
+  const int chunks = D >> 4;          // 16-byte chunks per row, at most 256
+  const int ML = 256 / chunks;        // member lanes
+  const int m = tid / chunks, ch = tid - m * chunks;
+  long long p = (long long)blockIdx.x * kSumsSlice;
+  const long long end = p + kSumsSlice < n ? p + kSumsSlice : n;
+  while (p < end) {   // p, c, q are the same in every thread: the barriers below are taken by all
+    const int c = sorted_assign[p];
+    long long lo = p + 1, hi = end;   // the run's end: the first position after p whose id is not c
+    while (lo < hi) {
+      const long long mid = (lo + hi) >> 1;
+      if (sorted_assign[mid] == c) lo = mid + 1; else hi = mid;
+    }
+    const long long q = lo;
+    if (c >= 0 && c < K) {   // the caller has checked the ids; an id outside [0, K) is skipped, never written
+      const int mlim = q - p < ML ? (int)(q - p) : ML;
+      if (m < mlim) {
+        unsigned acc[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) acc[j] = 0;
+        int members = 0;
+        for (long long i = p + m; i < q; i += ML) {
+          const long long row = order[i];
+          if ((unsigned long long)row >= (unsigned long long)n) continue;
+          const uint4 v = *reinterpret_cast<const uint4 *>(codes + (size_t)row * D + 16 * ch);
+          const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int j = 0; j < 16; j++) acc[j] += (w[j >> 2] >> (8 * (j & 3))) & 255u;
+          members++;
+        }
+        int4 *dst = reinterpret_cast<int4 *>(red + (size_t)m * D + 16 * ch);
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          dst[j] = int4{2 * (int)acc[4 * j] - 255 * members, 2 * (int)acc[4 * j + 1] - 255 * members,
+                        2 * (int)acc[4 * j + 2] - 255 * members, 2 * (int)acc[4 * j + 3] - 255 * members};
+      }
+      __syncthreads();
+      for (int t = tid; t < D; t += 256) {
+        int s = 0;
+        for (int mm = 0; mm < mlim; mm++) s += red[mm * D + t];
+        atomicAdd(&sums[(size_t)c * D + t], (unsigned long long)(long long)s);
+      }
+      if (tid == 0) atomicAdd(&counts[c], (unsigned long long)(q - p));
+      __syncthreads();
+    }
+    p = q;
+  }
+}
+
+int assign_work_bytes(int K, int D, size_t *bytes) {
+  SGIC_REQUIRE(K >= 1 && K <= kAssignMaxK, "1 <= K <= 65536");
+  SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= kMaxDimF32Q, "D must be a multiple of 64, at most 2048");
+  const size_t kpad = ((size_t)K + 15) / 16 * 16;
+  *bytes = kpad * ((size_t)3 * D + 8);   // three planes, then sum Q
+  return SGIC_OK;
+}
+
+template <bool REG>
+int launch_assign(size_t lds, unsigned blocks, const v4i *planes, const long long *sumq, const uint8_t *db, int K, int n, int D, int ct,
+                  int *out_c, long long *out_M, hipStream_t st) {
+  static bool lds_raised = false;   // largest use: one tile at D = 2048 -> 96.1 KiB
+  if (lds > 60 * 1024 && !lds_raised) {
+    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(assign_codes_kernel<REG>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 128 * 1024));
+    lds_raised = true;
+  }
+  assign_codes_kernel<REG><<<blocks, 256, lds, st>>>(planes, sumq, db, K, n, D, ct, out_c, out_M);
+  return sgic::check_launch("assign_codes_kernel");
+}
+
+}  // namespace
+
+extern "C" int sgic_assign_codes_f32c_work_bytes(int K, int D, size_t *bytes) {
+  SGIC_REQUIRE(bytes, "null pointer");
+  return assign_work_bytes(K, D, bytes);
+}
+
+extern "C" int sgic_assign_codes_f32c(const float *d_cent, const uint8_t *d_db, int K, int n, int D, uint8_t *d_work, size_t work_bytes,
+                                      int32_t *d_out_c, int64_t *d_out_M, sgic_stream_t stream) {
+  size_t need = 0;
+  const int rc = assign_work_bytes(K, D, &need);
+  if (rc != SGIC_OK) return rc;
+  SGIC_REQUIRE(n >= 1, "sizes");
+  SGIC_REQUIRE(d_cent && d_db && d_work && d_out_c && d_out_M, "null pointer");
+  SGIC_REQUIRE(((uintptr_t)d_cent | (uintptr_t)d_db | (uintptr_t)d_work) % 16 == 0, "centroids, codes and workspace must be 16-byte aligned");
+  SGIC_REQUIRE((uintptr_t)d_out_M % 8 == 0 && (uintptr_t)d_out_c % 4 == 0, "outputs must be aligned to their element size");
+  SGIC_REQUIRE(work_bytes >= need, "workspace (sgic_assign_codes_f32c_work_bytes)");
+  hipStream_t st = to_stream(stream);
+  const int tiles = (K + 15) / 16;
+  v4i *planes = reinterpret_cast<v4i *>(d_work);
+  long long *sumq = reinterpret_cast<long long *>(d_work + (size_t)tiles * 16 * 3 * D);
+  assign_prepare_kernel<<<tiles, 256, 0, st>>>(d_cent, K, D, planes, sumq);
+  const int prc = sgic::check_launch("assign_prepare_kernel");
+  if (prc != SGIC_OK) return prc;
+  const size_t tile_bytes = (size_t)48 * D + 128;   // three planes of 16 centroids and their sum Q
+  int ct = (int)((size_t)48 * 1024 / ((size_t)48 * D));   // about 48 KiB of planes per round
+  ct = ct < 1 ? 1 : (ct > kAssignMaxCt ? kAssignMaxCt : ct);
+  ct = ct < tiles ? ct : tiles;
+  const size_t lds = ct * tile_bytes;
+  const unsigned blocks = cdiv((size_t)n, kAssignRows);
+  long long *oM = reinterpret_cast<long long *>(d_out_M);
+  return D == 512 ? launch_assign<true>(lds, blocks, planes, sumq, d_db, K, n, D, ct, d_out_c, oM, st)
+                  : launch_assign<false>(lds, blocks, planes, sumq, d_db, K, n, D, ct, d_out_c, oM, st);
+}
+
+extern "C" int sgic_cluster_sums_u8(const uint8_t *d_db, const int64_t *d_order, const int32_t *d_sorted_assign, int n, int D, int K,
+                                    int64_t *d_sums, int64_t *d_counts, sgic_stream_t stream) {
+  SGIC_REQUIRE(n >= 1 && K >= 1, "sizes");
+  SGIC_REQUIRE(D > 0 && D % 16 == 0 && D <= kSumsMaxDim, "D must be a multiple of 16, at most 4096");
+  SGIC_REQUIRE(d_db && d_order && d_sorted_assign && d_sums && d_counts, "null pointer");
+  SGIC_REQUIRE((uintptr_t)d_db % 16 == 0, "codes must be 16-byte aligned");
+  SGIC_REQUIRE(((uintptr_t)d_order | (uintptr_t)d_sums | (uintptr_t)d_counts) % 8 == 0 && (uintptr_t)d_sorted_assign % 4 == 0,
+               "arrays must be aligned to their element size");
+  cluster_sums_kernel<<<cdiv((size_t)n, kSumsSlice), 256, 0, to_stream(stream)>>>(
+      d_db, reinterpret_cast<const long long *>(d_order), d_sorted_assign, n, D, K, reinterpret_cast<unsigned long long *>(d_sums),
+      reinterpret_cast<unsigned long long *>(d_counts));
+  return sgic::check_launch("cluster_sums_kernel");
+}

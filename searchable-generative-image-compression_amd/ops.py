@@ -1171,6 +1171,51 @@ def search_codes_range_f32q(q, db_codes, r_db, threshold, capacity=None, splits=
     return _range_collect(launch_into, q.shape[0], db_codes.shape[0], db_codes.device, threshold, capacity, max_pairs)
 
 
+def assign_codes(centroids, db_codes, r_db, return_int=False):
+    """for every row of the u8 codes the best of K fp32 centroids (csrc/search.hip, assign_codes_kernel): centroids (K, D) fp32 rows
+    of norm <= 1, db_codes (n, D) u8, r_db (n,) fp32 (search.code_rnorm), all contiguous on one device -> (cluster (n,) int32, score
+    (n,) fp32).  The argmax runs on the integer M of search_codes_f32q (equal M -> the lower centroid index); score =
+    (float32(M) * r_db) * 2^-22, the bits search_codes_f32q reports for that (centroid, row) pair.  return_int: -> (cluster, score,
+    M (n,) int64).  D % 64 == 0, D <= 2048, K <= 65536.  No synchronisation."""
+    require_gpu()
+    for t, dt in ((centroids, torch.float32), (db_codes, torch.uint8), (r_db, torch.float32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
+    K, D = centroids.shape
+    n, Dd = db_codes.shape
+    assert D == Dd and r_db.shape == (n,)
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_assign_codes_f32c_work_bytes", K, D, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=db_codes.device)
+    oc = torch.empty(n, dtype=torch.int32, device=db_codes.device)
+    oM = torch.empty(n, dtype=torch.int64, device=db_codes.device)
+    call("sgic_assign_codes_f32c", _p(centroids), _p(db_codes), K, n, D, _p(work), ctypes.c_size_t(nbytes.value), _p(oc), _p(oM))
+    score = (oM.to(torch.float32) * r_db) * (2.0 ** -22)
+    return (oc, score, oM) if return_int else (oc, score)
+
+
+def cluster_sums(db_codes, assign, K):
+    """the exact integer sums of a partition (csrc/search.hip, cluster_sums_kernel): db_codes (n, D) u8 and assign (n,) int32 with
+    every entry in [0, K), contiguous on one device -> (sums (K, D) int64, counts (K,) int64), sums[c] = sum of 2 code - 255 over
+    the rows of cluster c.  The rows are sorted by cluster on the device first (stable).  One read-back, the range check of
+    `assign`; an id outside [0, K) is a ValueError before the launch.  D % 16 == 0, D <= 4096."""
+    require_gpu()
+    for t, dt in ((db_codes, torch.uint8), (assign, torch.int32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
+    n, D = db_codes.shape
+    K = int(K)
+    assert assign.shape == (n,)
+    if K < 1 or n < 1:
+        raise ValueError(f"cluster_sums needs K >= 1 and at least one row, got K = {K}, n = {n}")
+    lo, hi = (int(v) for v in torch.stack(torch.aminmax(assign)).tolist())
+    if lo < 0 or hi >= K:
+        raise ValueError(f"cluster ids span [{lo}, {hi}], outside [0, {K})")
+    sorted_assign, order = torch.sort(assign, stable=True)
+    sums = torch.zeros(K, D, dtype=torch.int64, device=db_codes.device)
+    counts = torch.zeros(K, dtype=torch.int64, device=db_codes.device)
+    call("sgic_cluster_sums_u8", _p(db_codes), _p(order), _p(sorted_assign), n, D, K, _p(sums), _p(counts))
+    return sums, counts
+
+
 def jpeg_decode_batch(params, scan, tabs, segs, quant, B, H, W, total_blocks, plane_bytes, max_blocks, out=None, check=True):
     """baseline JPEG batch -> (B,H,W,3) u8 on the device (csrc/jpeg.hip; descriptors built by sgic_amd.jpeg.JpegBatch)"""
     require_gpu()

@@ -13,6 +13,9 @@ as it is; an fp32 text / image vector is taken to 2^-22 fixed point and searched
 codes, each pair computed once), and `--codes --min_score T` on any of the three query commands returns every hit with score >= T
 instead of the top k (`--max_pairs` bounds their number): u8 queries through the range kernel, text / image vectors through its
 fp32-query sibling.
+`clusters --k K` groups the code index into K themes: spherical k-means over the u8 codes (assignment on the i8 kernels' integer
+score, exact integer sums per cluster, the corpus never leaving its one byte per coordinate) and one JSON line per cluster with its
+representative and best members.
 `build-images` (the reference's `build.py build-images`) indexes a folder of ordinary images with the CLIP tower alone: no codec, no
 container.  The decoded bytes go to the tower as they are (clip.py preprocess_u8), and the index directory carries the same files
 as `build`, the tower's own u8 codes included."""
@@ -178,6 +181,40 @@ def duplicate_groups(i, j):
     return [g for _, g in sorted(groups.items()) if len(g) > 1]
 
 
+MAX_CLUSTERS = 65536     # sgic_assign_codes_f32c's limit on K
+
+
+def centroids_from_sums(sums, counts, previous):
+    """the update step of the spherical k-means over the codes: sums (K, D) int64, the exact sum of the members' dequantised
+    integer vectors 2c - 255 (ops.cluster_sums), counts (K,), previous (K, D) fp32 -> (K, D) fp32 unit rows,
+    float32(s / sqrt(sum s^2)) with s in float64.  A cluster without members, or whose sum is all zero, keeps its previous row"""
+    s = np.asarray(sums).astype(np.float64)
+    out = np.array(previous, dtype=np.float32, copy=True)
+    if s.shape != out.shape or np.asarray(counts).shape != (s.shape[0],):
+        raise ValueError(f"sums {s.shape}, counts {np.asarray(counts).shape} and previous centroids {out.shape} do not match")
+    length = np.sqrt((s * s).sum(axis=1))
+    live = (np.asarray(counts) > 0) & (length > 0)
+    out[live] = (s[live] / length[live, None]).astype(np.float32)
+    return out
+
+
+def cluster_report(assign, score):
+    """the clusters of an assignment as the `clusters` command lists them: assign (n,) cluster ids, score (n,) fp32, each row's
+    score against its own centroid -> [{"cluster", "size", "representative", "members"}] for the non-empty clusters.  `members`:
+    the cluster's rows, score descending (the fp32 bits), equal scores -> the lower row; `representative`: the first of them.
+    Clusters by size descending, equal sizes -> the lower cluster index"""
+    assign, score = np.asarray(assign), np.asarray(score, dtype=np.float32)
+    if assign.ndim != 1 or assign.shape != score.shape:
+        raise ValueError(f"assign {assign.shape} and score {score.shape} must be two vectors of one length")
+    order = np.lexsort((np.arange(assign.size), -score, assign))       # by cluster, then score descending, then row
+    ids, start, size = np.unique(assign[order], return_index=True, return_counts=True)
+    out = []
+    for j in np.lexsort((ids, -size)):
+        rows = order[start[j]:start[j] + size[j]]
+        out.append({"cluster": int(ids[j]), "size": int(size[j]), "representative": int(rows[0]), "members": rows.astype(np.int64)})
+    return out
+
+
 class CodeIndex:
     """an index of the u8 CLIP codes themselves: `codes` (n, D) u8, `ids` [n].  Searched with the fused i8 kernel
     (ops.search_codes) for u8 query codes and with its fp32-query sibling (ops.search_codes_f32q) for text / image vectors: scores
@@ -302,6 +339,67 @@ class CodeIndex:
         lims = np.zeros(t.shape[0] + 1, dtype=np.int64)
         np.cumsum(np.bincount(hq.cpu().numpy(), minlength=t.shape[0]), out=lims[1:])
         return lims, hs.cpu().numpy(), hd.cpu().numpy()
+
+    def assign(self, centroids):
+        """which of the centroids each row of the index belongs to: centroids (K, D) fp32 unit rows, numpy or a tensor on either
+        side -> (cluster (n,) int32, score (n,) fp32), the centroid with the highest score per row (equal scores -> the lower
+        centroid) and that score, the bits `search_vectors` reports for the pair.  One fused launch (ops.assign_codes), no score
+        matrix.  Refused, before anything is loaded or launched: what search_vectors refuses, and more than 65536 centroids"""
+        c, s = self._assign_device(self._centroids(centroids, "assign"))
+        return c.cpu().numpy(), s.cpu().numpy()
+
+    def _centroids(self, centroids, what):
+        t = self._unit_queries(centroids, what)
+        if not 1 <= t.shape[0] <= MAX_CLUSTERS:
+            raise ValueError(f"{what} takes 1 .. {MAX_CLUSTERS} centroids, got {t.shape[0]}")
+        return t
+
+    def _assign_device(self, t):
+        from . import ops
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        return ops.assign_codes(t.to(db.device).contiguous(), db, r_db)
+
+    def kmeans(self, k, iters=10, seed=0, init=None):
+        """spherical k-means (Lloyd) over the codes, the corpus staying on the device as u8: each iteration assigns every row to its
+        best centroid (ops.assign_codes), sums each cluster's members exactly in integers (ops.cluster_sums) and normalises the sums
+        on the host (centroids_from_sums).  Initial centroids: `init` (k, D) fp32 unit rows, else the dequantised codes of
+        default_rng(seed).choice(n, k, replace=False), sorted.  The loop ends after `iters` iterations or at the first assignment
+        pass that moves no row; otherwise one more pass assigns the rows to the last update, so `assign` and `score` always belong
+        to the returned centroids.  -> {"centroids" (k, D) fp32, "assign" (n,) int32, "score" (n,) fp32, "counts" (k,) int64,
+        "moved": rows that changed cluster in each pass of the loop (the first pass moves all n), "iters_run": those passes}.
+        Refused before anything is loaded or launched: k < 1, k > n, k > 65536, iters < 1, and what `assign` refuses of `init`"""
+        k, iters, n = int(k), int(iters), len(self)
+        if not 1 <= k <= min(n, MAX_CLUSTERS):
+            raise ValueError(f"kmeans needs 1 <= k <= min(rows, {MAX_CLUSTERS}), got k = {k} for {n} rows")
+        if iters < 1:
+            raise ValueError(f"kmeans needs iters >= 1, got {iters}")
+        if init is None:
+            init = codes_to_unit(self.codes[np.sort(np.random.default_rng(seed).choice(n, k, replace=False))])
+        cent_t = self._centroids(init, "kmeans")
+        if cent_t.shape[0] != k:
+            raise ValueError(f"init holds {cent_t.shape[0]} centroids, k = {k}")
+        cent = cent_t.cpu().numpy()
+        from . import ops
+        if self._dev is None:
+            self.to()
+        db = self._dev[0]
+        previous, moved, settled = torch.full((n,), -1, dtype=torch.int32, device=db.device), [], False
+        for _ in range(iters):
+            assign, score = self._assign_device(torch.from_numpy(cent))
+            moved.append(int((assign != previous).sum().item()))
+            if moved[-1] == 0:
+                settled = True
+                break
+            sums, counts = ops.cluster_sums(db, assign, k)
+            cent = centroids_from_sums(sums.cpu().numpy(), counts.cpu().numpy(), cent)
+            previous = assign
+        if not settled:
+            assign, score = self._assign_device(torch.from_numpy(cent))
+        assign = assign.cpu().numpy()
+        return {"centroids": cent, "assign": assign, "score": score.cpu().numpy(),
+                "counts": np.bincount(assign, minlength=k).astype(np.int64), "moved": moved, "iters_run": len(moved)}
 
     def range_search(self, q_codes, threshold, max_pairs=None):
         """every database row whose score against a query is >= threshold (fp32, the bits `search` reports), the FAISS range_search
@@ -598,6 +696,38 @@ def write_duplicates(index_dir, threshold, out=None, max_pairs=1 << 24):
     return counts
 
 
+def write_clusters(index_dir, k, iters=10, seed=0, members=20, save_dir=None, out=None):
+    """`clusters`: spherical k-means over the code index, one JSON line per non-empty cluster, largest first:
+    {"cluster", "size", "representative": path, "mean_score", "members": [{"path", "score"}, ...]} -- members score descending, at
+    most `members` of them (-1: all); mean_score the fp64 mean of all the cluster's fp32 scores.  A last line on stderr gives n, k,
+    the passes run, the rows moved in each and the mean score over all rows.  save_dir: centroids.npy, assign.npy, clusters.json.
+    -> the k-means result"""
+    ci = CodeIndex.load(index_dir)
+    res = ci.kmeans(k, iters=iters, seed=seed)
+    fh = open(out, "w", encoding="utf-8") if out else sys.stdout
+    try:
+        for c in cluster_report(res["assign"], res["score"]):
+            rows = c["members"]
+            listed = rows if members < 0 else rows[:members]
+            fh.write(json.dumps({"cluster": c["cluster"], "size": c["size"], "representative": ci.ids[c["representative"]],
+                                 "mean_score": float(res["score"][rows].astype(np.float64).mean()),
+                                 "members": [{"path": ci.ids[r], "score": float(res["score"][r])} for r in listed]},
+                                ensure_ascii=False) + "\n")
+    finally:
+        if out:
+            fh.close()
+    if save_dir is not None:
+        root = Path(save_dir)
+        root.mkdir(parents=True, exist_ok=True)
+        np.save(root / "centroids.npy", res["centroids"])
+        np.save(root / "assign.npy", res["assign"])
+        (root / "clusters.json").write_text(json.dumps({"n": len(ci), "dim": ci.dim, "k": int(k), "seed": int(seed),
+                                                        "iters_run": res["iters_run"], "moved": res["moved"]}), encoding="utf-8")
+    print("[OK] %d rows, k = %d, %d passes, moved %s, mean score %.6f" % (len(ci), int(k), res["iters_run"], res["moved"],
+                                                                       float(res["score"].astype(np.float64).mean())), file=sys.stderr)
+    return res
+
+
 _THRESHOLD_HELP = ("score threshold (cosine of the dequantised codes, fp32).  Measured on quantised unit codes at D = 512: a row scores "
                    "1 +- 2^-23 against itself (so 1.0 can miss it), one code off by one step <= 0.99997, 64 codes off about 0.998, all 512 "
                    "off about 0.985, unrelated rows < 0.2.  About 0.99999 selects identical codes only, 0.98-0.99 re-encodes of one "
@@ -617,7 +747,7 @@ _MAX_PAIRS_HELP = "with --min_score: refuse (and name the count) when more hits 
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours / duplicates")
+    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours / duplicates / clusters")
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name, arg in (("query-text", "--text"), ("query-image", "--image"), ("query-c2df", "--c2df")):
         p = sub.add_parser(name)
@@ -670,12 +800,29 @@ def main(argv=None):
     p.add_argument("--threshold", type=float, required=True, help=_THRESHOLD_HELP + ".  There is no default")
     p.add_argument("--out", type=Path, default=None)
     p.add_argument("--max_pairs", type=int, default=1 << 24, help="refuse (and name the count) when more pairs than this pass the threshold")
+    p = sub.add_parser("clusters", help="group the code index into k themes (spherical k-means), one JSON line per cluster")
+    p.add_argument("--index_dir", type=Path, required=True)
+    p.add_argument("--k", type=int, required=True, help="number of clusters, 1 .. min(rows, 65536)")
+    p.add_argument("--iters", type=int, default=10, help="iterations at most; the loop ends early once no row changes cluster")
+    p.add_argument("--seed", type=int, default=0, help="seed of the initial centroids (k rows of the index)")
+    p.add_argument("--members", type=int, default=20, help="members listed per cluster, best first; -1 lists all")
+    p.add_argument("--save_dir", type=Path, default=None, help="also write centroids.npy, assign.npy and clusters.json here")
+    p.add_argument("--out", type=Path, default=None)
     args = ap.parse_args(argv)
     for flag in ("threshold", "min_score"):      # refused before any file is read or kernel launched
         if getattr(args, flag, None) is not None and not np.isfinite(getattr(args, flag)):
             ap.error(f"--{flag} {getattr(args, flag)}: a finite score is needed")
     if getattr(args, "min_score", None) is not None and not args.codes:
         ap.error("--min_score needs --codes: only the u8 code index has a threshold search")
+    if args.cmd == "clusters":
+        if args.k < 1 or args.k > MAX_CLUSTERS:      # refused before any file is read or kernel launched
+            ap.error(f"--k {args.k}: 1 .. {MAX_CLUSTERS} clusters")
+        if args.iters < 1:
+            ap.error(f"--iters {args.iters}: at least one iteration")
+        if args.members < -1:
+            ap.error(f"--members {args.members}: a count, or -1 for all")
+        write_clusters(args.index_dir, args.k, args.iters, args.seed, args.members, args.save_dir, args.out)
+        return 0
     if args.cmd == "duplicates":
         write_duplicates(args.index_dir, args.threshold, args.out, args.max_pairs)
         return 0
