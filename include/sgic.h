@@ -322,7 +322,7 @@ int sgic_codebook_gather_norm(const int32_t *d_idx, const float *d_codebook, int
 int sgic_nhwc3_to_nchw_clamp(const float *d_in, int ld, int B, int H, int W, float *d_out, sgic_stream_t stream);
 
 /* exact top-k per row, descending, ties -> lower index (IndexFlatIP.search, search.py:113-120); d_scores
- * (nq, n) = sgic_gemm_f32(queries, database) and is consumed (taken entries become -inf). */
+ * (nq, n) = sgic_gemm_f32(queries, database) and is consumed (taken entries become NaN). */
 int sgic_topk_rows(float *d_scores, int nq, int n, int k, float *d_out_scores, int32_t *d_out_idx, sgic_stream_t stream);
 
 /* Fused exact search over u8 CLIP codes (sgic_amd/search.py CodeIndex): i8 MFMA inner products and top-k in one kernel; the

@@ -361,7 +361,7 @@ extern "C" int sgic_nhwc3_to_nchw_clamp(const float *d_in, int ld, int B, int H,
 // ------------------------------------------------------------------------------------------------
 // Exact top-k per row (descending score, ties -> lower index) for IndexFlatIP.search semantics
 // (search.py:113-120): scores [nq, n] come from sgic_gemm_f32(q, db).  One workgroup per query row,
-// k selection passes; k <= 1024, n arbitrary.  Scores are overwritten with -inf as they are taken.
+// k selection passes; k <= 1024, n arbitrary.  Scores are overwritten with NaN as they are taken.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void topk_rows_kernel(float *__restrict__ scores, int n, int k, float *__restrict__ out_s,
                                                         int *__restrict__ out_i) {
@@ -389,7 +389,9 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(float *__restrict__ scor
     if (threadIdx.x == 0) {
       out_s[(long)blockIdx.x * k + j] = sv[0];
       out_i[(long)blockIdx.x * k + j] = si[0] == 0x7fffffff ? -1 : si[0];
-      if (si[0] != 0x7fffffff) row[si[0]] = -INFINITY;
+      // NaN compares neither greater nor equal, so a taken entry is never taken again (-inf as the mark would be: once the
+      // finite scores of a row run out, a -inf entry that was already taken ties with the ones that were not)
+      if (si[0] != 0x7fffffff) row[si[0]] = __builtin_nanf("");
     }
     __syncthreads();
   }

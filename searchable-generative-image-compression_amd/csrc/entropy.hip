@@ -635,11 +635,12 @@ __global__ void index_margin_kernel(const float *__restrict__ scales, int ld_sm,
       other = skipped ? as_coded : -1;
     }
     if (!skipped) {                                          // bin edges (none below index 0 / above 255: the clamp)
-      const double ti = (ls - log_min) / log_step, f = ti - floor(ti);
-      if (ti > 0.0 && ti < 255.0) {
-        if (as_coded >= 1 && f < best) best = f, other = as_coded - 1;
-        if (as_coded <= 254 && 1.0 - f < best) best = 1.0 - f, other = as_coded + 1;
-      }
+      // The two edges next to the index AS CODED (the fp32 arithmetic of scale_to_index), not next to floor(ti): within a few ulps
+      // of an edge the two disagree, and the index on the other side of that edge is then as_coded +- 1 all the same.
+      const double ti = (ls - log_min) / log_step;
+      const double lo = fabs(ti - (double)as_coded), hi = fabs((double)(as_coded + 1) - ti);
+      if (as_coded >= 1 && lo < best) best = lo, other = as_coded - 1;
+      if (as_coded <= 254 && hi < best) best = hi, other = as_coded + 1;
     }
     margin[o] = (float)best;
     alt[o] = (int16_t)other;

@@ -442,7 +442,9 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float *__restrict_
       const int oi = s_besti[w][tid];
       if (ob < b || (ob == b && oi < bi)) b = ob, bi = oi;
     }
-    idx[m0 + tid] = bi;
+    // no distance compared below +inf (a NaN / Inf token, or every distance NaN): besti is still its initial value, which is not
+    // an index -- return code 0, as torch.argmin does on an all-NaN row
+    idx[m0 + tid] = bi == 0x7fffffff ? 0 : bi;
   }
 }
 
