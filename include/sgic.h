@@ -409,6 +409,22 @@ int sgic_assign_codes_f32c(const float *d_cent, const uint8_t *d_db, int K, int 
 int sgic_cluster_sums_u8(const uint8_t *d_db, const int64_t *d_order, const int32_t *d_sorted_assign, int n, int D, int K,
                          int64_t *d_sums, int64_t *d_counts, sgic_stream_t stream);
 
+/* Rate-distortion measurement of B pairs of u8 images (quality.measure, evaluate.py; the arithmetic of the reference's
+ * taming/modules/losses/quality.py: PSNR and pytorch_msssim.MS_SSIM(data_range=1.0)).  d_a (original) and d_b (reconstruction) are
+ * (B, H, W, 3) interleaved RGB.  d_sse[b][c] = sum (a - b)^2 over the plane, int64, exact (integer adds only; zeroed here).
+ * d_levels[b][c][s] = {mean ssim, mean cs} of level s = 0..4 in fp64: level 0 is the u8 values, level s + 1 the 2 x 2 SUM of level s
+ * with stride 2 starting at -(H_s % 2), -(W_s % 2), cells outside the plane 0 (avg_pool2d(2, padding = size % 2) without the
+ * division: u16 numerators over 255 * 4^s, kept in d_work for both images); the window is g_i = exp(-(i - 5)^2 / 4.5) / sum, 11
+ * taps, valid filtering, rows then columns; mu = F(X), s1 = F(XX) - mu1^2, s2 = F(YY) - mu2^2, s12 = F(XY) - mu1 mu2 with the
+ * products formed exactly from the integers; cs = (2 s12 + 9e-4) / (s1 + s2 + 9e-4), ssim = (2 mu1 mu2 + 1e-4) / (mu1^2 + mu2^2 +
+ * 1e-4) cs; each averaged over the (H_s - 10) x (W_s - 10) map.  A workgroup reduces its tile, the tiles' sums are added in a fixed
+ * order (no float atomics): the same input gives the same bits.  The caller combines the levels (relu, weights, channel mean).
+ * d_work: 16-byte aligned, at least the *bytes sgic_quality_u8_work_bytes returns (host-only, takes no stream).  1 <= B <= 65536,
+ * 160 < H, W <= 16384; anything else, a null pointer, a misaligned or too small workspace is SGIC_EINVAL before any launch. */
+int sgic_quality_u8_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_quality_u8(const uint8_t *d_a, const uint8_t *d_b, int B, int H, int W, uint8_t *d_work, size_t work_bytes,
+                    int64_t *d_sse, double *d_levels, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

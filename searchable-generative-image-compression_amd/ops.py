@@ -1216,6 +1216,24 @@ def cluster_sums(db_codes, assign, K):
     return sums, counts
 
 
+def quality_u8(a, b):
+    """squared error and MS-SSIM level means of B pairs of u8 images (csrc/quality.hip): a (original) and b (reconstruction)
+    (B, H, W, 3) u8, contiguous on one device, min(H, W) > 160 -> (sse (B, 3) int64, exact; levels (B, 3, 5, 2) float64: the mean
+    ssim and the mean cs of every level and channel).  quality.combine turns them into psnr / ssim / ms_ssim.  No synchronisation."""
+    require_gpu()
+    for t in (a, b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a.device
+    assert a.dim() == 4 and a.shape[3] == 3 and a.shape == b.shape
+    B, H, W, _ = a.shape
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_quality_u8_work_bytes", B, H, W, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device)
+    sse = torch.empty(B, 3, dtype=torch.int64, device=a.device)
+    levels = torch.empty(B, 3, 5, 2, dtype=torch.float64, device=a.device)
+    call("sgic_quality_u8", _p(a), _p(b), B, H, W, _p(work), ctypes.c_size_t(nbytes.value), _p(sse), _p(levels))
+    return sse, levels
+
+
 def jpeg_decode_batch(params, scan, tabs, segs, quant, B, H, W, total_blocks, plane_bytes, max_blocks, out=None, check=True):
     """baseline JPEG batch -> (B,H,W,3) u8 on the device (csrc/jpeg.hip; descriptors built by sgic_amd.jpeg.JpegBatch)"""
     require_gpu()
