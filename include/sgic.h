@@ -496,6 +496,22 @@ int sgic_jpeg_decode_scans_batch(const int32_t *d_params, const int32_t *d_descs
                                  long total_blocks, int max_blocks, const int32_t *h_level_start, int nlevels,
                                  sgic_stream_t stream);
 
+/* Baseline JPEG encode of a batch of B equal-geometry images on the device: d_rgb (B, H, W, 3) u8 interleaved RGB -> for image b
+ * the entropy-coded segment followed by FF D9 in d_out[b * cap .. b * cap + d_len[b]), the very bytes that Pillow / libjpeg-turbo's
+ * `save(format="JPEG", quality, subsampling)` writes after its SOS header for the same pixels and tables (jccolor, jcsample without
+ * smoothing, jfdctint islow, the Annex K Huffman tables, no restart markers).  The header is the host's (sgic_amd/jpeg_enc.py).
+ * subsampling: Pillow's 0 (4:4:4), 1 (4:2:2), 2 (4:2:0).  h_qt: HOST array (B, 2, 64) u16, luma and chroma quantisation table of
+ * every image in natural order, entries in [1, 255]; checked here and uploaded on the stream.  Limits: 1 <= H, W <= 16384 and at
+ * most 2581110 coded 8 x 8 blocks per image (dummy blocks of partial MCUs included), so that a bit offset within an image fits 32
+ * bits; offsets across images are 64-bit.  cap: bytes per slot, at least sgic_jpeg_encode_cap's (416 per coded block + 2: the
+ * largest code of a block is 208 bytes, doubled for byte stuffing) and below 2^31.  d_work: a device workspace (16-byte aligned) of
+ * at least sgic_jpeg_encode_work_bytes.  d_err[b] != 0 and d_len[b] = 0 if a slot was too small (with the computed cap it is not).
+ * Every bad argument is SGIC_EINVAL before anything is launched.  The two helpers are host-only and take no stream. */
+int sgic_jpeg_encode_cap(int H, int W, int subsampling, size_t *cap);
+int sgic_jpeg_encode_work_bytes(int B, int H, int W, int subsampling, size_t *bytes);
+int sgic_jpeg_encode_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt, uint8_t *d_work,
+                           size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, sgic_stream_t stream);
+
 /* CLIP text tower front end: out[b*L+l,:] = table[ids[b,l],:] + pos[l,:] (open_clip CLIP.encode_text, reached from
  * search.py:93-97; ids outside [0,vocab) are clamped).  D multiple of 4. */
 int sgic_embed_tokens(const int32_t *d_ids, const float *d_table, const float *d_pos, float *d_out, int B, int L, int D,

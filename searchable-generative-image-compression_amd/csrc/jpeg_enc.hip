@@ -1,0 +1,572 @@
+// Baseline JPEG encode of a batch of B equal-geometry RGB u8 images (sgic_jpeg_encode_batch, include/sgic.h): the entropy-coded
+// segment and EOI of the file that Pillow / libjpeg-turbo writes for the same pixels, quantisation tables and sampling layout, byte
+// for byte.  Integer arithmetic only (jccolor, jcsample without smoothing, jfdctint islow, division by 8 q with rounding, the
+// Annex K Huffman tables); DESIGN.md section 13 has the definition.  Six passes, every one parallel in 8 x 8 blocks or in bytes:
+//   coef   one thread per coded block: colour, downsampling, edge replication, DCT, quantisation -> i16 coefficients in zigzag order
+//   bits   one thread per block: its code length; a workgroup scan leaves offsets within 256 blocks and the sum of the 256
+//   scan   one workgroup per image: exclusive scan of those sums (used again for the stuffing counts)
+//   pack   one thread per block: its codes go to the zeroed bit stream; blocks share at most their first and last word, which take an
+//          integer atomicOr (order-free, so two runs give the same bytes), words in between are plain stores
+//   count  one workgroup per 4 KiB of the stream: the 0xFF bytes (the 1-bit padding of the last byte included)
+//   emit   the same split: bytes move to their slot, a 0x00 follows every 0xFF, then FF D9, the length and the error word
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int MAX_GRID_Y = 32768;
+constexpr int WORDS_PER_BLOCK = 52;        // a block codes to at most 20 + 63 * 26 = 1658 bits <= 208 bytes
+constexpr int CHUNK_WORDS = NT * 4;        // words of the bit stream that a workgroup of count / emit takes at a time
+constexpr int MAX_CHUNK_GRID = 1024;
+constexpr unsigned MAX_BLOCKS = 2581110;   // 1664 bits each stay below 2^32: bit offsets within an image are 32-bit
+
+constexpr int ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// T.81 Annex K.3: BITS and HUFFVAL of the four typical tables
+constexpr unsigned char DC_LUMA_BITS[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+constexpr unsigned char DC_CHROMA_BITS[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+constexpr unsigned char DC_VALS[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr unsigned char AC_LUMA_BITS[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+constexpr unsigned char AC_LUMA_VALS[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+constexpr unsigned char AC_CHROMA_BITS[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+constexpr unsigned char AC_CHROMA_VALS[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+
+// code << 8 | length by symbol: DC luma, DC chroma (12 each), AC luma, AC chroma (256 each; 0 where the table has no such symbol)
+constexpr int TAB_DC = 0, TAB_AC = 24, TAB_WORDS = 24 + 512;
+struct HuffTabs {
+  uint32_t w[TAB_WORDS];
+};
+
+constexpr void fill_codes(uint32_t *dst, const unsigned char *bits, const unsigned char *vals) {
+  unsigned code = 0;
+  int k = 0;
+  for (int len = 1; len <= 16; ++len) {
+    for (int i = 0; i < bits[len - 1]; ++i) dst[vals[k++]] = (code++ << 8) | (unsigned)len;
+    code <<= 1;
+  }
+}
+
+constexpr HuffTabs make_tabs() {
+  HuffTabs t{};
+  fill_codes(t.w + TAB_DC, DC_LUMA_BITS, DC_VALS);
+  fill_codes(t.w + TAB_DC + 12, DC_CHROMA_BITS, DC_VALS);
+  fill_codes(t.w + TAB_AC, AC_LUMA_BITS, AC_LUMA_VALS);
+  fill_codes(t.w + TAB_AC + 256, AC_CHROMA_BITS, AC_CHROMA_VALS);
+  return t;
+}
+
+__constant__ HuffTabs kTabs = make_tabs();
+
+struct EPlan {
+  int B, H, W;
+  int hs, vs;        // luma sampling factors; chroma is 1 x 1
+  int mx, my;        // MCUs across and down
+  int wb, hb;        // luma blocks that are not dummy blocks: ceil(W / 8) x ceil(H / 8)
+  int ny, bpm;       // luma blocks and all blocks of an MCU
+  int nblk;          // coded blocks of an image, dummy blocks included
+  int nchunk;        // workgroups of bits / pack per image
+  int nbchunk;       // CHUNK_WORDS pieces of an image's worst-case bit stream
+  size_t words;      // u32 words of one image's bit stream (a multiple of 4, one spare word for the last flush)
+  size_t off_qt, off_local, off_csum, off_bits, off_ffsum, off_tot;   // bytes from d_work; the coefficients lie at 0
+  size_t bytes, cap;
+};
+
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+bool make_plan(int B, int H, int W, int sub, EPlan *p) {
+  if (B < 1 || H < 1 || W < 1 || H > 16384 || W > 16384 || sub < 0 || sub > 2) return false;
+  p->B = B; p->H = H; p->W = W;
+  p->hs = sub == 0 ? 1 : 2;
+  p->vs = sub == 2 ? 2 : 1;
+  p->mx = (W + 8 * p->hs - 1) / (8 * p->hs);
+  p->my = (H + 8 * p->vs - 1) / (8 * p->vs);
+  p->wb = (W + 7) / 8;
+  p->hb = (H + 7) / 8;
+  p->ny = p->hs * p->vs;
+  p->bpm = p->ny + 2;
+  const size_t nblk = (size_t)p->mx * p->my * p->bpm;
+  if (nblk > MAX_BLOCKS) return false;
+  p->nblk = (int)nblk;
+  p->nchunk = (int)((nblk + NT - 1) / NT);
+  p->words = (nblk * WORDS_PER_BLOCK + 1 + 3) & ~(size_t)3;
+  p->nbchunk = (int)((p->words + CHUNK_WORDS - 1) / CHUNK_WORDS);
+  size_t o = align16((size_t)B * nblk * 64 * sizeof(int16_t));
+  p->off_qt = o;     o += align16((size_t)B * 128 * sizeof(uint16_t));
+  p->off_local = o;  o += align16((size_t)B * nblk * sizeof(uint32_t));
+  p->off_csum = o;   o += align16((size_t)B * p->nchunk * sizeof(uint32_t));
+  p->off_bits = o;   o += (size_t)B * p->words * sizeof(uint32_t);
+  p->off_ffsum = o;  o += align16((size_t)B * p->nbchunk * sizeof(uint32_t));
+  p->off_tot = o;    o += align16((size_t)B * 2 * sizeof(uint32_t));
+  p->bytes = o;
+  p->cap = nblk * (2 * WORDS_PER_BLOCK * 4) + 2;
+  return true;
+}
+
+// block t of an image's scan -> component (0 luma, 1 Cb, 2 Cr) and block coordinates within the component; false for a dummy block
+__device__ __forceinline__ bool block_of(const EPlan &p, int t, int &comp, int &bx, int &by) {
+  const int mcu = t / p.bpm, k = t - mcu * p.bpm;
+  const int my = mcu / p.mx, mx = mcu - my * p.mx;
+  if (k < p.ny) {
+    const int dy = k / p.hs, dx = k - dy * p.hs;
+    comp = 0;
+    bx = mx * p.hs + dx;
+    by = my * p.vs + dy;
+    return bx < p.wb && by < p.hb;
+  }
+  comp = 1 + k - p.ny;
+  bx = mx;
+  by = my;
+  return true;
+}
+
+// one jfdctint pass over eight values: the row pass keeps 2 extra bits, the column pass removes them and the factor 8 stays
+template <bool FIRST>
+__device__ __forceinline__ void fdct8(int &d0, int &d1, int &d2, int &d3, int &d4, int &d5, int &d6, int &d7) {
+  constexpr int N = FIRST ? 11 : 15, R = 1 << (N - 1);
+  const int t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  if (FIRST) {
+    d0 = (t10 + t11) << 2;
+    d4 = (t10 - t11) << 2;
+  } else {
+    d0 = (t10 + t11 + 2) >> 2;
+    d4 = (t10 - t11 + 2) >> 2;
+  }
+  int z1 = (t12 + t13) * 4433;
+  d2 = (z1 + t13 * 6270 + R) >> N;
+  d6 = (z1 - t12 * 15137 + R) >> N;
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * 9633;
+  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  z1 *= -7373;
+  z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  d7 = (a4 + z1 + z3 + R) >> N;
+  d5 = (a5 + z2 + z4 + R) >> N;
+  d3 = (a6 + z2 + z3 + R) >> N;
+  d1 = (a7 + z1 + z4 + R) >> N;
+}
+
+__global__ __launch_bounds__(NT) void jpeg_enc_coef_kernel(const uint8_t *__restrict__ rgb, const uint16_t *__restrict__ qt,
+                                                           int16_t *__restrict__ coef, EPlan p) {
+  const int t = blockIdx.x * NT + threadIdx.x;
+  if (t >= p.nblk) return;
+  int comp, bx, by;
+  if (!block_of(p, t, comp, bx, by)) return;
+  // jccolor: 16 fractional bits
+  const int kr = comp == 0 ? 19595 : comp == 1 ? -11059 : 32768;
+  const int kg = comp == 0 ? 38470 : comp == 1 ? -21709 : -27439;
+  const int kb = comp == 0 ? 7471 : comp == 1 ? 32768 : -5329;
+  const int ka = comp == 0 ? 32768 : (128 << 16) + 32767;
+  const int hsub = comp ? p.hs : 1, vsub = comp ? p.vs : 1;
+  const int rows = (p.H + vsub - 1) / vsub;        // rows of the component that come from the image
+  const int H = p.H, W = p.W;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const uint8_t *im = rgb + (size_t)img * H * W * 3;
+    int ws[64];
+    if (hsub * vsub == 1) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const uint8_t *row = im + (size_t)min(by * 8 + r, H - 1) * W * 3;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint8_t *px = row + min(bx * 8 + c, W - 1) * 3;
+          ws[r * 8 + c] = ((kr * px[0] + kg * px[1] + kb * px[2] + ka) >> 16) - 128;
+        }
+      }
+    } else {
+      // 2 x 1 and 2 x 2 as one form: a row taken twice doubles the sum and the bias, and (2 s + 2 b) >> 2 == (s + b) >> 1
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int cy = min(by * 8 + r, rows - 1);
+        const uint8_t *row0 = im + (size_t)min(cy * vsub, H - 1) * W * 3;
+        const uint8_t *row1 = im + (size_t)min(cy * vsub + vsub - 1, H - 1) * W * 3;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const int x0 = min((bx * 8 + c) * 2, W - 1) * 3, x1 = min((bx * 8 + c) * 2 + 1, W - 1) * 3;
+          const int s = ((kr * row0[x0] + kg * row0[x0 + 1] + kb * row0[x0 + 2] + ka) >> 16) +
+                        ((kr * row0[x1] + kg * row0[x1 + 1] + kb * row0[x1 + 2] + ka) >> 16) +
+                        ((kr * row1[x0] + kg * row1[x0 + 1] + kb * row1[x0 + 2] + ka) >> 16) +
+                        ((kr * row1[x1] + kg * row1[x1 + 1] + kb * row1[x1 + 2] + ka) >> 16);
+          const int bias = vsub == 2 ? 1 + (c & 1) : 2 * (c & 1);
+          ws[r * 8 + c] = ((s + bias) >> 2) - 128;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+      fdct8<true>(ws[r * 8], ws[r * 8 + 1], ws[r * 8 + 2], ws[r * 8 + 3], ws[r * 8 + 4], ws[r * 8 + 5], ws[r * 8 + 6], ws[r * 8 + 7]);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      fdct8<false>(ws[c], ws[8 + c], ws[16 + c], ws[24 + c], ws[32 + c], ws[40 + c], ws[48 + c], ws[56 + c]);
+    const uint16_t *q = qt + ((size_t)img * 2 + (comp ? 1 : 0)) * 64;
+#pragma unroll
+    for (int n = 0; n < 64; ++n) {
+      const unsigned d = 8u * q[n];
+      const int v = ws[n];
+      const unsigned m = ((unsigned)abs(v) + (d >> 1)) / d;
+      ws[n] = v < 0 ? -(int)m : (int)m;
+    }
+    uint4 *dst = reinterpret_cast<uint4 *>(coef + ((size_t)img * p.nblk + t) * 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      uint4 o;
+      o.x = (unsigned)(ws[ZIGZAG[8 * j]] & 0xffff) | ((unsigned)ws[ZIGZAG[8 * j + 1]] << 16);
+      o.y = (unsigned)(ws[ZIGZAG[8 * j + 2]] & 0xffff) | ((unsigned)ws[ZIGZAG[8 * j + 3]] << 16);
+      o.z = (unsigned)(ws[ZIGZAG[8 * j + 4]] & 0xffff) | ((unsigned)ws[ZIGZAG[8 * j + 5]] << 16);
+      o.w = (unsigned)(ws[ZIGZAG[8 * j + 6]] & 0xffff) | ((unsigned)ws[ZIGZAG[8 * j + 7]] << 16);
+      dst[j] = o;
+    }
+  }
+}
+
+// the DC that block t's difference is taken from: the last block of its component before it in the scan that is no dummy block
+// (a dummy block repeats the DC before it, so it passes that value on)
+__device__ __forceinline__ int dc_before(const EPlan &p, const int16_t *__restrict__ coef, int t) {
+  int mcu = t / p.bpm, k = t - mcu * p.bpm;
+  if (k >= p.ny) return mcu ? coef[(size_t)(t - p.bpm) * 64] : 0;
+  if (--k < 0) {
+    if (mcu == 0) return 0;
+    --mcu;
+    k = p.ny - 1;
+  }
+  for (; k > 0; --k) {     // block 0 of an MCU is never a dummy block
+    int comp, bx, by;
+    if (block_of(p, mcu * p.bpm + k, comp, bx, by)) break;
+  }
+  return coef[(size_t)(mcu * p.bpm + k) * 64];
+}
+
+struct CountSink {
+  unsigned bits;
+  __device__ __forceinline__ void put(unsigned, int len) { bits += (unsigned)len; }
+};
+
+// MSB first: bit i of the stream is bit 31 - i % 32 of word i / 32
+struct PackSink {
+  uint32_t *words;
+  unsigned wi;
+  unsigned long long acc;
+  int n;
+  bool shared;      // the next word to leave may hold bits of the block before this one
+  __device__ __forceinline__ void put(unsigned code, int len) {
+    acc = (acc << len) | code;
+    n += len;
+    if (n >= 32) {
+      n -= 32;
+      const uint32_t w = (uint32_t)(acc >> n);
+      if (shared) {
+        atomicOr(&words[wi], w);
+        shared = false;
+      } else {
+        words[wi] = w;
+      }
+      ++wi;
+      acc &= (1ull << n) - 1;
+    }
+  }
+};
+
+// the codes of one block: c holds its 64 coefficients in zigzag order (8 x uint4 of i16 pairs), tab the tables in LDS
+template <typename Sink>
+__device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int pred, int chroma, const uint32_t *tab) {
+  const uint32_t *dc = tab + TAB_DC + 12 * chroma, *ac = tab + TAB_AC + 256 * chroma;
+  const int diff = (int)(short)(c[0].x & 0xffff) - pred;
+  {
+    const int nb = min(32 - __clz(abs(diff)), 11);
+    const uint32_t e = dc[nb];
+    const unsigned extra = (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1);
+    sink.put(((e >> 8) << nb) | extra, (int)(e & 0xff) + nb);
+  }
+  int run = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    const unsigned w = (k & 7) < 2 ? c[k >> 3].x : (k & 7) < 4 ? c[k >> 3].y : (k & 7) < 6 ? c[k >> 3].z : c[k >> 3].w;
+    const int v = (int)(short)((k & 1) ? (w >> 16) : (w & 0xffff));
+    if (v == 0) {
+      ++run;
+    } else {
+      const uint32_t zrl = ac[0xF0];
+      for (; run > 15; run -= 16) sink.put(zrl >> 8, (int)(zrl & 0xff));
+      const int nb = min(32 - __clz(abs(v)), 15);
+      const uint32_t e = ac[(run << 4) | nb];
+      const unsigned extra = (unsigned)(v < 0 ? v - 1 : v) & ((1u << nb) - 1);
+      sink.put(((e >> 8) << nb) | extra, (int)(e & 0xff) + nb);
+      run = 0;
+    }
+  }
+  if (run) sink.put(ac[0] >> 8, (int)(ac[0] & 0xff));
+}
+
+__device__ __forceinline__ void stage_tabs(uint32_t *tab) {
+  for (int i = threadIdx.x; i < TAB_WORDS; i += NT) tab[i] = kTabs.w[i];
+  __syncthreads();
+}
+
+// exclusive scan of one value per thread over the workgroup; *total: the sum.  red: NT / 64 words of LDS
+__device__ __forceinline__ unsigned wg_exclusive_scan(unsigned v, unsigned *red, unsigned *total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned o = (unsigned)__shfl_up((int)inc, d, 64);
+    if (lane >= d) inc += o;
+  }
+  if (lane == 63) red[wave] = inc;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    const unsigned s = red[w];
+    if (w < wave) before += s;
+    all += s;
+  }
+  __syncthreads();
+  *total = all;
+  return before + inc - v;
+}
+
+// The codes of a dummy block: a zero DC difference in the luma table (00) and EOB (1010).
+constexpr unsigned DUMMY_CODE = 0x0A, DUMMY_BITS = 6;
+
+__global__ __launch_bounds__(NT) void jpeg_enc_bits_kernel(const int16_t *__restrict__ coef, uint32_t *__restrict__ local,
+                                                           uint32_t *__restrict__ csum, EPlan p) {
+  __shared__ uint32_t tab[TAB_WORDS];
+  __shared__ unsigned red[NT / 64];
+  stage_tabs(tab);
+  const int t = blockIdx.x * NT + threadIdx.x;
+  int comp = 0, bx, by;
+  const bool real = t < p.nblk && block_of(p, t, comp, bx, by);
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    unsigned bits = t < p.nblk ? DUMMY_BITS : 0;
+    if (real) {
+      const int16_t *ci = coef + (size_t)img * p.nblk * 64;
+      const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
+      uint4 c[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) c[j] = src[j];
+      CountSink sink{0};
+      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0, tab);
+      bits = sink.bits;
+    }
+    unsigned total;
+    const unsigned off = wg_exclusive_scan(bits, red, &total);
+    if (t < p.nblk) local[(size_t)img * p.nblk + t] = off;
+    if (threadIdx.x == 0) csum[(size_t)img * p.nchunk + blockIdx.x] = total;
+  }
+}
+
+// One workgroup per image: v[img][0 .. n) becomes its exclusive scan and tot[img * 2 + slot] the sum.  With from_bits, n is the
+// number of CHUNK_WORDS pieces that hold the tot[img * 2] bits of the image (the pieces that the count pass has written).
+__global__ __launch_bounds__(NT) void jpeg_enc_scan_kernel(uint32_t *__restrict__ v, int stride, int n, uint32_t *__restrict__ tot,
+                                                           int slot, int from_bits, int B) {
+  __shared__ unsigned red[NT / 64];
+  for (int img = blockIdx.x; img < B; img += gridDim.x) {
+    uint32_t *a = v + (size_t)img * stride;
+    int cnt = n;
+    if (from_bits) {
+      const unsigned nbytes = (tot[(size_t)img * 2] >> 3) + ((tot[(size_t)img * 2] & 7) ? 1 : 0);
+      cnt = (int)((nbytes + CHUNK_WORDS * 4 - 1) / (CHUNK_WORDS * 4));
+    }
+    unsigned carry = 0;
+    for (int base = 0; base < cnt; base += NT) {
+      const int i = base + threadIdx.x;
+      const unsigned x = i < cnt ? a[i] : 0;
+      unsigned total;
+      const unsigned off = wg_exclusive_scan(x, red, &total);
+      if (i < cnt) a[i] = carry + off;
+      carry += total;
+    }
+    if (threadIdx.x == 0) tot[(size_t)img * 2 + slot] = carry;
+  }
+}
+
+__global__ __launch_bounds__(NT) void jpeg_enc_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ local,
+                                                           const uint32_t *__restrict__ csum, uint32_t *__restrict__ bits, EPlan p) {
+  __shared__ uint32_t tab[TAB_WORDS];
+  stage_tabs(tab);
+  const int t = blockIdx.x * NT + threadIdx.x;
+  if (t >= p.nblk) return;
+  int comp, bx, by;
+  const bool real = block_of(p, t, comp, bx, by);
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const unsigned pos = csum[(size_t)img * p.nchunk + blockIdx.x] + local[(size_t)img * p.nblk + t];
+    // the bits of the word in front of this block count as zeros of the accumulator, so that whole words leave it
+    PackSink sink{bits + (size_t)img * p.words, pos >> 5, 0ull, (int)(pos & 31), true};
+    if (real) {
+      const int16_t *ci = coef + (size_t)img * p.nblk * 64;
+      const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
+      uint4 c[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) c[j] = src[j];
+      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0, tab);
+    } else {
+      sink.put(DUMMY_CODE, DUMMY_BITS);
+    }
+    if (sink.n) atomicOr(&sink.words[sink.wi], (uint32_t)(sink.acc << (32 - sink.n)));
+  }
+}
+
+// the four words of the stream at word index wi (a multiple of 4 below the image's word count), with the 1-bits that pad the last
+// byte.  Bytes past the stream's end are zero: the words were zeroed and only coded bits were set.
+__device__ __forceinline__ uint4 padded_words(const uint32_t *__restrict__ words, unsigned wi, unsigned tbits) {
+  uint4 w = *reinterpret_cast<const uint4 *>(words + wi);
+  if (tbits & 7) {
+    const unsigned last = tbits >> 3;      // the byte that holds the last bits
+    if ((last >> 2) - wi < 4) {
+      const unsigned m = ((1u << (8 - (tbits & 7))) - 1) << (24 - 8 * (last & 3));
+      const unsigned j = (last >> 2) - wi;
+      if (j == 0) w.x |= m; else if (j == 1) w.y |= m; else if (j == 2) w.z |= m; else w.w |= m;
+    }
+  }
+  return w;
+}
+
+__device__ __forceinline__ unsigned count_ff(unsigned w) {
+  return (unsigned)((w >> 24) == 0xff) + (unsigned)(((w >> 16) & 0xff) == 0xff) + (unsigned)(((w >> 8) & 0xff) == 0xff) +
+         (unsigned)((w & 0xff) == 0xff);
+}
+
+__global__ __launch_bounds__(NT) void jpeg_enc_count_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
+                                                            uint32_t *__restrict__ ffsum, EPlan p) {
+  __shared__ unsigned red[NT / 64];
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const unsigned tbits = tot[(size_t)img * 2];
+    const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
+    const uint32_t *words = bits + (size_t)img * p.words;
+    for (unsigned c = blockIdx.x; (size_t)c * CHUNK_WORDS * 4 < nbytes; c += gridDim.x) {
+      const unsigned wi = c * CHUNK_WORDS + threadIdx.x * 4;
+      unsigned n = 0;
+      if ((size_t)wi * 4 < nbytes) {
+        const uint4 w = padded_words(words, wi, tbits);
+        n = count_ff(w.x) + count_ff(w.y) + count_ff(w.z) + count_ff(w.w);
+      }
+      unsigned total;
+      wg_exclusive_scan(n, red, &total);
+      if (threadIdx.x == 0) ffsum[(size_t)img * p.nbchunk + c] = total;
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
+                                                           const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
+                                                           int32_t *__restrict__ lens, int32_t *__restrict__ err, EPlan p) {
+  __shared__ unsigned red[NT / 64];
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const unsigned tbits = tot[(size_t)img * 2];
+    const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
+    const uint32_t *words = bits + (size_t)img * p.words;
+    uint8_t *slot = out + (size_t)img * cap;
+    for (unsigned c = blockIdx.x; (size_t)c * CHUNK_WORDS * 4 < nbytes; c += gridDim.x) {
+      const unsigned wi = c * CHUNK_WORDS + threadIdx.x * 4;
+      const bool live = (size_t)wi * 4 < nbytes;
+      uint4 w = make_uint4(0, 0, 0, 0);
+      unsigned n = 0;
+      if (live) {
+        w = padded_words(words, wi, tbits);
+        n = count_ff(w.x) + count_ff(w.y) + count_ff(w.z) + count_ff(w.w);
+      }
+      unsigned total;
+      const unsigned before = wg_exclusive_scan(n, red, &total);
+      if (live) {
+        size_t o = (size_t)wi * 4 + ffsum[(size_t)img * p.nbchunk + c] + before;
+        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          if ((size_t)wi * 4 + j < nbytes) {
+            const unsigned byte = (ww[j >> 2] >> (24 - 8 * (j & 3))) & 0xff;
+            if (o < cap) slot[o] = (uint8_t)byte;
+            ++o;
+            if (byte == 0xff) {
+              if (o < cap) slot[o] = 0;
+              ++o;
+            }
+          }
+        }
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      const size_t len = (size_t)nbytes + tot[(size_t)img * 2 + 1] + 2;
+      const bool fits = len <= cap;
+      if (fits) {
+        slot[len - 2] = 0xff;
+        slot[len - 1] = 0xd9;
+      }
+      lens[img] = fits ? (int32_t)len : 0;
+      err[img] = fits ? 0 : 1;
+    }
+  }
+}
+
+}  // namespace
+
+#define JPEG_ENC_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2581110 coded blocks per image"
+
+extern "C" int sgic_jpeg_encode_cap(int H, int W, int subsampling, size_t *cap) {
+  SGIC_REQUIRE(cap != nullptr, "null output");
+  EPlan p;
+  SGIC_REQUIRE(make_plan(1, H, W, subsampling, &p), JPEG_ENC_LIMITS);
+  *cap = p.cap;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_jpeg_encode_work_bytes(int B, int H, int W, int subsampling, size_t *bytes) {
+  SGIC_REQUIRE(bytes != nullptr, "null output");
+  EPlan p;
+  SGIC_REQUIRE(make_plan(B, H, W, subsampling, &p), JPEG_ENC_LIMITS);
+  *bytes = p.bytes;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_jpeg_encode_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt, uint8_t *d_work,
+                                      size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err,
+                                      sgic_stream_t stream) {
+  EPlan p;
+  SGIC_REQUIRE(make_plan(B, H, W, subsampling, &p), JPEG_ENC_LIMITS);
+  SGIC_REQUIRE(d_rgb && h_qt && d_work && d_out && d_len && d_err, "null pointer");
+  SGIC_REQUIRE(((uintptr_t)d_work & 15) == 0, "the workspace must be 16-byte aligned");
+  SGIC_REQUIRE(((uintptr_t)h_qt & 1) == 0 && ((uintptr_t)d_len & 3) == 0 && ((uintptr_t)d_err & 3) == 0, "misaligned pointer");
+  SGIC_REQUIRE(work_bytes >= p.bytes, "the workspace is smaller than sgic_jpeg_encode_work_bytes says");
+  SGIC_REQUIRE(cap >= p.cap && cap <= 0x7fffffff, "the slots are smaller than sgic_jpeg_encode_cap says");
+  for (size_t i = 0; i < (size_t)B * 128; ++i) SGIC_REQUIRE(h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
+  hipStream_t st = to_stream(stream);
+  int16_t *coef = reinterpret_cast<int16_t *>(d_work);
+  uint16_t *qt = reinterpret_cast<uint16_t *>(d_work + p.off_qt);
+  uint32_t *local = reinterpret_cast<uint32_t *>(d_work + p.off_local);
+  uint32_t *csum = reinterpret_cast<uint32_t *>(d_work + p.off_csum);
+  uint32_t *bits = reinterpret_cast<uint32_t *>(d_work + p.off_bits);
+  uint32_t *ffsum = reinterpret_cast<uint32_t *>(d_work + p.off_ffsum);
+  uint32_t *tot = reinterpret_cast<uint32_t *>(d_work + p.off_tot);
+  SGIC_HIP(hipMemcpyAsync(qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+  SGIC_HIP(hipMemsetAsync(bits, 0, (size_t)B * p.words * sizeof(uint32_t), st));
+  const unsigned gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+  const dim3 gblocks(p.nchunk, gy), gbytes(p.nbchunk < MAX_CHUNK_GRID ? p.nbchunk : MAX_CHUNK_GRID, gy);
+  jpeg_enc_coef_kernel<<<gblocks, NT, 0, st>>>(d_rgb, qt, coef, p);
+  jpeg_enc_bits_kernel<<<gblocks, NT, 0, st>>>(coef, local, csum, p);
+  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(csum, p.nchunk, p.nchunk, tot, 0, 0, B);
+  jpeg_enc_pack_kernel<<<gblocks, NT, 0, st>>>(coef, local, csum, bits, p);
+  jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, p);
+  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(ffsum, p.nbchunk, 0, tot, 1, 1, B);
+  jpeg_enc_emit_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, d_out, cap, d_len, d_err, p);
+  return sgic::check_launch("sgic_jpeg_encode_batch");
+}

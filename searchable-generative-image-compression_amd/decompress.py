@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Counterpart of the reference driver src/decompress.py (same flags; writes save_dir/results/<stem>.png),
-running the MI355X decode path.  Files with identical shapes are decoded as one batch."""
+running the MI355X decode path.  Files with identical shapes are decoded as one batch.  --format jpg writes baseline JPEG files
+encoded on the GPU instead (jpeg_enc: the bytes Pillow's save(quality, subsampling) would write for the same pixels)."""
 import argparse
 import os
 import sys
@@ -22,6 +23,11 @@ def save_png(x_chw_01, path):
     Image.fromarray(to_u8_hwc(x_chw_01)).save(path)
 
 
+def _write_bytes(path, data):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--base_config", type=str, default=None)
@@ -31,7 +37,12 @@ def main(argv=None):
     ap.add_argument("--gpu_idx", type=int, default=0)
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--format", choices=("png", "jpg"), default="png", help="results as PNG (host zlib) or as JPEG encoded on the GPU")
+    ap.add_argument("--quality", type=int, default=90, help="JPEG quality, 1..100 (--format jpg)")
+    ap.add_argument("--subsampling", type=int, choices=(0, 1, 2), default=2, help="JPEG chroma layout: 0 4:4:4, 1 4:2:2, 2 4:2:0")
     args = ap.parse_args(argv)
+    if not 1 <= args.quality <= 100:
+        ap.error("--quality must be in 1..100")
 
     from . import weights as W
     from .codec import Codec
@@ -66,13 +77,25 @@ def main(argv=None):
             for s in range(0, len(idxs), args.batch_size):
                 chunk = idxs[s:s + args.batch_size]
                 x_hat = model.decode_batch([items[i][1] for i in chunk])
+                crops = {}      # --format jpg: the u8 images of this batch by cropped size, still on the device
                 for j, i in enumerate(chunk):
                     fp, _, header = items[i]
                     pl, pr, pt, pb = header.get("padding", [0, 0, 0, 0])
                     H, Wd = x_hat.shape[2] - pt - pb, x_hat.shape[3] - pl - pr   # negative-pad crop (decompress.py:110-112)
-                    a = to_u8_hwc(x_hat[j, :, pt:pt + H, pl:pl + Wd].clamp(-1, 1) * 0.5 + 0.5)
-                    path = os.path.join(out_dir, os.path.splitext(os.path.basename(fp))[0] + ".png")
+                    x01 = x_hat[j, :, pt:pt + H, pl:pl + Wd].clamp(-1, 1) * 0.5 + 0.5
+                    stem = os.path.splitext(os.path.basename(fp))[0]
+                    if args.format == "jpg":
+                        from .evaluate import to_u8_hwc_device
+                        crops.setdefault((H, Wd), []).append((os.path.join(out_dir, stem + ".jpg"), to_u8_hwc_device(x01)))
+                        continue
+                    a = to_u8_hwc(x01)
+                    path = os.path.join(out_dir, stem + ".png")
                     pending.append(pool.submit(lambda arr, p: Image.fromarray(arr).save(p), a, path))
+                for members in crops.values():       # one encode per distinct cropped size; only the coded bytes cross the bus
+                    from . import jpeg_enc
+                    files = jpeg_enc.encode_batch(torch.stack([m[1] for m in members]), args.quality, args.subsampling)
+                    for (path, _), data in zip(members, files):
+                        pending.append(pool.submit(_write_bytes, path, data))
         for f in pending:
             f.result()
     return 0

@@ -6,6 +6,12 @@
                                                                 on the device and no PNG is written)
   evaluate.py --originals imgs --recon_dir out/results          compares two folders; no model is built (--bitstreams adds the rate)
 
+  evaluate.py ... --bitstreams out/bitstreams --anchor jpeg      adds a JPEG anchor at matched rate to every record: the original is
+                                                                encoded on the GPU at qualities 1..95 (jpeg_enc), the largest
+                                                                quality whose file is not larger than the container is kept, decoded
+                                                                on the GPU (jpeg.JpegBatch) and measured like the reconstruction
+  evaluate.py ... --anchor_quality Q                            the anchor at a fixed quality (needs no --bitstreams)
+
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
 import argparse
@@ -56,8 +62,43 @@ def summarise(records):
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
     with np.errstate(divide="ignore"):
         db = None if ms is None else float(0.0 - 10.0 * np.log10(1.0 - ms))
-    return {"images": len(records), "bpp": mean([r["bpp"] for r in records if r["bpp"] is not None]),
-            "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
+    out = {"images": len(records), "bpp": mean([r["bpp"] for r in records if r["bpp"] is not None]),
+           "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
+    anchors = [r["anchor"] for r in records if "anchor" in r]
+    if anchors:      # the same means over the anchors; over_rate counts the images whose smallest JPEG is larger than the container
+        ams = mean([a["ms_ssim"] for a in anchors if a["ms_ssim"] is not None])
+        with np.errstate(divide="ignore"):
+            adb = None if ams is None else float(0.0 - 10.0 * np.log10(1.0 - ams))
+        out.update({"anchor_bpp": mean([a["bpp"] for a in anchors]),
+                    "anchor_psnr": mean([a["psnr"] for a in anchors if isinstance(a["psnr"], float)]), "anchor_ms_ssim": ams,
+                    "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
+    return out
+
+
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None):
+    """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
+    bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
+    jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
+    on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back."""
+    from . import jpeg, jpeg_enc, quality
+    B, H, W, _ = a_u8.shape
+    if fixed_quality is None:
+        sizes = jpeg_enc.ladder_sizes(a_u8, subsampling)
+        picks = [jpeg_enc.pick_quality(dict(zip(jpeg_enc.LADDER, (int(v) for v in sizes[j]))), budgets[j]) for j in range(B)]
+    else:
+        picks = [(int(fixed_quality), None)] * B
+    files = jpeg_enc.encode_batch(a_u8, [q for q, _ in picks], subsampling)
+    m = quality.measure(a_u8, jpeg.JpegBatch(files).decode(a_u8.device))
+    out = []
+    for j, ((q, over), data) in enumerate(zip(picks, files)):
+        if over is None:      # a fixed quality: over the rate if the container is known and smaller
+            over = budgets[j] is not None and len(data) > budgets[j]
+        rec = {"codec": "jpeg", "quality": q, "subsampling": int(subsampling), "bytes": len(data), "bpp": 8 * len(data) / (H * W)}
+        for k in FIELDS:
+            rec[k] = None if m[k] is None else _json_number(m[k][j])
+        rec["over_rate"] = bool(over)
+        out.append(rec)
+    return out
 
 
 def main(argv=None):
@@ -70,9 +111,19 @@ def main(argv=None):
     ap.add_argument("--gpu_idx", type=int, default=0)
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--anchor", choices=("jpeg",), default=None,
+                    help="add a conventional codec at matched rate to every record: the largest JPEG quality in 1..95 whose file is "
+                         "not larger than the container (needs --bitstreams for the sizes)")
+    ap.add_argument("--anchor_subsampling", type=int, choices=(0, 1, 2), default=2, help="the anchor's chroma layout (Pillow's values)")
+    ap.add_argument("--anchor_quality", type=int, default=None, help="fix the anchor's quality instead of searching (implies --anchor jpeg)")
     args = ap.parse_args(argv)
     if not args.bitstreams and not args.recon_dir:
         ap.error("give --bitstreams, --recon_dir or both")
+    if args.anchor_quality is not None and not 1 <= args.anchor_quality <= 100:
+        ap.error("--anchor_quality must be in 1..100")
+    if args.anchor and args.anchor_quality is None and not args.bitstreams:
+        ap.error("--anchor jpeg matches the rate of the containers: give --bitstreams, or fix the quality with --anchor_quality")
+    anchor = args.anchor or ("jpeg" if args.anchor_quality is not None else None)
     if args.batch_size < 1:
         ap.error("--batch_size must be at least 1")
 
@@ -111,11 +162,15 @@ def main(argv=None):
         for (H, W, _), members in groups.items():
             a = torch.from_numpy(np.stack([m[1] for m in members])).to(dev)
             m = quality.measure(a, torch.stack([m[2] for m in members]))
+            sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality) if anchor else None
             for j, (stem, _, _) in enumerate(members):
-                nbytes = os.path.getsize(containers[stem]) if stem in containers else None
+                nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
                 for k in FIELDS:
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
+                if anchors:
+                    rec["anchor"] = anchors[j]
                 records.append(rec)
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
