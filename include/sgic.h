@@ -425,6 +425,32 @@ int sgic_quality_u8_work_bytes(int B, int H, int W, size_t *bytes);
 int sgic_quality_u8(const uint8_t *d_a, const uint8_t *d_b, int B, int H, int W, uint8_t *d_work, size_t work_bytes,
                     int64_t *d_sse, double *d_levels, sgic_stream_t stream);
 
+/* LPIPS with the VGG16 trunk (lpips.LpipsVGG, evaluate.py --lpips_ckpt; the reference's taming/modules/losses/lpips.py): the
+ * memory-bound glue around sgic_conv3x3_split3_f32, which runs the thirteen convolutions.  All planes are slice-major (a_packed = 1).
+ *
+ * sgic_lpips_input_split3: d_img (B, H, W, 3) u8 -> the interior of the zero-halo planes [3][1][total_images (H+2) (W+2)][32] of
+ * images image_offset .. image_offset + B - 1 (two calls fill one buffer with both sides of the pairs).  Per channel c, each step one
+ * IEEE fp32 operation: x = float(u) / 255 * 2 - 1; y = (x - shift_c) / scale_c with shift = (-.030, -.088, -.188), scale = (.458,
+ * .448, .450).  Channels 3..31 are written as zero; the border is not written.
+ *
+ * sgic_relu_pool_halo_split3: d_in (B H W, C) fp32 -> relu -> (pool2x2: max over 2 x 2, stride 2, an odd last row / column dropped)
+ * -> the interior of the planes [3][C / 32][B (H'+2) (W'+2)][32]; only the interior is written (the sgic_halo_copy_split3 contract).
+ *
+ * sgic_lpips_head: d_feat (2 B H W, C) fp32 BEFORE relu, image pair b = rows of image b and of image B + b; d_w (C).  With f =
+ * relu(feat), n = sqrt(sum_c f_c^2), u = f * (1 / (n + 1e-10)): d_d[b] = mean over pixels of sum_c w_c (u_a - u_b)^2, in fp64 (an
+ * all-zero pixel gives u = 0).  One partial per workgroup in d_work, added in a fixed order by a last kernel: no float atomics, the
+ * same input gives the same bits.  d_work: at least the *bytes sgic_lpips_head_work_bytes returns (host-only, takes no stream).
+ *
+ * SGIC_EINVAL before any launch: a null pointer, B < 1 (head: B > 65535), H or W < 1, C % 32 != 0, a buffer that is not 16-byte
+ * aligned, image slots outside total_images, a pool of fewer than two rows or columns, a workspace that is too small. */
+int sgic_lpips_input_split3(const uint8_t *d_img, int B, int H, int W, int total_images, int image_offset, uint16_t *d_halo_planes,
+                            sgic_stream_t stream);
+int sgic_relu_pool_halo_split3(const float *d_in, int B, int H, int W, int C, int pool2x2, uint16_t *d_halo_planes,
+                               sgic_stream_t stream);
+int sgic_lpips_head_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_lpips_head(const float *d_feat, const float *d_w, int B, int H, int W, int C, uint8_t *d_work, size_t work_bytes,
+                    double *d_d, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

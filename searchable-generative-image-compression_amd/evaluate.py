@@ -11,6 +11,10 @@
                                                                 quality whose file is not larger than the container is kept, decoded
                                                                 on the GPU (jpeg.JpegBatch) and measured like the reconstruction
   evaluate.py ... --anchor_quality Q                            the anchor at a fixed quality (needs no --bitstreams)
+  evaluate.py ... --lpips_ckpt P [P ...]                        adds "lpips" to every record, to its anchor and to the summary: LPIPS
+                                                                with the VGG16 trunk (lpips.LpipsVGG) on the same u8 tensors; P: one
+                                                                or more state dict files that together hold the trunk and the lin
+                                                                layers (lpips.load_weights)
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -56,7 +60,8 @@ def _json_number(v):
 
 
 def summarise(records):
-    """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim"""
+    """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
+    lpips when the records carry it"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
@@ -64,6 +69,8 @@ def summarise(records):
         db = None if ms is None else float(0.0 - 10.0 * np.log10(1.0 - ms))
     out = {"images": len(records), "bpp": mean([r["bpp"] for r in records if r["bpp"] is not None]),
            "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
+    if any("lpips" in r for r in records):
+        out["lpips"] = mean([r["lpips"] for r in records if r.get("lpips") is not None])
     anchors = [r["anchor"] for r in records if "anchor" in r]
     if anchors:      # the same means over the anchors; over_rate counts the images whose smallest JPEG is larger than the container
         ams = mean([a["ms_ssim"] for a in anchors if a["ms_ssim"] is not None])
@@ -72,14 +79,17 @@ def summarise(records):
         out.update({"anchor_bpp": mean([a["bpp"] for a in anchors]),
                     "anchor_psnr": mean([a["psnr"] for a in anchors if isinstance(a["psnr"], float)]), "anchor_ms_ssim": ams,
                     "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
+        if any("lpips" in a for a in anchors):
+            out["anchor_lpips"] = mean([a["lpips"] for a in anchors if a.get("lpips") is not None])
     return out
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None):
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
-    on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back."""
+    on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back.
+    lpips_model (lpips.LpipsVGG): every record also carries "lpips" of the decoded anchor against the original."""
     from . import jpeg, jpeg_enc, quality
     B, H, W, _ = a_u8.shape
     if fixed_quality is None:
@@ -88,7 +98,9 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None):
     else:
         picks = [(int(fixed_quality), None)] * B
     files = jpeg_enc.encode_batch(a_u8, [q for q, _ in picks], subsampling)
-    m = quality.measure(a_u8, jpeg.JpegBatch(files).decode(a_u8.device))
+    decoded = jpeg.JpegBatch(files).decode(a_u8.device)
+    m = quality.measure(a_u8, decoded)
+    lp = lpips_model.measure(a_u8, decoded) if lpips_model is not None else None
     out = []
     for j, ((q, over), data) in enumerate(zip(picks, files)):
         if over is None:      # a fixed quality: over the rate if the container is known and smaller
@@ -96,6 +108,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None):
         rec = {"codec": "jpeg", "quality": q, "subsampling": int(subsampling), "bytes": len(data), "bpp": 8 * len(data) / (H * W)}
         for k in FIELDS:
             rec[k] = None if m[k] is None else _json_number(m[k][j])
+        if lpips_model is not None:
+            rec["lpips"] = None if lp is None else float(lp[0][j])
         rec["over_rate"] = bool(over)
         out.append(rec)
     return out
@@ -116,6 +130,8 @@ def main(argv=None):
                          "not larger than the container (needs --bitstreams for the sizes)")
     ap.add_argument("--anchor_subsampling", type=int, choices=(0, 1, 2), default=2, help="the anchor's chroma layout (Pillow's values)")
     ap.add_argument("--anchor_quality", type=int, default=None, help="fix the anchor's quality instead of searching (implies --anchor jpeg)")
+    ap.add_argument("--lpips_ckpt", type=str, nargs="+", default=None,
+                    help="state dict file(s) with the VGG16 trunk and the lin layers of LPIPS: adds \"lpips\" to every record")
     args = ap.parse_args(argv)
     if not args.bitstreams and not args.recon_dir:
         ap.error("give --bitstreams, --recon_dir or both")
@@ -132,6 +148,10 @@ def main(argv=None):
 
     torch.cuda.set_device(args.gpu_idx)
     dev = torch.device("cuda", args.gpu_idx)
+    lpips_model = None
+    if args.lpips_ckpt:
+        from .lpips import LpipsVGG
+        lpips_model = LpipsVGG(args.lpips_ckpt, dev)
     originals = by_stem(glob(os.path.join(args.originals, "*.*")))
     containers = by_stem(glob(os.path.join(args.bitstreams, "*.c2df"))) if args.bitstreams else {}
     recons = by_stem(glob(os.path.join(args.recon_dir, "*.*"))) if args.recon_dir else None
@@ -161,14 +181,18 @@ def main(argv=None):
                 groups.setdefault(org.shape, []).append((stem, org, rec))
         for (H, W, _), members in groups.items():
             a = torch.from_numpy(np.stack([m[1] for m in members])).to(dev)
-            m = quality.measure(a, torch.stack([m[2] for m in members]))
+            b = torch.stack([m[2] for m in members])
+            m = quality.measure(a, b)
+            lp = lpips_model.measure(a, b) if lpips_model is not None else None
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
-            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality) if anchor else None
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model) if anchor else None
             for j, (stem, _, _) in enumerate(members):
                 nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
                 for k in FIELDS:
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
+                if lpips_model is not None:
+                    rec["lpips"] = None if lp is None else float(lp[0][j])
                 if anchors:
                     rec["anchor"] = anchors[j]
                 records.append(rec)

@@ -1234,6 +1234,45 @@ def quality_u8(a, b):
     return sse, levels
 
 
+def lpips_input(img_u8, hp, image_offset=0):
+    """the LPIPS input layer (csrc/lpips.hip): img_u8 (B, H, W, 3) u8 -> the interior of images image_offset .. image_offset+B-1 of
+    hp, a HaloPlanes of (total images, H, W, 32) from halo_planes_buffer; channels 3..31 are zero.  No synchronisation."""
+    require_gpu()
+    assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3
+    B, H, W, _ = img_u8.shape
+    assert (hp.H, hp.W, hp.C) == (H, W, 32) and 0 <= image_offset and image_offset + B <= hp.B, ((hp.B, hp.H, hp.W, hp.C), img_u8.shape)
+    call("sgic_lpips_input_split3", _p(img_u8), B, H, W, hp.B, int(image_offset), _p(hp.t))
+    return hp
+
+
+def relu_pool_halo(x, B, H, W, C, pool=False):
+    """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU, a 2x2 / stride 2 max-pool when pool (an odd last row or
+    column is dropped) -> the next 3x3 convolution's zero-halo operand planes (HaloPlanes; csrc/lpips.hip).  C % 32 == 0."""
+    require_gpu()
+    x, ldx = _rows(x)
+    assert ldx == C and x.shape == (B * H * W, C), (x.shape, (B, H, W, C))
+    hp = halo_planes_buffer(x.device, B, H // 2 if pool else H, W // 2 if pool else W, C)
+    call("sgic_relu_pool_halo_split3", _p(x), B, H, W, C, int(bool(pool)), _p(hp.t))
+    return hp
+
+
+def lpips_head(feat, w, B, H, W, out=None):
+    """one LPIPS tap (csrc/lpips.hip): feat (2*B*H*W, C) fp32 before its ReLU, the first B images against the last B; w (C,) fp32
+    -> d (B,) float64 = the pixel mean of sum_c w_c (u_a - u_b)^2 over the unit-normalised ReLU features.  No synchronisation."""
+    require_gpu()
+    feat, ldf = _rows(feat)
+    C = feat.shape[1]
+    assert ldf == C and feat.shape[0] == 2 * B * H * W and w.shape == (C,) and w.is_contiguous() and w.dtype == torch.float32
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_lpips_head_work_bytes", B, H, W, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=feat.device)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=feat.device)
+    assert out.shape == (B,) and out.dtype == torch.float64 and out.is_contiguous()
+    call("sgic_lpips_head", _p(feat), _p(w), B, H, W, C, _p(work), ctypes.c_size_t(nbytes.value), _p(out))
+    return out
+
+
 def jpeg_encode(rgb_u8, tables, subsampling):
     """baseline JPEG encode of B equal-size images (csrc/jpeg_enc.hip): rgb_u8 (B, H, W, 3) u8, contiguous on the device; tables
     (B, 2, 64) u16 numpy array on the host (luma and chroma quantisation table of every image, natural order); subsampling 0 / 1 / 2
