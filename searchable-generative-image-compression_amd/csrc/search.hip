@@ -13,15 +13,20 @@
 // by rank and raises the threshold.  The threshold only moves at block-wide sync points, after which every later candidate has a
 // higher index than everything kept, so a strict `>` implements the tie rule.
 //
-// fp32 queries against the same codes (search_f32q_kernel, CodeIndex.search_vectors).  The query goes to fixed point,
+// fp32 queries against the same codes (F32Query, CodeIndex.search_vectors).  The query goes to fixed point,
 // Q = clamp(rint(q 2^22), -2^22, 2^22) (NaN -> 0), and is cut into balanced base-256 digits Q = 65536 d2 + 256 d1 + d0 with
 // d0, d1 in [-128, 127], d2 in [-64, 64]: three i8 planes, each laid out in LDS exactly like the u8 query tile, quantised in the
 // kernel's prologue.  One database fragment feeds three MFMAs, S_p = sum d_p a_d, and
 //   M = 2 (65536 S_2 + 256 S_1 + S_0) + sum Q  ==  sum Q (2 c_d - 255)
 // in int64 (|M| <= 2^22 255 D needs 41 bits at D = 2048).  Key = float(M) * r_d, score = key * 2^-22 (exact); the candidate
-// buffers, pruning, splits and the merge are those of the u8 kernel.  D <= 2048: three planes of a 16-query tile plus the
+// buffers, pruning, splits and the merge are those of the u8 queries.  D <= 2048: three planes of a 16-query tile plus the
 // candidate buffers at k = 128 take 120 KiB of the CU's 160 KiB of LDS, D = 4096 would not fit.
+//
+// The two query types (U8Query, F32Query) own the prologue, the step loop and the integer of a score; what happens to a score is
+// one of two kernels, each compiled for both: search_topk_kernel (candidate buffers) and search_range_kernel (append to a list).
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -32,7 +37,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int kMaxK = 128;
 constexpr int kCandPerIter = 64;   // 4 waves x 16 database rows
 constexpr int kMaxSplits = 2048;
-constexpr int kLdsBigTile = 80 * 1024;   // the 64-query tile is used only while two workgroups still fit a CU
+constexpr int kLdsBigTile = 80 * 1024;   // the wide query tile is used only while two workgroups still fit a CU
 
 __device__ __forceinline__ bool beats(float ka, int ia, float kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
 
@@ -85,125 +90,6 @@ __device__ __forceinline__ v4i to_i8x16(const uint4 &v) {   // sixteen u8 codes 
   return r;
 }
 
-template <int QF, int U>
-__global__ __launch_bounds__(256) void search_codes_kernel(const uint8_t *__restrict__ q, const float *__restrict__ r_q,
-                                                           const uint8_t *__restrict__ db, const float *__restrict__ r_db, int nq,
-                                                           int n, int D, int k, int rows_per_split, int splits, int final_out,
-                                                           float *__restrict__ out_key, int *__restrict__ out_idx) {
-  constexpr int QT = 16 * QF;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int steps = D >> 6;
-  const int cap = k + kCandPerIter;
-  v4i *A = reinterpret_cast<v4i *>(smem);   // [QF][steps][64 lanes] fragments
-  float *keys = reinterpret_cast<float *>(smem + (size_t)QT * D);
-  int *idxs = reinterpret_cast<int *>(keys + QT * cap);
-  int *cnt = idxs + QT * cap;
-  float *thr = reinterpret_cast<float *>(cnt + QT);
-  int *sq = reinterpret_cast<int *>(thr + QT);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int qbase = blockIdx.x * QT, split = blockIdx.y;
-
-  if (tid < QT) {
-    cnt[tid] = 0;
-    thr[tid] = -INFINITY;
-    sq[tid] = 0;
-  }
-  __syncthreads();
-  for (int i = tid; i < QF * steps * 64; i += 256) {   // one 16-byte fragment per (query fragment, step, lane)
-    const int ln = i & 63, t = i >> 6;
-    const int step = t % steps, f = t / steps;
-    const int row = f * 16 + (ln & 15);
-    int qi = qbase + row;
-    qi = qi < nq ? qi : nq - 1;
-    const uint4 v = *reinterpret_cast<const uint4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4));
-    atomicAdd(&sq[row], (int)sum_bytes16(v, 0u));
-    A[i] = to_i8x16(v);
-  }
-  __syncthreads();
-
-  int baseq[QF][4];
-  float thr_r[QF][4];
-#pragma unroll
-  for (int f = 0; f < QF; f++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      baseq[f][r] = 2 * (sq[f * 16 + 4 * (lane >> 4) + r] - 128 * D) + D;
-      thr_r[f][r] = -INFINITY;
-    }
-
-  const int row0 = split * rows_per_split;
-  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
-  for (int base = row0; base < row_end; base += kCandPerIter) {
-    const int my = base + wave * 16 + (lane & 15);
-    const int myc = my < n ? my : n - 1;
-    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
-    v4i acc[QF];
-#pragma unroll
-    for (int f = 0; f < QF; f++) acc[f] = v4i{0, 0, 0, 0};
-    unsigned ssum = 0;
-    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
-      uint4 bv[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        ssum = sum_bytes16(bv[u], ssum);
-        const v4i b = to_i8x16(bv[u]);
-#pragma unroll
-        for (int f = 0; f < QF; f++)
-          acc[f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(f * steps + s0 + u) * 64 + lane], b, acc[f], 0, 0, 0);
-      }
-    }
-    ssum += __shfl_xor(ssum, 16);
-    ssum += __shfl_xor(ssum, 32);
-    const int sd2 = 2 * ((int)ssum - 128 * D);
-    const float rd = r_db[myc];
-    const bool valid = my < row_end;
-    int any = 0;
-#pragma unroll
-    for (int f = 0; f < QF; f++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int N = 4 * acc[f][r] + baseq[f][r] + sd2;
-        const float key = (float)N * rd;
-        if (valid && key > thr_r[f][r]) {
-          const int ql = f * 16 + 4 * (lane >> 4) + r;
-          const int pos = atomicAdd(&cnt[ql], 1);
-          keys[ql * cap + pos] = key;
-          idxs[ql * cap + pos] = my;
-          any = 1;
-        }
-      }
-    if (__syncthreads_or(any)) {
-      for (int ql = wave; ql < QT; ql += 4) {
-        const int c = cnt[ql];
-        if (c > k) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int f = 0; f < QF; f++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) thr_r[f][r] = thr[f * 16 + 4 * (lane >> 4) + r];
-    }
-  }
-  __syncthreads();
-  for (int ql = wave; ql < QT; ql += 4) {
-    const int gq = qbase + ql;
-    if (gq >= nq) break;
-    int c = cnt[ql];
-    if (c > 0) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
-    c = c < k ? c : k;
-    const float rq = final_out ? r_q[gq] : 1.0f;
-    const size_t o = ((size_t)gq * splits + split) * k;
-    for (int j = lane; j < k; j += 64) {
-      const float key = j < c ? keys[ql * cap + j] : -INFINITY;
-      out_key[o + j] = final_out ? key * rq : key;
-      out_idx[o + j] = j < c ? idxs[ql * cap + j] : -1;
-    }
-  }
-}
-
 constexpr float kQScale = 4194304.0f;   // 2^22: 2^23 would push the top digit to 128 at q = 1
 constexpr int kMaxDimF32Q = 2048;
 
@@ -234,70 +120,110 @@ __device__ __forceinline__ int quantise16(const float4 *__restrict__ src, v4i &p
   return sum;
 }
 
-// search_codes_kernel with an fp32 query tile: three digit planes in LDS, three MFMAs per database fragment, int64 combine.
-// No byte sums of the database rows are needed (v_d = 2 a_d + 1 turns into the `+ sum Q` term).
-template <int QF, int U>
-__global__ __launch_bounds__(256) void search_f32q_kernel(const float *__restrict__ q, const uint8_t *__restrict__ db,
-                                                          const float *__restrict__ r_db, int nq, int n, int D, int k,
-                                                          int rows_per_split, int splits, int final_out, float *__restrict__ out_key,
-                                                          int *__restrict__ out_idx) {
-  constexpr int QT = 16 * QF;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int steps = D >> 6;
-  const int cap = k + kCandPerIter;
-  const int plane = QF * steps * 64;         // fragments per digit plane
-  v4i *A = reinterpret_cast<v4i *>(smem);   // [3 planes][QF][steps][64 lanes] fragments
-  float *keys = reinterpret_cast<float *>(smem + (size_t)3 * QT * D);
-  int *idxs = reinterpret_cast<int *>(keys + QT * cap);
-  unsigned long long *sq = reinterpret_cast<unsigned long long *>(idxs + QT * cap);   // sum Q per query: up to 2^33 at D = 2048
-  int *cnt = reinterpret_cast<int *>(sq + QT);
-  float *thr = reinterpret_cast<float *>(cnt + QT);
+// sixteen fp32 coordinates of one row -> its fragment in each of the three digit planes (`plane` fragments apart), and into sum Q
+__device__ __forceinline__ void stage_f32_fragment(const float *__restrict__ src, v4i *dst, int plane, unsigned long long *sum) {
+  v4i p0, p1, p2;
+  const int s = quantise16(reinterpret_cast<const float4 *>(src), p0, p1, p2);
+  atomicAdd(sum, (unsigned long long)(long long)s);
+  dst[0] = p0;
+  dst[plane] = p1;
+  dst[2 * plane] = p2;
+}
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+// What differs between the query types.  LDS of a tile of QT = 16 QF queries: kPlanes planes of [QF][steps][64 lanes] fragments
+// and one Sum per query.  stage() fills both (query rows >= nq repeat row nq - 1), term() is a lane's share of a query's Sum,
+// accumulate() adds the steps of this lane's database row (bp: its first fragment) into acc and returns the row's own term,
+// key() is the ranking key of (fragment f, register r), scale() takes a key to the reported score.
+struct U8Query {
+  typedef uint8_t T;
+  typedef int Sum;    // s_q + 128 D, the byte sum
+  typedef int Term;   // 2 s_q + D
+  static constexpr int kPlanes = 1, kWideQF = 4;
+  static constexpr bool kSelfJoin = true;
 
-  if (tid < QT) {
-    cnt[tid] = 0;
-    thr[tid] = -INFINITY;
-    sq[tid] = 0;
-  }
-  __syncthreads();
-  for (int i = tid; i < plane; i += 256) {   // sixteen coordinates -> one fragment in each plane per (query fragment, step, lane)
-    const int ln = i & 63, t = i >> 6;
-    const int step = t % steps, f = t / steps;
-    const int row = f * 16 + (ln & 15);
-    int qi = qbase + row;
-    qi = qi < nq ? qi : nq - 1;
-    v4i p0, p1, p2;
-    const int s = quantise16(reinterpret_cast<const float4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4)), p0, p1, p2);
-    atomicAdd(&sq[row], (unsigned long long)(long long)s);
-    A[i] = p0;
-    A[plane + i] = p1;
-    A[2 * plane + i] = p2;
-  }
-  __syncthreads();
-
-  long long sumq[QF][4];
-  float thr_r[QF][4];
-#pragma unroll
-  for (int f = 0; f < QF; f++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      sumq[f][r] = (long long)sq[f * 16 + 4 * (lane >> 4) + r];
-      thr_r[f][r] = -INFINITY;
+  template <int QF>
+  static __device__ __forceinline__ void stage(const T *__restrict__ q, int nq, int qbase, int D, int tid, v4i *A, Sum *sq) {
+    const int steps = D >> 6;
+    if (tid < 16 * QF) sq[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < QF * steps * 64; i += 256) {   // one 16-byte fragment per (query fragment, step, lane)
+      const int ln = i & 63, t = i >> 6;
+      const int step = t % steps, f = t / steps;
+      const int row = f * 16 + (ln & 15);
+      int qi = qbase + row;
+      qi = qi < nq ? qi : nq - 1;
+      const uint4 v = *reinterpret_cast<const uint4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4));
+      atomicAdd(&sq[row], (int)sum_bytes16(v, 0u));
+      A[i] = to_i8x16(v);
     }
+    __syncthreads();
+  }
 
-  const int row0 = split * rows_per_split;
-  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
-  for (int base = row0; base < row_end; base += kCandPerIter) {
-    const int my = base + wave * 16 + (lane & 15);
-    const int myc = my < n ? my : n - 1;
-    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
-    v4i acc[3][QF];
+  static __device__ __forceinline__ Term term(const Sum *sq, int ql, int D) { return 2 * (sq[ql] - 128 * D) + D; }
+
+  template <int QF, int U>
+  static __device__ __forceinline__ int accumulate(const v4i *A, const uint4 *bp, int D, int lane, v4i (&acc)[kPlanes][QF]) {
+    const int steps = D >> 6;
+    unsigned ssum = 0;
+    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
+      uint4 bv[U];
 #pragma unroll
-    for (int p = 0; p < 3; p++)
+      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
 #pragma unroll
-      for (int f = 0; f < QF; f++) acc[p][f] = v4i{0, 0, 0, 0};
+      for (int u = 0; u < U; u++) {
+        ssum = sum_bytes16(bv[u], ssum);
+        const v4i b = to_i8x16(bv[u]);
+#pragma unroll
+        for (int f = 0; f < QF; f++)
+          acc[0][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(f * steps + s0 + u) * 64 + lane], b, acc[0][f], 0, 0, 0);
+      }
+    }
+    ssum += __shfl_xor(ssum, 16);
+    ssum += __shfl_xor(ssum, 32);
+    return 2 * ((int)ssum - 128 * D);   // 2 s_d
+  }
+
+  template <int QF>
+  static __device__ __forceinline__ float key(const v4i (&acc)[kPlanes][QF], int f, int r, Term tq, int td, float rd) {
+    const int N = 4 * acc[0][f][r] + tq + td;
+    return (float)N * rd;
+  }
+
+  static __device__ __forceinline__ float scale(const float *__restrict__ r_q, int gq) { return r_q[gq]; }
+};
+
+// No byte sums of the database rows are needed (v_d = 2 a_d + 1 turns into the `+ sum Q` term), and no self-join: fp32 queries are
+// not the database.
+struct F32Query {
+  typedef float T;
+  typedef unsigned long long Sum;   // sum Q: up to 2^33 at D = 2048
+  typedef long long Term;
+  static constexpr int kPlanes = 3, kWideQF = 2;
+  static constexpr bool kSelfJoin = false;
+
+  template <int QF>
+  static __device__ __forceinline__ void stage(const T *__restrict__ q, int nq, int qbase, int D, int tid, v4i *A, Sum *sq) {
+    const int steps = D >> 6;
+    const int plane = QF * steps * 64;   // fragments per digit plane
+    if (tid < 16 * QF) sq[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < plane; i += 256) {   // sixteen coordinates -> one fragment in each plane per (query fragment, step, lane)
+      const int ln = i & 63, t = i >> 6;
+      const int step = t % steps, f = t / steps;
+      const int row = f * 16 + (ln & 15);
+      int qi = qbase + row;
+      qi = qi < nq ? qi : nq - 1;
+      stage_f32_fragment(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4), A + i, plane, &sq[row]);
+    }
+    __syncthreads();
+  }
+
+  static __device__ __forceinline__ Term term(const Sum *sq, int ql, int) { return (long long)sq[ql]; }
+
+  template <int QF, int U>
+  static __device__ __forceinline__ int accumulate(const v4i *A, const uint4 *bp, int D, int lane, v4i (&acc)[kPlanes][QF]) {
+    const int steps = D >> 6;
+    const int plane = QF * steps * 64;
     for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
       uint4 bv[U];
 #pragma unroll
@@ -306,12 +232,71 @@ __global__ __launch_bounds__(256) void search_f32q_kernel(const float *__restric
       for (int u = 0; u < U; u++) {
         const v4i b = to_i8x16(bv[u]);
 #pragma unroll
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p < kPlanes; p++)
 #pragma unroll
           for (int f = 0; f < QF; f++)
             acc[p][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[p * plane + (f * steps + s0 + u) * 64 + lane], b, acc[p][f], 0, 0, 0);
       }
     }
+    return 0;
+  }
+
+  template <int QF>
+  static __device__ __forceinline__ float key(const v4i (&acc)[kPlanes][QF], int f, int r, Term tq, int, float rd) {
+    const long long M = 2 * (65536LL * acc[2][f][r] + 256LL * acc[1][f][r] + acc[0][f][r]) + tq;
+    return (float)M * rd;
+  }
+
+  static __device__ __forceinline__ float scale(const float *__restrict__, int) { return 1.0f / kQScale; }
+};
+
+// Top-k: r_q is read for u8 queries only (fp32 queries pass nullptr).  LDS: the query tile, the candidate buffers, then the sums.
+template <class Query, int QF, int U>
+__global__ __launch_bounds__(256) void search_topk_kernel(const typename Query::T *__restrict__ q, const float *__restrict__ r_q,
+                                                          const uint8_t *__restrict__ db, const float *__restrict__ r_db, int nq,
+                                                          int n, int D, int k, int rows_per_split, int splits, int final_out,
+                                                          float *__restrict__ out_key, int *__restrict__ out_idx) {
+  constexpr int QT = 16 * QF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int cap = k + kCandPerIter;
+  v4i *A = reinterpret_cast<v4i *>(smem);
+  float *keys = reinterpret_cast<float *>(smem + (size_t)Query::kPlanes * QT * D);
+  int *idxs = reinterpret_cast<int *>(keys + QT * cap);
+  int *cnt = idxs + QT * cap;
+  float *thr = reinterpret_cast<float *>(cnt + QT);
+  typename Query::Sum *sq = reinterpret_cast<typename Query::Sum *>(thr + QT);   // 8-byte aligned: every block before it is
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+
+  if (tid < QT) {
+    cnt[tid] = 0;
+    thr[tid] = -INFINITY;
+  }
+  Query::template stage<QF>(q, nq, qbase, D, tid, A, sq);
+
+  typename Query::Term tq[QF][4];
+  float thr_r[QF][4];
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      tq[f][r] = Query::term(sq, f * 16 + 4 * (lane >> 4) + r, D);
+      thr_r[f][r] = -INFINITY;
+    }
+
+  const int row0 = split * rows_per_split;
+  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
+  for (int base = row0; base < row_end; base += kCandPerIter) {
+    const int my = base + wave * 16 + (lane & 15);
+    v4i acc[Query::kPlanes][QF];   // zeroed here, not in accumulate(): through its reference that costs registers (an occupancy step)
+#pragma unroll
+    for (int p = 0; p < Query::kPlanes; p++)
+#pragma unroll
+      for (int f = 0; f < QF; f++) acc[p][f] = v4i{0, 0, 0, 0};
+    const int myc = my < n ? my : n - 1;   // rows >= n are clamped for the loads and masked below
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    const int td = Query::template accumulate<QF, U>(A, bp, D, lane, acc);
     const float rd = r_db[myc];
     const bool valid = my < row_end;
     int any = 0;
@@ -319,8 +304,7 @@ __global__ __launch_bounds__(256) void search_f32q_kernel(const float *__restric
     for (int f = 0; f < QF; f++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const long long M = 2 * (65536LL * acc[2][f][r] + 256LL * acc[1][f][r] + acc[0][f][r]) + sumq[f][r];
-        const float key = (float)M * rd;
+        const float key = Query::key(acc, f, r, tq[f][r], td, rd);
         if (valid && key > thr_r[f][r]) {
           const int ql = f * 16 + 4 * (lane >> 4) + r;
           const int pos = atomicAdd(&cnt[ql], 1);
@@ -348,10 +332,11 @@ __global__ __launch_bounds__(256) void search_f32q_kernel(const float *__restric
     int c = cnt[ql];
     if (c > 0) prune_wave(keys + ql * cap, idxs + ql * cap, c, k, lane, &cnt[ql], &thr[ql]);
     c = c < k ? c : k;
+    const float rq = final_out ? Query::scale(r_q, gq) : 1.0f;
     const size_t o = ((size_t)gq * splits + split) * k;
     for (int j = lane; j < k; j += 64) {
       const float key = j < c ? keys[ql * cap + j] : -INFINITY;
-      out_key[o + j] = final_out ? key * (1.0f / kQScale) : key;
+      out_key[o + j] = final_out ? key * rq : key;
       out_idx[o + j] = j < c ? idxs[ql * cap + j] : -1;
     }
   }
@@ -399,52 +384,41 @@ __global__ __launch_bounds__(256) void search_merge_kernel(const float *__restri
   }
 }
 
-// Threshold (range) search: search_codes_kernel's tiles and integer score, no top-k.  Every (query, database row) pair with
-//   score = (float(N) * r_d) * r_q >= T      (fp32; the bits sgic_search_codes_u8 reports)
+// Threshold (range) search: search_topk_kernel's tiles and integer score, no top-k.  Every (query, database row) pair with
+//   score = key * scale >= T      (fp32; the bits the top-k search reports: (float(N) * r_d) * r_q, (float(M) * r_d) * 2^-22)
 // is appended to one global list (q, d, score) through one 64-bit counter.  A wave that has hits in a step takes one atomic add for
 // all of them (ballots + lane ranks place the entries); a step without hits costs one wave-uniform branch.  The counter receives
 // every hit, an entry is stored only at a position < capacity: the count stays exact after an overflow and nothing is written past
 // capacity.  Query rows >= nq and database rows >= row_end are clamped for the loads and masked where entries are emitted.
-// self_join (q == db): only d > q is emitted, and the row loop starts at the first 64-row step that can hold a d > qbase, so
-// the tiles wholly at or below the diagonal are never computed; the diagonal tile is masked per element.
-template <int QF, int U>
-__global__ __launch_bounds__(256, 4) void search_range_kernel(const uint8_t *__restrict__ q, const float *__restrict__ r_q,
-                                                           const uint8_t *__restrict__ db, const float *__restrict__ r_db, int nq,
-                                                           int n, int D, int rows_per_split, float threshold, int self_join,
-                                                           unsigned long long capacity, unsigned long long *__restrict__ count,
-                                                           int *__restrict__ out_q, int *__restrict__ out_d,
-                                                           float *__restrict__ out_score) {
+// self_join (q == db, u8 queries only): only d > q is emitted, and the row loop starts at the first 64-row step that can hold a
+// d > qbase, so the tiles wholly at or below the diagonal are never computed; the diagonal tile is masked per element.
+// LDS holds the query tile and its sums only.
+template <class Query, int QF, int U>
+__global__ __launch_bounds__(256, 4) void search_range_kernel(const typename Query::T *__restrict__ q, const float *__restrict__ r_q,
+                                                              const uint8_t *__restrict__ db, const float *__restrict__ r_db, int nq,
+                                                              int n, int D, int rows_per_split, float threshold, int self_join,
+                                                              unsigned long long capacity, unsigned long long *__restrict__ count,
+                                                              int *__restrict__ out_q, int *__restrict__ out_d,
+                                                              float *__restrict__ out_score) {
   constexpr int QT = 16 * QF;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int steps = D >> 6;
-  v4i *A = reinterpret_cast<v4i *>(smem);   // [QF][steps][64 lanes] fragments
-  int *sq = reinterpret_cast<int *>(smem + (size_t)QT * D);
+  v4i *A = reinterpret_cast<v4i *>(smem);
+  typename Query::Sum *sq = reinterpret_cast<typename Query::Sum *>(smem + (size_t)Query::kPlanes * QT * D);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int qbase = blockIdx.x * QT, split = blockIdx.y;
+  const bool sj = Query::kSelfJoin && self_join;
   int row0 = split * rows_per_split;
   const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
-  if (self_join) {   // row0 is a multiple of 64, so is the step that holds qbase + 1
+  if (sj) {   // row0 is a multiple of 64, so is the step that holds qbase + 1
     const int first = (qbase + 1) & ~(kCandPerIter - 1);
     row0 = row0 > first ? row0 : first;
+    if (row0 >= row_end) return;   // the whole split lies at or below the diagonal
   }
-  if (row0 >= row_end) return;   // the whole split lies at or below the diagonal
 
-  if (tid < QT) sq[tid] = 0;
-  __syncthreads();
-  for (int i = tid; i < QF * steps * 64; i += 256) {   // one 16-byte fragment per (query fragment, step, lane)
-    const int ln = i & 63, t = i >> 6;
-    const int step = t % steps, f = t / steps;
-    const int row = f * 16 + (ln & 15);
-    int qi = qbase + row;
-    qi = qi < nq ? qi : nq - 1;
-    const uint4 v = *reinterpret_cast<const uint4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4));
-    atomicAdd(&sq[row], (int)sum_bytes16(v, 0u));
-    A[i] = to_i8x16(v);
-  }
-  __syncthreads();
+  Query::template stage<QF>(q, nq, qbase, D, tid, A, sq);
 
-  int baseq[QF][4];
+  typename Query::Term tq[QF][4];
   float rq[QF][4];
   const int gq0 = qbase + 4 * (lane >> 4);   // this lane's query of (f, r) is gq0 + 16 f + r
 #pragma unroll
@@ -452,147 +426,22 @@ __global__ __launch_bounds__(256, 4) void search_range_kernel(const uint8_t *__r
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int gq = gq0 + 16 * f + r;
-      baseq[f][r] = 2 * (sq[f * 16 + 4 * (lane >> 4) + r] - 128 * D) + D;
-      rq[f][r] = r_q[gq < nq ? gq : nq - 1];
+      tq[f][r] = Query::term(sq, f * 16 + 4 * (lane >> 4) + r, D);
+      rq[f][r] = Query::scale(r_q, gq < nq ? gq : nq - 1);
     }
 
   for (int base = row0; base < row_end; base += kCandPerIter) {
     const int my = base + wave * 16 + (lane & 15);
-    const int myc = my < n ? my : n - 1;
-    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
-    v4i acc[QF];
+    v4i acc[Query::kPlanes][QF];   // zeroed here, not in accumulate(): through its reference that costs registers (an occupancy step)
 #pragma unroll
-    for (int f = 0; f < QF; f++) acc[f] = v4i{0, 0, 0, 0};
-    unsigned ssum = 0;
-    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
-      uint4 bv[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        ssum = sum_bytes16(bv[u], ssum);
-        const v4i b = to_i8x16(bv[u]);
-#pragma unroll
-        for (int f = 0; f < QF; f++)
-          acc[f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(f * steps + s0 + u) * 64 + lane], b, acc[f], 0, 0, 0);
-      }
-    }
-    ssum += __shfl_xor(ssum, 16);
-    ssum += __shfl_xor(ssum, 32);
-    const int sd2 = 2 * ((int)ssum - 128 * D);
-    const float rd = r_db[myc];
-    const int qlim = self_join ? my : nq;   // queries this lane may emit for: below nq, in a self-join (nq == n) below its own row
-    const bool valid = my < row_end;
-    unsigned hits = 0;   // bit 4 f + r
-#pragma unroll
-    for (int f = 0; f < QF; f++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const float score = ((float)(4 * acc[f][r] + baseq[f][r] + sd2) * rd) * rq[f][r];
-        const bool hit = valid && gq0 + 16 * f + r < qlim && score >= threshold;
-        hits |= hit ? 1u << (4 * f + r) : 0u;
-      }
-    if (__ballot(hits != 0) != 0ull) {   // rare: one atomic for all of this wave's hits of the step
-      unsigned before[QF * 4];           // entries of (f, r) start this far into the wave's block (wave-uniform)
-      unsigned total = 0;
-#pragma unroll
-      for (int m = 0; m < QF * 4; m++) {
-        before[m] = total;
-        total += (unsigned)__popcll(__ballot((hits >> m) & 1u));
-      }
-      unsigned long long start = 0;
-      if (lane == 0) start = atomicAdd(count, (unsigned long long)total);
-      start = __shfl(start, 0);
-#pragma unroll
-      for (int f = 0; f < QF; f++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int m = 4 * f + r;
-          const unsigned long long mask = __ballot((hits >> m) & 1u);
-          if ((hits >> m) & 1u) {
-            const unsigned long long pos = start + before[m] + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-            if (pos < capacity) {
-              out_q[pos] = gq0 + 16 * f + r;
-              out_d[pos] = my;
-              out_score[pos] = ((float)(4 * acc[f][r] + baseq[f][r] + sd2) * rd) * rq[f][r];   // the value tested above
-            }
-          }
-        }
-    }
-  }
-}
-
-// Threshold (range) search with fp32 queries: search_f32q_kernel's prologue (three digit planes and sum Q in LDS) in front of
-// search_range_kernel's row loop and append protocol.  A pair is a hit iff
-//   score = (float(M) * r_d) * 2^-22 >= T      (fp32; the bits sgic_search_codes_f32q reports)
-// LDS holds the planes and sum Q only, 16 QF (3 D + 8) bytes; there is no self-join (fp32 queries are not the database) and, as in
-// the top-k sibling, no byte sum of the database rows.
-template <int QF, int U>
-__global__ __launch_bounds__(256, 4) void search_range_f32q_kernel(const float *__restrict__ q, const uint8_t *__restrict__ db,
-                                                                const float *__restrict__ r_db, int nq, int n, int D,
-                                                                int rows_per_split, float threshold, unsigned long long capacity,
-                                                                unsigned long long *__restrict__ count, int *__restrict__ out_q,
-                                                                int *__restrict__ out_d, float *__restrict__ out_score) {
-  constexpr int QT = 16 * QF;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int steps = D >> 6;
-  const int plane = QF * steps * 64;         // fragments per digit plane
-  v4i *A = reinterpret_cast<v4i *>(smem);   // [3 planes][QF][steps][64 lanes] fragments
-  unsigned long long *sq = reinterpret_cast<unsigned long long *>(smem + (size_t)3 * QT * D);   // sum Q per query
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int qbase = blockIdx.x * QT, split = blockIdx.y;
-  const int row0 = split * rows_per_split;
-  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
-
-  if (tid < QT) sq[tid] = 0;
-  __syncthreads();
-  for (int i = tid; i < plane; i += 256) {   // sixteen coordinates -> one fragment in each plane per (query fragment, step, lane)
-    const int ln = i & 63, t = i >> 6;
-    const int step = t % steps, f = t / steps;
-    const int row = f * 16 + (ln & 15);
-    int qi = qbase + row;
-    qi = qi < nq ? qi : nq - 1;
-    v4i p0, p1, p2;
-    const int s = quantise16(reinterpret_cast<const float4 *>(q + (size_t)qi * D + 64 * step + 16 * (ln >> 4)), p0, p1, p2);
-    atomicAdd(&sq[row], (unsigned long long)(long long)s);
-    A[i] = p0;
-    A[plane + i] = p1;
-    A[2 * plane + i] = p2;
-  }
-  __syncthreads();
-
-  long long sumq[QF][4];
-  const int gq0 = qbase + 4 * (lane >> 4);   // this lane's query of (f, r) is gq0 + 16 f + r
-#pragma unroll
-  for (int f = 0; f < QF; f++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) sumq[f][r] = (long long)sq[f * 16 + 4 * (lane >> 4) + r];
-
-  for (int base = row0; base < row_end; base += kCandPerIter) {
-    const int my = base + wave * 16 + (lane & 15);
-    const int myc = my < n ? my : n - 1;
-    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
-    v4i acc[3][QF];
-#pragma unroll
-    for (int p = 0; p < 3; p++)
+    for (int p = 0; p < Query::kPlanes; p++)
 #pragma unroll
       for (int f = 0; f < QF; f++) acc[p][f] = v4i{0, 0, 0, 0};
-    for (int s0 = 0; s0 < steps; s0 += U) {   // U divides steps; the U loads of a round are issued together
-      uint4 bv[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) bv[u] = bp[(s0 + u) * 4];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const v4i b = to_i8x16(bv[u]);
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-          for (int f = 0; f < QF; f++)
-            acc[p][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[p * plane + (f * steps + s0 + u) * 64 + lane], b, acc[p][f], 0, 0, 0);
-      }
-    }
+    const int myc = my < n ? my : n - 1;   // rows >= n are clamped for the loads and masked below
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    const int td = Query::template accumulate<QF, U>(A, bp, D, lane, acc);
     const float rd = r_db[myc];
+    const int qlim = sj ? my : nq;   // queries this lane may emit for: below nq, in a self-join (nq == n) below its own row
     const bool valid = my < row_end;
     float score[QF][4];
     unsigned hits = 0;   // bit 4 f + r
@@ -600,9 +449,8 @@ __global__ __launch_bounds__(256, 4) void search_range_f32q_kernel(const float *
     for (int f = 0; f < QF; f++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const long long M = 2 * (65536LL * acc[2][f][r] + 256LL * acc[1][f][r] + acc[0][f][r]) + sumq[f][r];
-        score[f][r] = ((float)M * rd) * (1.0f / kQScale);
-        const bool hit = valid && gq0 + 16 * f + r < nq && score[f][r] >= threshold;
+        score[f][r] = Query::key(acc, f, r, tq[f][r], td, rd) * rq[f][r];
+        const bool hit = valid && gq0 + 16 * f + r < qlim && score[f][r] >= threshold;
         hits |= hit ? 1u << (4 * f + r) : 0u;
       }
     if (__ballot(hits != 0) != 0ull) {   // rare: one atomic for all of this wave's hits of the step
@@ -640,10 +488,11 @@ struct Plan {
   size_t lds, work_bytes;
 };
 
-size_t lds_bytes(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)D + (size_t)(k + kCandPerIter) * 8 + 12); }
-size_t lds_bytes_f32q(int qf, int D, int k) { return (size_t)16 * qf * ((size_t)3 * D + (size_t)(k + kCandPerIter) * 8 + 16); }
-size_t lds_bytes_range(int qf, int D) { return (size_t)16 * qf * ((size_t)D + 4); }   // the query tile and its byte sums
-size_t lds_bytes_range_f32q(int qf, int D) { return (size_t)16 * qf * ((size_t)3 * D + 8); }   // three digit planes and sum Q
+// the query tile and its sums; with k > 0 the candidate buffers (k + 64 keys and indices), a count and a threshold per query
+size_t lds_bytes(bool f32q, int qf, int D, int k) {
+  const size_t query = f32q ? (size_t)F32Query::kPlanes * D + sizeof(F32Query::Sum) : (size_t)U8Query::kPlanes * D + sizeof(U8Query::Sum);
+  return (size_t)16 * qf * (query + (k ? (size_t)(k + kCandPerIter) * 8 + 8 : 0));
+}
 
 // contiguous ascending database splits of whole 64-row steps, none empty; splits <= 0: cover the chip a few times over
 void plan_splits(int n, int splits, Plan *p) {
@@ -660,95 +509,85 @@ void plan_splits(int n, int splits, Plan *p) {
   p->splits = (n + p->rows_per_split - 1) / p->rows_per_split;
 }
 
+// k == 0: the plan of a threshold search (no candidate buffers, no workspace); the top-k entry points refuse it before they ask
 int make_plan(int nq, int n, int D, int k, int splits, bool f32q, Plan *p) {
-  SGIC_REQUIRE(nq > 0 && n > 0 && k > 0 && k <= n, "sizes");
+  SGIC_REQUIRE(nq > 0 && n > 0 && k >= 0 && k <= n, "sizes");
   SGIC_REQUIRE(k <= kMaxK, "the fused search keeps at most 128 results per query");
   SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "D must be a multiple of 64, at most 4096 (int32 exactness)");
   SGIC_REQUIRE(!f32q || D <= kMaxDimF32Q, "fp32 queries: D at most 2048 (three query digit planes have to fit the LDS)");
-  if (f32q)   // three planes: the wide tile is 32 queries
-    p->qf = (nq > 16 && lds_bytes_f32q(2, D, k) <= (size_t)kLdsBigTile) ? 2 : 1;
-  else
-    p->qf = (nq > 16 && lds_bytes(4, D, k) <= (size_t)kLdsBigTile) ? 4 : 1;
-  p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
   SGIC_REQUIRE(splits <= kMaxSplits, "splits");
+  const int wide = f32q ? F32Query::kWideQF : U8Query::kWideQF;   // three planes: the wide tile is 32 queries, not 64
+  p->qf = (nq > 16 && lds_bytes(f32q, wide, D, k) <= (size_t)kLdsBigTile) ? wide : 1;
+  p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
   plan_splits(n, splits, p);
-  p->lds = f32q ? lds_bytes_f32q(p->qf, D, k) : lds_bytes(p->qf, D, k);
+  p->lds = lds_bytes(f32q, p->qf, D, k);
   p->work_bytes = p->splits > 1 ? (size_t)nq * p->splits * k * 8 : 0;
   return SGIC_OK;
 }
 
-// the plan of the threshold searches: make_plan's tile choice with the smaller LDS formulas (no candidate buffers), its splits
-int make_range_plan(int nq, int n, int D, int splits, bool f32q, Plan *p) {
-  SGIC_REQUIRE(nq > 0 && n > 0, "sizes");
-  SGIC_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "D must be a multiple of 64, at most 4096 (int32 exactness)");
-  SGIC_REQUIRE(!f32q || D <= kMaxDimF32Q, "fp32 queries: D at most 2048 (three query digit planes have to fit the LDS)");
-  SGIC_REQUIRE(splits <= kMaxSplits, "splits");
-  if (f32q)   // three planes: the wide tile is 32 queries, up to D = 832
-    p->qf = (nq > 16 && lds_bytes_range_f32q(2, D) <= (size_t)kLdsBigTile) ? 2 : 1;
-  else
-    p->qf = (nq > 16 && lds_bytes_range(4, D) <= (size_t)kLdsBigTile) ? 4 : 1;
-  p->qtiles = (nq + 16 * p->qf - 1) / (16 * p->qf);
-  plan_splits(n, splits, p);
-  p->lds = f32q ? lds_bytes_range_f32q(p->qf, D) : lds_bytes_range(p->qf, D);
-  p->work_bytes = 0;
+template <auto Kernel, class... Args>
+int launch(const Plan &p, const char *name, hipStream_t st, Args... args) {
+  static bool lds_raised = false;   // beyond the default 64 KiB a kernel has to be allowed its dynamic LDS once (largest use: 120.25 KiB)
+  if (p.lds > 60 * 1024 && !lds_raised) {
+    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    lds_raised = true;
+  }
+  Kernel<<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(args...);
+  return sgic::check_launch(name);
+}
+
+// f(QF, U) for the plan's tile (Query's wide tile or 16 queries) and eight 64-byte steps per round when D allows it, else one
+template <class Query, class F>
+int dispatch(const Plan &p, int D, F f) {
+  constexpr std::integral_constant<int, Query::kWideQF> wide{};
+  constexpr std::integral_constant<int, 1> one{};
+  constexpr std::integral_constant<int, 8> eight{};
+  const bool u8 = D % 512 == 0;
+  return p.qf == wide ? (u8 ? f(wide, eight) : f(wide, one)) : (u8 ? f(one, eight) : f(one, one));
+}
+
+template <class Query>
+int search_range(const Plan &p, const typename Query::T *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
+                 int D, float threshold, int self_join, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,
+                 float *d_out_score, sgic_stream_t stream) {
+  return dispatch<Query>(p, D, [&](auto qf, auto u) {
+    return launch<search_range_kernel<Query, qf, u>>(p, "search_range_kernel", to_stream(stream), d_q, d_rq, d_db, d_rdb, nq, n, D,
+                                                    p.rows_per_split, threshold, self_join, (unsigned long long)capacity,
+                                                    reinterpret_cast<unsigned long long *>(d_count), d_out_q, d_out_d, d_out_score);
+  });
+}
+
+int topk_work_bytes(int nq, int n, int D, int k, int splits, bool f32q, int *splits_used, size_t *bytes) {
+  SGIC_REQUIRE(k > 0, "sizes");
+  Plan p;
+  const int rc = make_plan(nq, n, D, k, splits, f32q, &p);
+  if (rc != SGIC_OK) return rc;
+  if (splits_used) *splits_used = p.splits;
+  if (bytes) *bytes = p.work_bytes;
   return SGIC_OK;
 }
 
-template <int QF, int U>
-int launch_search(const Plan &p, const uint8_t *q, const float *r_q, const uint8_t *db, const float *r_db, int nq, int n, int D, int k,
-                  float *okey, int *oidx, hipStream_t st) {
-  static bool lds_raised = false;   // beyond the default 64 KiB a kernel has to be allowed its dynamic LDS once (largest use: 90 KiB)
-  if (p.lds > 60 * 1024 && !lds_raised) {
-    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_codes_kernel<QF, U>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 128 * 1024));
-    lds_raised = true;
+// the search into the outputs, or with several splits into the workspace and the merge from there; d_rq: nullptr for fp32 queries
+template <class Query>
+int search_topk(const Plan &p, const typename Query::T *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
+                int D, int k, uint8_t *d_work, float *d_out_scores, int32_t *d_out_idx, sgic_stream_t stream) {
+  hipStream_t st = to_stream(stream);
+  float *okey = d_out_scores;
+  int *oidx = d_out_idx;
+  if (p.splits > 1) {
+    okey = reinterpret_cast<float *>(d_work);
+    oidx = reinterpret_cast<int *>(d_work + (size_t)nq * p.splits * k * 4);
   }
-  search_codes_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, r_q, db, r_db, nq, n, D, k, p.rows_per_split, p.splits,
-                                                                         p.splits == 1, okey, oidx);
-  return sgic::check_launch("search_codes_kernel");
-}
-
-template <int QF, int U>
-int launch_search_f32q(const Plan &p, const float *q, const uint8_t *db, const float *r_db, int nq, int n, int D, int k, float *okey,
-                       int *oidx, hipStream_t st) {
-  static bool lds_raised = false;   // largest use: 16 queries, D = 2048, k = 128 -> 120.25 KiB
-  if (p.lds > 60 * 1024 && !lds_raised) {
-    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_f32q_kernel<QF, U>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 128 * 1024));
-    lds_raised = true;
+  const int lrc = dispatch<Query>(p, D, [&](auto qf, auto u) {
+    return launch<search_topk_kernel<Query, qf, u>>(p, "search_topk_kernel", st, d_q, d_rq, d_db, d_rdb, nq, n, D, k, p.rows_per_split,
+                                                   p.splits, (int)(p.splits == 1), okey, oidx);
+  });
+  if (lrc != SGIC_OK) return lrc;
+  if (p.splits > 1) {
+    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, d_rq, 1.0f / kQScale, p.splits, k, d_out_scores, d_out_idx);
+    return sgic::check_launch("search_merge_kernel");
   }
-  search_f32q_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, db, r_db, nq, n, D, k, p.rows_per_split, p.splits,
-                                                                        p.splits == 1, okey, oidx);
-  return sgic::check_launch("search_f32q_kernel");
-}
-
-template <int QF, int U>
-int launch_search_range(const Plan &p, const uint8_t *q, const float *r_q, const uint8_t *db, const float *r_db, int nq, int n, int D,
-                        float threshold, int self_join, unsigned long long capacity, unsigned long long *count, int *oq, int *od,
-                        float *os, hipStream_t st) {
-  static bool lds_raised = false;   // largest use: 16 queries, D = 4096 -> 64.06 KiB
-  if (p.lds > 60 * 1024 && !lds_raised) {
-    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_range_kernel<QF, U>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 128 * 1024));
-    lds_raised = true;
-  }
-  search_range_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, r_q, db, r_db, nq, n, D, p.rows_per_split, threshold,
-                                                                         self_join, capacity, count, oq, od, os);
-  return sgic::check_launch("search_range_kernel");
-}
-
-template <int QF, int U>
-int launch_search_range_f32q(const Plan &p, const float *q, const uint8_t *db, const float *r_db, int nq, int n, int D, float threshold,
-                             unsigned long long capacity, unsigned long long *count, int *oq, int *od, float *os, hipStream_t st) {
-  static bool lds_raised = false;   // largest use: 16 queries, D = 2048 -> 96.1 KiB
-  if (p.lds > 60 * 1024 && !lds_raised) {
-    SGIC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_range_f32q_kernel<QF, U>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    lds_raised = true;
-  }
-  search_range_f32q_kernel<QF, U><<<dim3(p.qtiles, p.splits), 256, p.lds, st>>>(q, db, r_db, nq, n, D, p.rows_per_split, threshold,
-                                                                              capacity, count, oq, od, os);
-  return sgic::check_launch("search_range_f32q_kernel");
+  return SGIC_OK;
 }
 
 }  // namespace
@@ -757,28 +596,22 @@ extern "C" int sgic_search_range_f32q(const float *d_q, const uint8_t *d_db, con
                                       int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,
                                       float *d_out_score, sgic_stream_t stream) {
   Plan p;
-  const int rc = make_range_plan(nq, n, D, splits, true, &p);
+  const int rc = make_plan(nq, n, D, 0, splits, true, &p);
   if (rc != SGIC_OK) return rc;
   SGIC_REQUIRE(d_q && d_db && d_rdb && d_count, "null pointer");
   SGIC_REQUIRE(capacity >= 0 && (capacity == 0 || (d_out_q && d_out_d && d_out_score)), "capacity > 0 needs the three output arrays");
   SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db) % 16 == 0, "queries and codes must be 16-byte aligned");
   SGIC_REQUIRE((uintptr_t)d_count % 8 == 0, "the hit counter must be 8-byte aligned");
   SGIC_REQUIRE(isfinite(threshold), "the threshold must be finite");
-  hipStream_t st = to_stream(stream);
-  unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_count);
-  const unsigned long long cap = (unsigned long long)capacity;
-  const bool u8 = D % 512 == 0;   // eight 64-byte steps per round when D allows it, else one
-  return p.qf == 2 ? (u8 ? launch_search_range_f32q<2, 8>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st)
-                         : launch_search_range_f32q<2, 1>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st))
-                   : (u8 ? launch_search_range_f32q<1, 8>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st)
-                         : launch_search_range_f32q<1, 1>(p, d_q, d_db, d_rdb, nq, n, D, threshold, cap, cnt, d_out_q, d_out_d, d_out_score, st));
+  return search_range<F32Query>(p, d_q, nullptr, d_db, d_rdb, nq, n, D, threshold, 0, capacity, d_count, d_out_q, d_out_d, d_out_score,
+                                stream);
 }
 
 extern "C" int sgic_search_range_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
                                     int D, float threshold, int self_join, int splits, long long capacity, uint64_t *d_count,
                                     int32_t *d_out_q, int32_t *d_out_d, float *d_out_score, sgic_stream_t stream) {
   Plan p;
-  const int rc = make_range_plan(nq, n, D, splits, false, &p);
+  const int rc = make_plan(nq, n, D, 0, splits, false, &p);
   if (rc != SGIC_OK) return rc;
   SGIC_REQUIRE(d_q && d_rq && d_db && d_rdb && d_count, "null pointer");
   SGIC_REQUIRE(capacity >= 0 && (capacity == 0 || (d_out_q && d_out_d && d_out_score)), "capacity > 0 needs the three output arrays");
@@ -786,97 +619,48 @@ extern "C" int sgic_search_range_u8(const uint8_t *d_q, const float *d_rq, const
   SGIC_REQUIRE((uintptr_t)d_count % 8 == 0, "the hit counter must be 8-byte aligned");
   SGIC_REQUIRE(isfinite(threshold), "the threshold must be finite");
   SGIC_REQUIRE(!self_join || nq == n, "self_join: the queries are the database (nq == n)");
-  hipStream_t st = to_stream(stream);
-  unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_count);
-  const unsigned long long cap = (unsigned long long)capacity;
-  const int sj = self_join ? 1 : 0;
-  const bool u8 = D % 512 == 0;   // eight 64-byte steps per round when D allows it, else one
-  return p.qf == 4 ? (u8 ? launch_search_range<4, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st)
-                         : launch_search_range<4, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st))
-                   : (u8 ? launch_search_range<1, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st)
-                         : launch_search_range<1, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, sj, cap, cnt, d_out_q, d_out_d, d_out_score, st));
+  return search_range<U8Query>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, threshold, self_join ? 1 : 0, capacity, d_count, d_out_q, d_out_d,
+                               d_out_score, stream);
 }
 
 extern "C" int sgic_search_codes_u8_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes) {
-  Plan p;
-  const int rc = make_plan(nq, n, D, k, splits, false, &p);
-  if (rc != SGIC_OK) return rc;
-  if (splits_used) *splits_used = p.splits;
-  if (bytes) *bytes = p.work_bytes;
-  return SGIC_OK;
+  return topk_work_bytes(nq, n, D, k, splits, false, splits_used, bytes);
 }
 
 extern "C" int sgic_search_codes_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, int nq, int n,
                                     int D, int k, int splits, uint8_t *d_work, size_t work_bytes, float *d_out_scores,
                                     int32_t *d_out_idx, sgic_stream_t stream) {
+  SGIC_REQUIRE(k > 0, "sizes");
   Plan p;
   const int rc = make_plan(nq, n, D, k, splits, false, &p);
   if (rc != SGIC_OK) return rc;
   SGIC_REQUIRE(d_q && d_rq && d_db && d_rdb && d_out_scores && d_out_idx, "null pointer");
   SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db | (uintptr_t)d_work) % 16 == 0, "codes and workspace must be 16-byte aligned");
   SGIC_REQUIRE(p.work_bytes == 0 || (d_work && work_bytes >= p.work_bytes), "workspace (sgic_search_codes_u8_work_bytes)");
-  hipStream_t st = to_stream(stream);
-  float *okey = d_out_scores;
-  int *oidx = d_out_idx;
-  if (p.splits > 1) {
-    okey = reinterpret_cast<float *>(d_work);
-    oidx = reinterpret_cast<int *>(d_work + (size_t)nq * p.splits * k * 4);
-  }
-  const bool u8 = D % 512 == 0;   // eight 64-byte steps per round when D allows it, else one
-  const int lrc = p.qf == 4 ? (u8 ? launch_search<4, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
-                                  : launch_search<4, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st))
-                            : (u8 ? launch_search<1, 8>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
-                                  : launch_search<1, 1>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, okey, oidx, st));
-  if (lrc != SGIC_OK) return lrc;
-  if (p.splits > 1) {
-    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, d_rq, 1.0f, p.splits, k, d_out_scores, d_out_idx);
-    return sgic::check_launch("search_merge_kernel");
-  }
-  return SGIC_OK;
+  return search_topk<U8Query>(p, d_q, d_rq, d_db, d_rdb, nq, n, D, k, d_work, d_out_scores, d_out_idx, stream);
 }
 
 extern "C" int sgic_search_codes_f32q_work_bytes(int nq, int n, int D, int k, int splits, int *splits_used, size_t *bytes) {
-  Plan p;
-  const int rc = make_plan(nq, n, D, k, splits, true, &p);
-  if (rc != SGIC_OK) return rc;
-  if (splits_used) *splits_used = p.splits;
-  if (bytes) *bytes = p.work_bytes;
-  return SGIC_OK;
+  return topk_work_bytes(nq, n, D, k, splits, true, splits_used, bytes);
 }
 
 extern "C" int sgic_search_codes_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, int k, int splits,
                                       uint8_t *d_work, size_t work_bytes, float *d_out_scores, int32_t *d_out_idx,
                                       sgic_stream_t stream) {
+  SGIC_REQUIRE(k > 0, "sizes");
   Plan p;
   const int rc = make_plan(nq, n, D, k, splits, true, &p);
   if (rc != SGIC_OK) return rc;
   SGIC_REQUIRE(d_q && d_db && d_rdb && d_out_scores && d_out_idx, "null pointer");
   SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db | (uintptr_t)d_work) % 16 == 0, "queries, codes and workspace must be 16-byte aligned");
   SGIC_REQUIRE(p.work_bytes == 0 || (d_work && work_bytes >= p.work_bytes), "workspace (sgic_search_codes_f32q_work_bytes)");
-  hipStream_t st = to_stream(stream);
-  float *okey = d_out_scores;
-  int *oidx = d_out_idx;
-  if (p.splits > 1) {
-    okey = reinterpret_cast<float *>(d_work);
-    oidx = reinterpret_cast<int *>(d_work + (size_t)nq * p.splits * k * 4);
-  }
-  const bool u8 = D % 512 == 0;
-  const int lrc = p.qf == 2 ? (u8 ? launch_search_f32q<2, 8>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
-                                  : launch_search_f32q<2, 1>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st))
-                            : (u8 ? launch_search_f32q<1, 8>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st)
-                                  : launch_search_f32q<1, 1>(p, d_q, d_db, d_rdb, nq, n, D, k, okey, oidx, st));
-  if (lrc != SGIC_OK) return lrc;
-  if (p.splits > 1) {
-    search_merge_kernel<<<nq, 256, 0, st>>>(okey, oidx, nullptr, 1.0f / kQScale, p.splits, k, d_out_scores, d_out_idx);
-    return sgic::check_launch("search_merge_kernel");
-  }
-  return SGIC_OK;
+  return search_topk<F32Query>(p, d_q, nullptr, d_db, d_rdb, nq, n, D, k, d_work, d_out_scores, d_out_idx, stream);
 }
 
 // Clustering over the same codes (CodeIndex.assign / kmeans): for every database row the best of K fp32 centroids, and the exact
 // integer sums of a partition.
 //
-// sgic_assign_codes_f32c.  M(c, d) is search_f32q_kernel's integer: the centroid goes through quantise16 into three balanced
+// sgic_assign_codes_f32c.  M(c, d) is F32Query's integer: the centroid goes through quantise16 into three balanced
 // base-256 digit planes, S_p = sum d_p (c_d - 128) comes from the i8 MFMA, M = 2 (65536 S_2 + 256 S_1 + S_0) + sum Q in int64.
 // r_d > 0 is common to all centroids of a row, so the argmax runs on M itself: larger M, equal M -> lower centroid index.  No float
 // compare, add, root or division; the caller derives the score (float32(M) * r_d) * 2^-22.
@@ -918,12 +702,7 @@ __global__ __launch_bounds__(256) void assign_prepare_kernel(const float *__rest
     const int ln = i & 63, step = i >> 6;
     int ci = tile * 16 + (ln & 15);
     ci = ci < K ? ci : K - 1;
-    v4i p0, p1, p2;
-    const int s = quantise16(reinterpret_cast<const float4 *>(cent + (size_t)ci * D + 64 * step + 16 * (ln >> 4)), p0, p1, p2);
-    atomicAdd(&sq[ln & 15], (unsigned long long)(long long)s);
-    dst[i] = p0;
-    dst[frags + i] = p1;
-    dst[2 * frags + i] = p2;
+    stage_f32_fragment(cent + (size_t)ci * D + 64 * step + 16 * (ln >> 4), dst + i, frags, &sq[ln & 15]);
   }
   __syncthreads();
   if (tid < 16) sumq[tile * 16 + tid] = (long long)sq[tid];

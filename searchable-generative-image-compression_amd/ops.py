@@ -1034,80 +1034,73 @@ def topk_rows(scores, k):
     return os_, oi
 
 
+def _search_inputs(q, r_q, db_codes, r_db, extra=()):
+    """the checks the four fused searches share: q (nq, D) u8 codes with their r_q (nq,), or fp32 queries with r_q None; db_codes
+    (n, D) u8, r_db (n,) fp32; `extra` further (tensor, dtype) pairs; all contiguous on db_codes' device -> (nq, n, D)"""
+    require_gpu()
+    qdt = torch.float32 if r_q is None else torch.uint8
+    for t, dt in ((q, qdt), (db_codes, torch.uint8), (r_db, torch.float32)) + (() if r_q is None else ((r_q, torch.float32),)) + extra:
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
+    nq, D = q.shape
+    n, Dd = db_codes.shape
+    assert D == Dd and r_db.shape == (n,) and (r_q is None or r_q.shape == (nq,))
+    return nq, n, D
+
+
+def _search_topk(q, r_q, db_codes, r_db, k, splits):
+    """sgic_search_codes_u8, or with r_q None sgic_search_codes_f32q: the checks, the workspace and the call"""
+    nq, n, D = _search_inputs(q, r_q, db_codes, r_db)
+    name = "sgic_search_codes_f32q" if r_q is None else "sgic_search_codes_u8"
+    want = 0 if splits is None else int(splits)
+    used, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+    call(name + "_work_bytes", nq, n, D, int(k), want, ctypes.byref(used), ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=db_codes.device) if nbytes.value else None
+    os_ = torch.empty(nq, k, device=db_codes.device, dtype=torch.float32)
+    oi = torch.empty(nq, k, device=db_codes.device, dtype=torch.int32)
+    call(name, _p(q), *(() if r_q is None else (_p(r_q),)), _p(db_codes), _p(r_db), nq, n, D, int(k), want, _p(work),
+         ctypes.c_size_t(nbytes.value), _p(os_), _p(oi))
+    return os_, oi
+
+
 def search_codes(q_codes, r_q, db_codes, r_db, k, splits=None):
     """fused exact search over u8 codes (csrc/search.hip): q_codes (nq, D) / db_codes (n, D) u8, r_q (nq,) / r_db (n,) fp32
     (search.code_rnorm), all contiguous on one device -> (scores (nq,k) fp32, idx (nq,k) int32), score descending, ties -> lower
     index.  D % 64 == 0, D <= 4096, k <= min(n, 128); `splits` forces the number of database splits (tests)."""
-    require_gpu()
-    for t, dt in ((q_codes, torch.uint8), (db_codes, torch.uint8), (r_q, torch.float32), (r_db, torch.float32)):
-        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
-    nq, D = q_codes.shape
-    n, Dd = db_codes.shape
-    assert D == Dd and r_q.shape == (nq,) and r_db.shape == (n,)
-    want = 0 if splits is None else int(splits)
-    used, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
-    call("sgic_search_codes_u8_work_bytes", nq, n, D, int(k), want, ctypes.byref(used), ctypes.byref(nbytes))
-    work = torch.empty(nbytes.value, dtype=torch.uint8, device=db_codes.device) if nbytes.value else None
-    os_ = torch.empty(nq, k, device=db_codes.device, dtype=torch.float32)
-    oi = torch.empty(nq, k, device=db_codes.device, dtype=torch.int32)
-    call("sgic_search_codes_u8", _p(q_codes), _p(r_q), _p(db_codes), _p(r_db), nq, n, D, int(k), want, _p(work), ctypes.c_size_t(nbytes.value),
-         _p(os_), _p(oi))
-    return os_, oi
+    return _search_topk(q_codes, r_q, db_codes, r_db, k, splits)
 
 
 def search_codes_f32q(q, db_codes, r_db, k, splits=None):
-    """fused exact search of fp32 queries over u8 codes (csrc/search.hip, search_f32q_kernel): q (nq, D) fp32, db_codes (n, D) u8,
+    """fused exact search of fp32 queries over u8 codes (csrc/search.hip, F32Query): q (nq, D) fp32, db_codes (n, D) u8,
     r_db (n,) fp32 (search.code_rnorm), all contiguous on one device -> (scores (nq,k) fp32, idx (nq,k) int32), score descending,
     ties -> lower index.  The query is taken to 2^-22 fixed point (include/sgic.h has the arithmetic).  D % 64 == 0, D <= 2048,
     k <= min(n, 128); `splits` forces the number of database splits (tests)."""
-    require_gpu()
-    for t, dt in ((q, torch.float32), (db_codes, torch.uint8), (r_db, torch.float32)):
-        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
-    nq, D = q.shape
-    n, Dd = db_codes.shape
-    assert D == Dd and r_db.shape == (n,)
-    want = 0 if splits is None else int(splits)
-    used, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
-    call("sgic_search_codes_f32q_work_bytes", nq, n, D, int(k), want, ctypes.byref(used), ctypes.byref(nbytes))
-    work = torch.empty(nbytes.value, dtype=torch.uint8, device=db_codes.device) if nbytes.value else None
-    os_ = torch.empty(nq, k, device=db_codes.device, dtype=torch.float32)
-    oi = torch.empty(nq, k, device=db_codes.device, dtype=torch.int32)
-    call("sgic_search_codes_f32q", _p(q), _p(db_codes), _p(r_db), nq, n, D, int(k), want, _p(work), ctypes.c_size_t(nbytes.value), _p(os_),
-         _p(oi))
-    return os_, oi
+    return _search_topk(q, None, db_codes, r_db, k, splits)
+
+
+def _search_range_launch(q, r_q, db_codes, r_db, threshold, self_join, splits, capacity, count, out_q, out_d, out_score):
+    """sgic_search_range_u8, or with r_q None sgic_search_range_f32q (no self_join): the checks and the call"""
+    nq, n, D = _search_inputs(q, r_q, db_codes, r_db, ((count, torch.int64),))
+    assert count.numel() == 1
+    capacity = int(capacity)
+    for t, dt in ((out_q, torch.int32), (out_d, torch.int32), (out_score, torch.float32)):
+        assert (t is None and capacity == 0) or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= capacity)
+    head = (_p(q), _p(db_codes), _p(r_db), nq, n, D, float(threshold)) if r_q is None else \
+        (_p(q), _p(r_q), _p(db_codes), _p(r_db), nq, n, D, float(threshold), bool(self_join))
+    call("sgic_search_range_f32q" if r_q is None else "sgic_search_range_u8", *head, 0 if splits is None else int(splits),
+         ctypes.c_longlong(capacity), _p(count), _p(out_q), _p(out_d), _p(out_score))
 
 
 def search_codes_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join, splits, capacity, count, out_q, out_d, out_score):
     """one call of sgic_search_range_u8 (include/sgic.h), nothing else: `count` (1,) int64 on the device is ADDED to (the caller
     zeroes it), out_q / out_d int32 and out_score fp32 hold at least `capacity` entries each (None with capacity = 0: count only).
     No synchronisation; hits arrive in no particular order."""
-    require_gpu()
-    for t, dt in ((q_codes, torch.uint8), (db_codes, torch.uint8), (r_q, torch.float32), (r_db, torch.float32), (count, torch.int64)):
-        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
-    nq, D = q_codes.shape
-    n, Dd = db_codes.shape
-    assert D == Dd and r_q.shape == (nq,) and r_db.shape == (n,) and count.numel() == 1
-    capacity = int(capacity)
-    for t, dt in ((out_q, torch.int32), (out_d, torch.int32), (out_score, torch.float32)):
-        assert (t is None and capacity == 0) or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= capacity)
-    call("sgic_search_range_u8", _p(q_codes), _p(r_q), _p(db_codes), _p(r_db), nq, n, D, float(threshold), bool(self_join),
-         0 if splits is None else int(splits), ctypes.c_longlong(capacity), _p(count), _p(out_q), _p(out_d), _p(out_score))
+    _search_range_launch(q_codes, r_q, db_codes, r_db, threshold, self_join, splits, capacity, count, out_q, out_d, out_score)
 
 
 def search_codes_range_f32q_launch(q, db_codes, r_db, threshold, splits, capacity, count, out_q, out_d, out_score):
     """one call of sgic_search_range_f32q (include/sgic.h), nothing else: q (nq, D) fp32; `count`, the output arrays and
     `capacity` as in search_codes_range_launch (the counter is ADDED to).  No synchronisation; hits arrive in no particular order."""
-    require_gpu()
-    for t, dt in ((q, torch.float32), (db_codes, torch.uint8), (r_db, torch.float32), (count, torch.int64)):
-        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == db_codes.device
-    nq, D = q.shape
-    n, Dd = db_codes.shape
-    assert D == Dd and r_db.shape == (n,) and count.numel() == 1
-    capacity = int(capacity)
-    for t, dt in ((out_q, torch.int32), (out_d, torch.int32), (out_score, torch.float32)):
-        assert (t is None and capacity == 0) or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= capacity)
-    call("sgic_search_range_f32q", _p(q), _p(db_codes), _p(r_db), nq, n, D, float(threshold), 0 if splits is None else int(splits),
-         ctypes.c_longlong(capacity), _p(count), _p(out_q), _p(out_d), _p(out_score))
+    _search_range_launch(q, None, db_codes, r_db, threshold, False, splits, capacity, count, out_q, out_d, out_score)
 
 
 def _range_collect(launch_into, nq, n, dev, threshold, capacity, max_pairs):
@@ -1161,7 +1154,7 @@ def search_codes_range(q_codes, r_q, db_codes, r_db, threshold, self_join=False,
 
 
 def search_codes_range_f32q(q, db_codes, r_db, threshold, capacity=None, splits=None, max_pairs=None):
-    """threshold (range) search of fp32 queries over u8 codes (csrc/search.hip, search_range_f32q_kernel): every pair whose score
+    """threshold (range) search of fp32 queries over u8 codes (csrc/search.hip, search_range_kernel with F32Query): every pair whose score
     -- the fp32 bits search_codes_f32q reports -- is >= threshold.  Inputs as for search_codes_f32q (D % 64 == 0, D <= 2048).
     -> (q int32, d int32, score fp32, count), sorted by (q, d) ascending on the device; capacity, the second launch after an
     overflow and max_pairs are _range_collect's."""

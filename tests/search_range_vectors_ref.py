@@ -1,4 +1,4 @@
-"""numpy restatement of the threshold (range) search of fp32 queries over u8 codes (csrc/search.hip search_range_f32q_kernel,
+"""numpy restatement of the threshold (range) search of fp32 queries over u8 codes (csrc/search.hip search_range_kernel with F32Query,
 ops.search_codes_range_f32q, sgic_amd.search.CodeIndex.range_search_vectors), built on search_vectors_ref.keys_and_scores.
 
 A pair (q, d) is a hit iff score(q, d) >= float32(T), score being the fp32 value the top-k search of fp32 queries reports,

@@ -1,4 +1,4 @@
-"""numpy restatement of the fp32-query search over u8 codes (csrc/search.hip search_f32q_kernel, CodeIndex.search_vectors), every
+"""numpy restatement of the fp32-query search over u8 codes (csrc/search.hip search_topk_kernel with F32Query, CodeIndex.search_vectors), every
 bit of it.
 
 Query to fixed point: Q = clamp(rint(float32(q) * 2^22), -2^22, 2^22) as an integer (round to nearest even, NaN -> 0).  Balanced

@@ -68,6 +68,22 @@ def test_sign_and_edge_rows(dim):
     _check(q, db, 3, "edge")
 
 
+@pytest.mark.parametrize("nq", [17, 33])
+def test_three_steps_one_load_per_round_wide_tile(nq):
+    """D = 192: three 64-byte steps, not a multiple of eight, so one load per round (U = 1) with more than one step, under the
+    64-query tile -- the query fragment index (f * steps + step) of every fragment f > 0.  nq = 17 / 33: the last live fragment
+    (f = 1 / f = 2) holds one query, the fragments after it only clamped rows; n = 65: a one-row tail tile, which splits = 2 makes a split of its own"""
+    rng = np.random.default_rng(192 + nq)
+    db = ref.quantised_unit_codes(rng, 65, 192)
+    q = ref.quantised_unit_codes(rng, nq, 192)
+    q[nq - 1] = db[64]
+    for k in (1, 10):
+        want = ref.search(q, db, k)
+        assert want[1][nq - 1, 0] == 64
+        for splits in (1, 2):
+            _same(_gpu(q, db, k, splits), want, ("D = 192", nq, k, splits))
+
+
 def test_operand_placement_identity_queries_asymmetric_database():
     """query i is the unit step at coordinate p_i (a = 1 there, 0 elsewhere), so S(i, j) = a_db[j][p_i]: a row/column swap or a
     lane-map error of either MFMA operand shows as a wrong integer, the database being asymmetric in (row, coordinate)"""

@@ -1,4 +1,4 @@
-"""GPU: the threshold (range) search of fp32 queries over u8 codes (csrc/search.hip search_range_f32q_kernel through
+"""GPU: the threshold (range) search of fp32 queries over u8 codes (csrc/search.hip search_range_kernel with F32Query through
 ops.search_codes_range_f32q, search.CodeIndex.range_search_vectors, the CLI and the resident service) against its numpy restatement
 (tests/search_range_vectors_ref.py): the same pairs, the same score bits, the exact count, everywhere."""
 import io

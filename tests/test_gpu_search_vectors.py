@@ -1,5 +1,5 @@
-"""GPU: fp32 text / image queries against the u8 code index (csrc/search.hip search_f32q_kernel through ops.search_codes_f32q /
-CodeIndex.search_vectors / the CLI / ResidentService) against the numpy restatement (tests/search_vectors_ref.py).  Ids and scores
+"""GPU: fp32 text / image queries against the u8 code index (csrc/search.hip search_topk_kernel with F32Query through
+ops.search_codes_f32q / CodeIndex.search_vectors / the CLI / ResidentService) against the numpy restatement (tests/search_vectors_ref.py).  Ids and scores
 are compared bit for bit everywhere; only the cross-check against the fp32 path has tolerances, those of that path's own 10k test,
 plus the derived bound against fp64."""
 import io
@@ -68,6 +68,22 @@ def test_every_score_compared_n100_k100():
     db = ref.quantised_unit_codes(rng, 100, 512)
     for nq in (5, 33):
         _check(ref.random_unit(rng, nq, 512), db, 100, ("all", nq))
+
+
+@pytest.mark.parametrize("nq", [17, 33])
+def test_three_steps_one_load_per_round_wide_tile(nq):
+    """D = 192: three 64-byte steps, not a multiple of eight, so one load per round (U = 1) with more than one step, under the
+    32-query tile -- the query fragment index (f * steps + step) of fragment f = 1 in each plane.  nq = 17 / 33: one full and one
+    partial wide tile, two full and one partial; n = 65: a one-row tail tile, which splits = 2 makes a split of its own"""
+    rng = np.random.default_rng(192 + nq)
+    db = ref.quantised_unit_codes(rng, 65, 192)
+    q = ref.random_unit(rng, nq, 192)
+    q[nq - 1] = _unit_of(db[64])
+    for k in (1, 10):
+        want = ref.search(q, db, k)
+        assert want[1][nq - 1, 0] == 64
+        for splits in (1, 2):
+            _same(_gpu(q, db, k, splits), want, ("D = 192", nq, k, splits))
 
 
 def test_plane_placement_one_hot_queries_asymmetric_database():

@@ -15,7 +15,7 @@ the run.
           search's own two repeats show.  Both read n D bytes once: the share of 6.3 TB/s is given for each.
   dense   T = -2, nq = 64, n = 1e5: every pair is a hit, 6.4e6 entries; output-bound, no pass mark.
 
---vectors runs the fp32-query points instead (search_range_f32q_kernel: ops.search_codes_range_f32q), same protocol:
+--vectors runs the fp32-query points instead (search_range_kernel with F32Query: ops.search_codes_range_f32q), same protocol:
 
   vrange  search_codes_range_f32q at n = 1e6, nq in {1, 16}; the queries are the dequantised unit vectors of corpus rows that have
           a planted near-duplicate, so a handful of hits exist.  Counterpart: search_codes_f32q with k = 10 on the same inputs, what
