@@ -503,7 +503,8 @@ int sgic_clip_preprocess_u8canvas(const uint8_t *d_canvas, int Hc, int Wc, int B
  * d_scan: cleaned entropy-coded segments (each padded to a multiple of 2048 B), d_tabs: B x 4 lookup tables of 1424 B,
  * d_segs: restart-interval byte offsets, d_quant: u16 tables in natural order -- these five may be device memory or PINNED host
  * memory (the kernels then pull the compressed bytes over PCIe themselves and no H2D copy exists); d_work_params (B x 64 int32),
- * d_work_quant (B x 256 u16), d_coef, d_planes: device workspaces; d_err[b]: 0 ok / 1 invalid code / 2 missing restart segment. */
+ * d_work_quant (B x 256 u16), d_coef, d_planes: device workspaces; d_err[b]: 0 ok / 1 invalid code / 2 missing restart segment /
+ * 3 the scan ended before the last MCU (more bytes consumed than its unpadded length, d_params[b][14]). */
 int sgic_jpeg_decode_batch(const int32_t *d_params, const uint8_t *d_scan, const uint8_t *d_tabs, const int32_t *d_segs,
                            const uint16_t *d_quant, int32_t *d_work_params, uint16_t *d_work_quant, int16_t *d_coef,
                            uint8_t *d_planes, uint8_t *d_out, int32_t *d_err, int B, int H, int W, int max_blocks,
@@ -515,7 +516,8 @@ int sgic_jpeg_decode_batch(const int32_t *d_params, const uint8_t *d_scan, const
  * byte stuffing (sgic_amd/jpeg.py ScanJpegBatch); d_descs: 32-int32 scan descriptors sorted by dependency level -- level l is
  * [h_level_start[l], h_level_start[l + 1]) of the HOST array h_level_start (nlevels + 1 entries), one launch per level, one wave per
  * scan; d_tabs: the batch's deduplicated Huffman lookup-table pool.  d_coef (total_blocks * 64 int16) is zeroed here.  Other
- * arguments as sgic_jpeg_decode_batch; d_err[b]: 0 ok / 1 invalid code / 2 missing restart segment / 3 coefficient past its band. */
+ * arguments as sgic_jpeg_decode_batch; d_err[b]: 0 ok / 1 invalid code / 2 missing restart segment / 3 coefficient past its band, or
+ * the scan ended before its last unit (more bytes consumed than its unpadded length, descriptor slot 29). */
 int sgic_jpeg_decode_scans_batch(const int32_t *d_params, const int32_t *d_descs, const uint8_t *d_scan, const uint8_t *d_tabs,
                                  const int32_t *d_segs, const uint16_t *d_quant, int32_t *d_work_params, uint16_t *d_work_quant,
                                  int16_t *d_coef, uint8_t *d_planes, uint8_t *d_out, int32_t *d_err, int B, int H, int W,

@@ -31,6 +31,12 @@ class _Bits:
     def seek(self, byte_off):
         self.pos, self.acc, self.cnt = byte_off, 0, 0
 
+    def check_end(self):
+        """after the last MCU / unit: a valid encoder pads its last byte and stops, so a decode that used more bytes than the segment
+        holds has read the zeros past its end -- the kernels' error code 3"""
+        if (self.pos * 8 - self.cnt + 7) // 8 > len(self.d):
+            raise ValueError("the scan ended before the last MCU")
+
 
 def _decode_sym(br, tab):
     fast = tab[:1024].view(np.uint16)
@@ -90,6 +96,7 @@ def huffman_decode(p):
                         k += r
                         blk[NATURAL[k]] = _receive(br, s)
                         k += 1
+    br.check_end()
     return coefs
 
 

@@ -26,6 +26,7 @@
 
 enum {
   P_SCAN_OFF = 0, P_SCAN_LEN, P_TAB_OFF, P_QUANT_OFF, P_NCOMP, P_W, P_H, P_HMAX, P_VMAX, P_MCUS_X, P_MCUS_Y, P_RESTART, P_SEG_OFF, P_NSEG,
+  P_SCAN_BYTES = 14,   // the scan's own length in bytes (P_SCAN_LEN is that length padded with zeros to whole chunks)
   P_COMP0 = 16,   // per component, 12 ints: h, v, qtab, dctab, actab, blocks_w, blocks_h, comp_w, comp_h, coef_off (blocks), plane_off (bytes), unused
   P_CSTRIDE = 12
 };
@@ -122,6 +123,9 @@ struct JpgBits {
     cnt -= n;
     return v;
   }
+  // bytes of the segment the decode has used so far: from the bit position (rp counts the words prefetched into `acc`, of which `cnt`
+  // bits are still unread), not from the prefetch pointer
+  __device__ __forceinline__ int consumed() const { return (rp * 8 - cnt + 7) >> 3; }
   __device__ __forceinline__ int receive(int s) {   // s extra bits, sign-extended (jdhuff.c HUFF_EXTEND)
     const int v = (int)bits(s);
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
@@ -178,6 +182,10 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
         for (int bx = 0; bx < hs; bx++) {
           blk[lane] = 0;
           int s = br.decode(Tdc);
+          if (s > 15) {   // not a magnitude category (the host refuses such a DC table: sgic_amd/jpeg.py _check_dc_table)
+            bad = 1;
+            s = 0;
+          }
           if (s) {
             br.refill();
             pred[c] += br.receive(s);
@@ -203,6 +211,8 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const int *__restrict__ p
         }
     }
   }
+  // a valid encoder pads its last byte with ones and stops: a decode that needed more bits than the scan holds read the zero padding
+  if (!bad && br.consumed() > P[P_SCAN_BYTES]) bad = 3;
   if (lane == 0) err[img] = bad;
 }
 
@@ -218,6 +228,7 @@ enum {   // per-scan descriptor, 32 int32 (sgic_amd/jpeg.py: S_*)
   S_NTAB = 17, S_TAB0,   // the scan's (<= 4) Huffman tables: indices into the batch's table pool
   S_DC0 = 22, S_AC0 = 25,   // per scan component: its DC / AC table among the scan's (0..3)
   S_FIRST = 28,   // the image's first scan (level 0): copies params / quant into device memory for the IDCT / colour kernels
+  S_SCAN_BYTES = 29,   // the scan's own length in bytes (S_SCAN_LEN is that length padded with zeros to whole chunks)
   JPG_NS = 32
 };
 enum { M_SEQ = 0, M_DC_FIRST, M_DC_REFINE, M_AC_FIRST, M_AC_REFINE };
@@ -448,6 +459,7 @@ __global__ __launch_bounds__(64) void jpeg_scan_kernel(const int *__restrict__ p
       }
     }
   }
+  if (!bad && br.consumed() > S[S_SCAN_BYTES]) bad = 3;   // the scan ended before its last unit (as in jpeg_huff_kernel)
   if (lane == 0 && bad) atomicMax(err + img, bad);
 }
 
@@ -519,7 +531,7 @@ __global__ void jpeg_idct_kernel(const int *__restrict__ params, const short *__
     const int *C = P + P_COMP0 + c * P_CSTRIDE;
     const int bw = C[5], by = local / bw, bx = local - by * bw;
     const short *cf = coef + ((size_t)C[9] + local) * 64;
-    const unsigned short *q = quant + (size_t)img * 256 + C[2] * 64;   // quant_dev of jpeg_huff_kernel: image-major
+    const unsigned short *q = quant + (size_t)img * 256 + (C[2] & 3) * 64;   // quant_dev of jpeg_huff_kernel: image-major, 4 tables each
     int ws[64];
     // pass 1: columns
 #pragma unroll
@@ -610,7 +622,8 @@ __global__ void jpeg_color_kernel(const int *__restrict__ params, const unsigned
 //   d_params  B x 64 int32 (layout above, built by sgic_amd/jpeg.py), d_scan the cleaned entropy-coded segments (each padded to a
 //   multiple of 2048 bytes), d_tabs B x 4 Huffman tables (dc0, dc1, ac0, ac1) of 1424 bytes, d_segs the restart-interval byte offsets,
 //   d_quant u16 quantisation tables in natural order, d_coef / d_planes workspaces (total_blocks * 64 int16 / plane_bytes u8),
-//   d_err B int32 (0 ok, 1 invalid Huffman code, 2 missing restart segment).  max_blocks = the largest per-image block count.
+//   d_err B int32 (0 ok, 1 invalid Huffman code or DC size, 2 missing restart segment, 3 the scan ended before the last MCU: more bytes
+//   were consumed than the unpadded length in params[14]).  max_blocks = the largest per-image block count.
 //   The five input arrays may be device memory or device-accessible PINNED host memory (no copy is then needed at all);
 //   d_work_params (B x 64 int32) / d_work_quant (B x 256 u16): device scratch for the copies the later kernels read.
 extern "C" int sgic_jpeg_decode_batch(const int32_t *d_params, const uint8_t *d_scan, const uint8_t *d_tabs, const int32_t *d_segs,
@@ -635,8 +648,9 @@ extern "C" int sgic_jpeg_decode_batch(const int32_t *d_params, const uint8_t *d_
 // Decode a batch of B JPEGs of equal geometry given as SCANS (progressive files, multi-scan sequential files, and baseline files as one
 // sequential scan each) to RGB u8 HWC (B, H, W, 3).  d_descs: nscans x 32 int32 scan descriptors sorted by dependency level, level l
 // being descriptors [h_level_start[l], h_level_start[l + 1]) (host array, nlevels + 1 entries); d_tabs: the batch's Huffman table pool
-// (1424 B each).  Other arguments as sgic_jpeg_decode_batch; d_err[b]: 0 ok, 1 invalid Huffman code, 2 missing restart segment,
-// 3 coefficient past the end of its band.
+// (1424 B each).  Other arguments as sgic_jpeg_decode_batch; d_err[b]: 0 ok, 1 invalid Huffman code or DC size, 2 missing restart segment,
+// 3 corrupt scan data: a coefficient past the end of its band, or the scan ended before its last unit (more bytes consumed than the
+// unpadded length in descriptor slot 29).
 extern "C" int sgic_jpeg_decode_scans_batch(const int32_t *d_params, const int32_t *d_descs, const uint8_t *d_scan, const uint8_t *d_tabs,
                                             const int32_t *d_segs, const uint16_t *d_quant, int32_t *d_work_params, uint16_t *d_work_quant,
                                             int16_t *d_coef, uint8_t *d_planes, uint8_t *d_out, int32_t *d_err, int B, int H, int W,

@@ -7,6 +7,13 @@ custom Huffman / quantisation tables.  Anything else (progressive, arithmetic co
 chroma planes too narrow for the fancy upsampler) raises `Unsupported`, and the ingest falls back to the host decoder for that
 batch -- the result is the same pixels either way, the GPU path being bit-exact with Pillow (tests/test_gpu_jpeg.py).
 
+Files are untrusted input.  Also refused (`Unsupported`, never a bare IndexError), so that a damaged file reaches the host decoder and
+its proper error instead of a kernel: a file cut short (no marker ends the entropy-coded segment, a marker segment longer than the
+file, a truncated SOS / SOF / DHT / DQT / DRI payload), Tq > 3, Th > 3 or Tc > 1, DHT counts above 256 or above what the segment holds,
+a DC table with a symbol above 15, H == 0 or W == 0, RSTn markers without a restart interval or not numbered 0, 1, .. 7, 0, ..  What
+a parser cannot see -- a scan that ends before its last MCU in front of an intact EOI -- the kernels report as error code 3: they
+compare the bytes consumed with the scan's unpadded length (P_SCAN_BYTES / S_SCAN_BYTES).  tests/jpeg_forge.py forges such files.
+
 parse_scans() / ScanJpegBatch take progressive Huffman and multi-scan sequential files as well (and baseline files as one scan, so that
 mixed batches decode together): one descriptor per scan, decoded by csrc/jpeg.hip jpeg_scan_kernel (tests/test_gpu_jpeg_scans.py)."""
 import struct
@@ -18,6 +25,7 @@ LOOK = 9
 TAB_BYTES = 1424
 CHUNK = 2048
 P_SCAN_OFF, P_SCAN_LEN, P_TAB_OFF, P_QUANT_OFF, P_NCOMP, P_W, P_H, P_HMAX, P_VMAX, P_MCUS_X, P_MCUS_Y, P_RESTART, P_SEG_OFF, P_NSEG = range(14)
+P_SCAN_BYTES = 14        # the scan's own length, without the zero padding of P_SCAN_LEN: decoding past it is error code 3
 P_COMP0, P_CSTRIDE = 16, 12
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49,
@@ -88,15 +96,109 @@ def _frame_geometry(frame, adobe_transform):
     return H, W, nc, hmax, vmax, comps
 
 
-def _clean_segment(data, pos):
+# ---- checks on untrusted marker segments, shared by parse() and parse_scans(): a damaged file is refused (Unsupported), never
+# ---- indexed past its end and never handed to a kernel with a table index or a symbol the kernels do not expect ----------------------
+def _marker_segment(data, pos):
+    """marker segment whose 2-byte length field is at `pos` -> (length, payload); the segment must lie inside the file"""
+    if pos + 2 > len(data):
+        raise Unsupported("truncated marker segment")
+    ln = struct.unpack(">H", data[pos:pos + 2])[0]
+    if ln < 2 or pos + ln > len(data):
+        raise Unsupported("marker segment runs past the end of the file")
+    return ln, data[pos + 2:pos + ln]
+
+
+def _dqt_tables(seg):
+    """DQT payload -> [(Tq, (64,) u16 table in natural order)]"""
+    out, i = [], 0
+    while i < len(seg):
+        pq, tq = seg[i] >> 4, seg[i] & 15
+        i += 1
+        if tq > 3 or pq > 1:
+            raise Unsupported("bad quantisation table id / precision")
+        nb = 128 if pq else 64
+        if i + nb > len(seg):
+            raise Unsupported("truncated DQT")
+        t = np.frombuffer(seg[i:i + nb], dtype=">u2" if pq else np.uint8).astype(np.uint16)
+        i += nb
+        nat = np.zeros(64, dtype=np.uint16)
+        nat[ZIGZAG] = t
+        out.append((tq, nat))
+    return out
+
+
+def _dht_tables(seg):
+    """DHT payload -> [(Tc, Th, bits u8[16], symbols u8[sum(bits)])]"""
+    out, i = [], 0
+    while i < len(seg):
+        if i + 17 > len(seg):
+            raise Unsupported("truncated DHT")
+        tc, th = seg[i] >> 4, seg[i] & 15
+        if th > 3 or tc > 1:
+            raise Unsupported("bad Huffman table slot")
+        bits = np.frombuffer(seg[i + 1:i + 17], dtype=np.uint8)
+        cnt = int(bits.sum())
+        if cnt > 256 or i + 17 + cnt > len(seg):
+            raise Unsupported("Huffman table with more symbols than 256 or than its segment holds")
+        out.append((tc, th, bits, np.frombuffer(seg[i + 17:i + 17 + cnt], dtype=np.uint8)))
+        i += 17 + cnt
+    return out
+
+
+def _sof_frame(seg):
+    """SOF payload -> (H, W, [(id, h, v, Tq)]) of an 8-bit frame"""
+    if len(seg) < 6:
+        raise Unsupported("truncated SOF")
+    prec, H, W, nc = struct.unpack(">BHHB", seg[:6])
+    if prec != 8:
+        raise Unsupported("not 8-bit")
+    if len(seg) < 6 + 3 * nc:
+        raise Unsupported("truncated SOF")
+    if H == 0 or W == 0:
+        raise Unsupported("empty frame (or a height left to a DNL marker)")
+    comps = [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nc)]
+    if any(tq > 3 for _, _, _, tq in comps):
+        raise Unsupported("bad quantisation table id")
+    return H, W, comps
+
+
+def _sos_header(seg):
+    """SOS payload -> ([(component id, Td, Ta)], Ss, Se, Ah << 4 | Al)"""
+    ns = seg[0] if len(seg) else 0
+    if len(seg) < 4 + 2 * ns:
+        raise Unsupported("truncated SOS")
+    sel = [(seg[1 + 2 * c], seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15) for c in range(ns)]
+    return sel, seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]
+
+
+def _restart_interval(seg):
+    if len(seg) < 2:
+        raise Unsupported("truncated DRI")
+    return struct.unpack(">H", seg[:2])[0]
+
+
+def _check_dc_table(tab):
+    """a table used as a DC table codes a magnitude category: a symbol above 15 is corrupt (jdhuff.c jpeg_make_d_derived_tbl) and
+    would have the kernels read that many extra bits"""
+    if int(tab[1168:1424].max()) > 15:
+        raise Unsupported("DC Huffman table with a symbol above 15")
+
+
+def _clean_segment(data, pos, restart):
     """entropy-coded segment starting at byte `pos` -> (cleaned u8 bytes, restart offsets i32, position of the marker ending it).
     The segment runs up to the marker that is not RSTn / stuffing; un-stuff, drop the RSTn markers and remember where each restart
-    interval starts in the cleaned stream"""
+    interval starts in the cleaned stream.  `restart`: the restart interval in force.  Raises Unsupported when no marker ends the
+    segment (a truncated file), when it holds RSTn markers although restart == 0, or when they are not numbered 0, 1, .. 7, 0, ..
+    (libjpeg resynchronises on those, which the GPU path does not restate)"""
+    if pos >= len(data):
+        raise Unsupported("file ends at the scan header")
     raw = np.frombuffer(data, dtype=np.uint8, offset=pos)
     ff = np.nonzero(raw[:-1] == 0xFF)[0]
     nxt = raw[ff + 1]
     stop = ff[(nxt != 0) & ~((nxt >= 0xD0) & (nxt <= 0xD7)) & (nxt != 0xFF)]
-    end = int(stop[0]) if len(stop) else len(raw)
+    if not len(stop):
+        raise Unsupported("truncated file: no marker ends the entropy-coded segment")
+    end = int(stop[0])
     raw = raw[:end]
     ff = ff[ff < end - 1] if end > 0 else ff[:0]
     nxt = raw[ff + 1] if len(ff) else nxt[:0]
@@ -104,6 +206,8 @@ def _clean_segment(data, pos):
     stuffed = ff[nxt == 0]
     keep[stuffed + 1] = False
     rst = ff[(nxt >= 0xD0) & (nxt <= 0xD7)]
+    if len(rst) and (restart == 0 or (raw[rst + 1] != 0xD0 + (np.arange(len(rst)) & 7)).any()):
+        raise Unsupported("restart markers without a restart interval, or out of sequence")
     keep[rst] = False
     keep[rst + 1] = False
     keep[ff[nxt == 0xFF]] = False                   # fill bytes (an 0xFF in front of another 0xFF) are not data (T.81 B.1.1.2)
@@ -128,61 +232,36 @@ def parse(data):
             raise Unsupported("truncated before SOS")
         if data[pos] != 0xFF:
             raise Unsupported("marker expected")
-        while data[pos + 1] == 0xFF:
+        while pos + 2 < n and data[pos + 1] == 0xFF:
             pos += 1
         m = data[pos + 1]
         pos += 2
         if m in (0x01,) or 0xD0 <= m <= 0xD7:
             continue
-        ln = struct.unpack(">H", data[pos:pos + 2])[0]
-        seg = data[pos + 2:pos + ln]
+        ln, seg = _marker_segment(data, pos)
         if m == 0xDB:
-            i = 0
-            while i < len(seg):
-                pq, tq = seg[i] >> 4, seg[i] & 15
-                i += 1
-                if pq:
-                    t = np.frombuffer(seg[i:i + 128], dtype=">u2").astype(np.uint16)
-                    i += 128
-                else:
-                    t = np.frombuffer(seg[i:i + 64], dtype=np.uint8).astype(np.uint16)
-                    i += 64
-                nat = np.zeros(64, dtype=np.uint16)
-                nat[ZIGZAG] = t
-                qt[tq] = nat
+            qt.update(_dqt_tables(seg))
         elif m == 0xC4:
-            i = 0
-            while i < len(seg):
-                tc, th = seg[i] >> 4, seg[i] & 15
-                bits = np.frombuffer(seg[i + 1:i + 17], dtype=np.uint8)
-                cnt = int(bits.sum())
-                vals = np.frombuffer(seg[i + 17:i + 17 + cnt], dtype=np.uint8)
-                i += 17 + cnt
-                if th > 1 or tc > 1:
+            for tc, th, bits, vals in _dht_tables(seg):
+                if th > 1:
                     raise Unsupported("more than two Huffman tables per class")
                 ht[(tc, th)] = huff_table(bits, vals)
         elif m in (0xC0, 0xC1):
-            prec, H, W, nc = struct.unpack(">BHHB", seg[:6])
-            if prec != 8:
-                raise Unsupported("not 8-bit")
-            frame = (H, W, [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nc)])
+            frame = _sof_frame(seg)
         elif m in (0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF):
             raise Unsupported("progressive / lossless / arithmetic JPEG")
         elif m == 0xDD:
-            restart = struct.unpack(">H", seg[:2])[0]
+            restart = _restart_interval(seg)
         elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
             adobe_transform = seg[11]
         elif m == 0xDA:
             if frame is None:
                 raise Unsupported("SOS before SOF")
-            ns = seg[0]
+            sel, ss, se, ahal = _sos_header(seg)
             H, W, comps = frame
-            if ns != len(comps):
+            if len(sel) != len(comps):
                 raise Unsupported("non-interleaved multi-scan file")
-            sel = {}
-            for c in range(ns):
-                sel[seg[1 + 2 * c]] = (seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15)
-            ss, se, ahal = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]
+            sel = {cid: (td, ta) for cid, td, ta in sel}
             if (ss, se, ahal) != (0, 63, 0):
                 raise Unsupported("not a sequential scan")
             pos += ln
@@ -207,7 +286,9 @@ def parse(data):
     p.tabs = np.zeros((4, TAB_BYTES), dtype=np.uint8)
     for (tc, th), t in ht.items():
         p.tabs[2 * tc + th] = t
-    p.scan, p.segs, _ = _clean_segment(data, pos)
+    for d in p.comps:
+        _check_dc_table(p.tabs[d["dc"]])
+    p.scan, p.segs, _ = _clean_segment(data, pos, restart)
     if restart and len(p.segs) < -(-p.mcus_x * p.mcus_y // restart):
         raise Unsupported("restart markers missing")
     return p
@@ -270,6 +351,7 @@ class JpegBatch:
             r[P_SCAN_OFF], r[P_SCAN_LEN], r[P_TAB_OFF], r[P_QUANT_OFF] = scan_off, scan_len[b], b * 4 * TAB_BYTES, b * 256
             r[P_NCOMP], r[P_W], r[P_H], r[P_HMAX], r[P_VMAX] = p.ncomp, p.W, p.H, p.hmax, p.vmax
             r[P_MCUS_X], r[P_MCUS_Y], r[P_RESTART], r[P_SEG_OFF], r[P_NSEG] = p.mcus_x, p.mcus_y, p.restart, seg_off, len(p.segs)
+            r[P_SCAN_BYTES] = len(p.scan)
             nblk = 0
             for c, d in enumerate(p.comps):
                 o = P_COMP0 + c * P_CSTRIDE
@@ -315,7 +397,7 @@ class JpegBatch:
 
 # ---- multi-scan files: progressive Huffman (T.81 Annex G), multi-scan sequential, and baseline files as one scan ---------------------
 S_IMG, S_MODE, S_NCOMP, S_COMP0, S_SS, S_SE, S_AH, S_AL, S_RESTART, S_SCAN_OFF, S_SCAN_LEN, S_SEG_OFF, S_NSEG = 0, 1, 2, 3, 6, 7, 8, 9, 10, 11, 12, 13, 14
-S_GW, S_GH, S_NTAB, S_TAB0, S_DC0, S_AC0, S_FIRST = 15, 16, 17, 18, 22, 25, 28
+S_GW, S_GH, S_NTAB, S_TAB0, S_DC0, S_AC0, S_FIRST, S_SCAN_BYTES = 15, 16, 17, 18, 22, 25, 28, 29
 NS = 32
 M_SEQ, M_DC_FIRST, M_DC_REFINE, M_AC_FIRST, M_AC_REFINE = range(5)
 
@@ -356,36 +438,13 @@ def parse_scans(data):
             break
         if m in (0x01,) or 0xD0 <= m <= 0xD7:
             continue
-        if pos + 2 > n:
-            raise Unsupported("truncated marker segment")
-        ln = struct.unpack(">H", data[pos:pos + 2])[0]
-        seg = data[pos + 2:pos + ln]
+        ln, seg = _marker_segment(data, pos)
         if m == 0xDB:
             if scans:
                 raise Unsupported("quantisation table redefined between scans")
-            i = 0
-            while i < len(seg):
-                pq, tq = seg[i] >> 4, seg[i] & 15
-                i += 1
-                if pq:
-                    t = np.frombuffer(seg[i:i + 128], dtype=">u2").astype(np.uint16)
-                    i += 128
-                else:
-                    t = np.frombuffer(seg[i:i + 64], dtype=np.uint8).astype(np.uint16)
-                    i += 64
-                nat = np.zeros(64, dtype=np.uint16)
-                nat[ZIGZAG] = t
-                qt[tq] = nat
+            qt.update(_dqt_tables(seg))
         elif m == 0xC4:
-            i = 0
-            while i < len(seg):
-                tc, th = seg[i] >> 4, seg[i] & 15
-                bits = np.frombuffer(seg[i + 1:i + 17], dtype=np.uint8)
-                cnt = int(bits.sum())
-                vals = np.frombuffer(seg[i + 17:i + 17 + cnt], dtype=np.uint8)
-                i += 17 + cnt
-                if th > 3 or tc > 1:
-                    raise Unsupported("bad Huffman table slot")
+            for tc, th, bits, vals in _dht_tables(seg):
                 t = huff_table(bits, vals)
                 ht[(tc, th)] = tab_idx.setdefault(t.tobytes(), len(tabs))
                 if ht[(tc, th)] == len(tabs):
@@ -393,15 +452,12 @@ def parse_scans(data):
         elif m in (0xC0, 0xC1, 0xC2):
             if frame is not None:
                 raise Unsupported("two frames")
-            prec, H, W, nc = struct.unpack(">BHHB", seg[:6])
-            if prec != 8:
-                raise Unsupported("not 8-bit")
-            frame = (H, W, [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nc)])
+            frame = _sof_frame(seg)
             progressive = m == 0xC2
         elif m in (0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF):
             raise Unsupported("lossless / hierarchical / arithmetic JPEG")
         elif m == 0xDD:
-            restart = struct.unpack(">H", seg[:2])[0]
+            restart = _restart_interval(seg)
         elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
             adobe_transform = seg[11]
         elif m == 0xDA:
@@ -412,19 +468,22 @@ def parse_scans(data):
                 p.progressive = progressive
                 coef_bits = np.full((p.ncomp, 64), -1, dtype=np.int32)
             ids = [c[0] for c in frame[2]]
-            ns = seg[0]
-            sel = [(seg[1 + 2 * c], seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15) for c in range(ns)]
+            sel, s_ss, s_se, s_ahal = _sos_header(seg)
+            ns = len(sel)
             if not 1 <= ns <= 3 or any(cid not in ids for cid, _, _ in sel) or len({cid for cid, _, _ in sel}) != ns:
                 raise Unsupported("bad scan component list")
             s = Scan()
             s.comps = [ids.index(cid) for cid, _, _ in sel]
-            s.ss, s.se, s.ah, s.al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+            s.ss, s.se, s.ah, s.al = s_ss, s_se, s_ahal >> 4, s_ahal & 15
             s.mode = _check_progression(s, progressive, coef_bits)
             need_dc, need_ac = s.mode in (M_SEQ, M_DC_FIRST), s.mode in (M_SEQ, M_AC_FIRST, M_AC_REFINE)
             if (need_dc and any((0, td) not in ht for _, td, _ in sel)) or (need_ac and any((1, ta) not in ht for _, _, ta in sel)):
                 raise Unsupported("missing Huffman table")
             s.dc = [ht[(0, td)] if need_dc else None for _, td, _ in sel]
             s.ac = [ht[(1, ta)] if need_ac else None for _, _, ta in sel]
+            for t in s.dc:
+                if t is not None:
+                    _check_dc_table(tabs[t])
             if len({t for t in s.dc + s.ac if t is not None}) > 4:
                 raise Unsupported("more than four Huffman tables in one scan")
             if ns == 1:
@@ -433,7 +492,7 @@ def parse_scans(data):
             else:
                 s.gw, s.gh = p.mcus_x, p.mcus_y
             s.restart = restart
-            s.data, s.segs, pos = _clean_segment(data, pos + ln)
+            s.data, s.segs, pos = _clean_segment(data, pos + ln, restart)
             if restart and len(s.segs) < -(-s.gw * s.gh // restart):
                 raise Unsupported("restart markers missing")
             s.level = 1 + max([t.level for t in scans if set(t.comps) & set(s.comps) and t.ss <= s.se and s.ss <= t.se], default=0)
@@ -569,7 +628,7 @@ class ScanJpegBatch:
             d[S_COMP0:S_COMP0 + len(s.comps)] = s.comps
             d[S_SS], d[S_SE], d[S_AH], d[S_AL], d[S_RESTART] = s.ss, s.se, s.ah, s.al, s.restart
             d[S_SCAN_OFF], d[S_SCAN_LEN], d[S_SEG_OFF], d[S_NSEG] = scan_off, padded(len(s.data)), seg_off, len(s.segs)
-            d[S_GW], d[S_GH], d[S_NTAB], d[S_FIRST] = s.gw, s.gh, len(local), int(i == 0)
+            d[S_GW], d[S_GH], d[S_NTAB], d[S_FIRST], d[S_SCAN_BYTES] = s.gw, s.gh, len(local), int(i == 0), len(s.data)
             d[S_TAB0:S_TAB0 + len(local)] = [remap[b][t] for t in local]
             d[S_DC0:S_DC0 + len(s.comps)] = [local.index(t) if t is not None else 0 for t in s.dc]
             d[S_AC0:S_AC0 + len(s.comps)] = [local.index(t) if t is not None else 0 for t in s.ac]

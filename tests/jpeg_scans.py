@@ -112,6 +112,7 @@ def decode_coefs(p):
                                 blk[z] += p1 if blk[z] >= 0 else -p1
                             k += 1
                         eobrun -= 1
+        br.check_end()
     return coefs
 
 
@@ -330,46 +331,59 @@ def transcode(data, script, restart=0, sequential=False):
             hv = [(c, p.comps[c]["h"], p.comps[c]["v"]) for c in comps]
             blocks_of = lambda u, hv=hv, gw=gw: [(c, (u // gw) * v + by, (u % gw) * h + bx) for c, h, v in hv for by in range(v) for bx in range(h)]
         ev = _events(coefs, comps, blocks_of, gw * gh, ss, se, ah, al, restart, (slot, sequential))
-        freq = {}
-        for e in ev:
-            if e[0] == "s":
-                freq.setdefault(e[1], np.zeros(256, dtype=np.int64))[e[2]] += 1
-        codes, dht = {}, b""
-        for key in sorted(freq):
-            bits, vals = _optimal_table(freq[key])
-            codes[key] = _codes(bits, vals)
-            dht += bytes([(0 if key[0] == "dc" else 1) << 4 | key[1]]) + bytes(bits) + bytes(vals)
+        codes, dht = tables_for(ev)
         if dht:
             out += _segment(0xC4, dht)
         out += _segment(0xDD, struct.pack(">H", restart))
         out += _segment(0xDA, bytes([len(comps)]) + b"".join(bytes([c + 1, slot[c] << 4 | slot[c]]) for c in comps) + bytes([ss, se, ah << 4 | al]))
-        acc, n, nrst = 0, 0, 0
-        body = bytearray()
-
-        def flush_bytes(acc, n):
-            while n >= 8:
-                b = (acc >> (n - 8)) & 255
-                body.append(b)
-                if b == 0xFF:
-                    body.append(0)
-                n -= 8
-            return acc & ((1 << n) - 1), n
-        for e in ev:
-            if e[0] == "rst":
-                if n:
-                    acc, n = (acc << (8 - n)) | ((1 << (8 - n)) - 1), 8
-                    acc, n = flush_bytes(acc, n)
-                body += bytes([0xFF, 0xD0 + (nrst & 7)])
-                nrst += 1
-                continue
-            code, l = codes[e[1]][e[2]] if e[0] == "s" else (e[1], e[2])
-            acc, n = (acc << l) | code, n + l
-            acc, n = flush_bytes(acc, n)
-        if n:
-            acc, n = flush_bytes((acc << (8 - n)) | ((1 << (8 - n)) - 1), 8)
-        out += body
+        out += pack_events(ev, codes)
     out += b"\xff\xd9"
     return bytes(out)
+
+
+def tables_for(ev):
+    """events of one scan -> ({table key: {symbol: (code, length)}}, the DHT payload of optimal tables for their symbol statistics);
+    a key is ("dc" | "ac", slot)"""
+    freq = {}
+    for e in ev:
+        if e[0] == "s":
+            freq.setdefault(e[1], np.zeros(256, dtype=np.int64))[e[2]] += 1
+    codes, dht = {}, b""
+    for key in sorted(freq):
+        bits, vals = _optimal_table(freq[key])
+        codes[key] = _codes(bits, vals)
+        dht += bytes([(0 if key[0] == "dc" else 1) << 4 | key[1]]) + bytes(bits) + bytes(vals)
+    return codes, dht
+
+
+def pack_events(ev, codes):
+    """events of one scan -> its entropy-coded segment: Huffman codes and raw bits MSB first, a zero byte stuffed after every 0xFF,
+    the last byte before an RSTn marker and at the end padded with ones, RSTn numbered mod 8"""
+    acc, n, nrst = 0, 0, 0
+    body = bytearray()
+
+    def flush_bytes(acc, n):
+        while n >= 8:
+            b = (acc >> (n - 8)) & 255
+            body.append(b)
+            if b == 0xFF:
+                body.append(0)
+            n -= 8
+        return acc & ((1 << n) - 1), n
+    for e in ev:
+        if e[0] == "rst":
+            if n:
+                acc, n = (acc << (8 - n)) | ((1 << (8 - n)) - 1), 8
+                acc, n = flush_bytes(acc, n)
+            body += bytes([0xFF, 0xD0 + (nrst & 7)])
+            nrst += 1
+            continue
+        code, l = codes[e[1]][e[2]] if e[0] == "s" else (e[1], e[2])
+        acc, n = (acc << l) | code, n + l
+        acc, n = flush_bytes(acc, n)
+    if n:
+        acc, n = flush_bytes((acc << (8 - n)) | ((1 << (8 - n)) - 1), 8)
+    return body
 
 
 # ---- the test corpus ---------------------------------------------------------------------------------------------------------------------
