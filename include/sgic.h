@@ -451,6 +451,43 @@ int sgic_lpips_head_work_bytes(int B, int H, int W, size_t *bytes);
 int sgic_lpips_head(const float *d_feat, const float *d_w, int B, int H, int W, int C, uint8_t *d_work, size_t work_bytes,
                     double *d_d, sgic_stream_t stream);
 
+/* DISTS with the VGG16 trunk (dists.DistsVGG, evaluate.py --dists_ckpt; DISTS_pytorch / piq.DISTS): the
+ * memory-bound glue around sgic_conv3x3_split3_f32, which runs the same thirteen convolutions as for LPIPS.  All planes are slice-major
+ * (a_packed = 1) with a zero halo; only the interior is written (the sgic_halo_copy_split3 contract).
+ *
+ * sgic_dists_input_split3: as sgic_lpips_input_split3 with another input layer.  Per channel c, each step one IEEE fp32 operation:
+ * x = float(u) / 255; y = (x - mean_c) / std_c with mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225).
+ *
+ * sgic_dists_moments_u8 (tap 0): d_a, d_b (B, H, W, 3) u8 -> d_sums (B, 3, 5) int64 = (sum a, sum b, sum a^2, sum b^2, sum a b) over
+ * the pixels of every pair and channel, exact (the entry clears d_sums first; 64-bit integer adds).
+ *
+ * sgic_relu_l2pool_halo_split3: d_in (B H W, C) fp32 BEFORE relu -> relu -> square -> the window g = (1, 2, 1) x (1, 2, 1) / 16 (the
+ * normalised 3x3 Hanning window) at stride 2 with zero padding 1 -> + 1e-12 -> sqrt -> the interior of the planes [3][C / 32][B (H'+2)
+ * (W'+2)][32], H' = (H + 1) / 2, W' = (W + 1) / 2.  fp32, the nine terms added in row-major order of the window, first to last.
+ *
+ * sgic_dists_moments: d_feat (2 B H W, C) fp32 BEFORE relu, pair b = rows of image b and of image B + b -> d_sums (B, 5, C) fp64 = (sum
+ * x, sum y, sum x^2, sum y^2, sum x y) over the pixels, x = relu of the first side, y of the second; the products are exact in fp64.
+ * A workgroup writes one partial per channel into d_work, a second kernel adds the partials in a fixed order: no float atomics, the
+ * same input gives the same bits.  d_work: at least the *bytes sgic_dists_moments_work_bytes returns (host-only, takes no stream).
+ *
+ * sgic_dists_head: d_sums (B, 5, C) of sgic_dists_moments, d_alpha, d_beta (C) fp32 -> d_terms (B, 2) fp64 = (sum_c alpha_c (1 - S1_c),
+ * sum_c beta_c (1 - S2_c)) with n = H W, mu = sum / n, var_x = sum x^2 / n - mu_x mu_x, cov = sum x y / n - mu_x mu_y (one expression, so
+ * x == y gives exactly 0 for both), S1 = (2 mu_x mu_y + 1e-6) / (mu_x^2 + mu_y^2 + 1e-6), S2 = (2 cov + 1e-6) / (var_x + var_y + 1e-6).
+ * The channels are added in a fixed order.
+ *
+ * SGIC_EINVAL before any launch: a null pointer, B < 1 (B > 65535 where pairs are grid rows), H or W < 1, C % 32 != 0 (moments: C >
+ * 1024), a misaligned buffer (16 bytes for planes, features and workspace, 8 for int64 / fp64), image slots outside total_images, a
+ * workspace that is too small. */
+int sgic_dists_input_split3(const uint8_t *d_img, int B, int H, int W, int total_images, int image_offset, uint16_t *d_halo_planes,
+                            sgic_stream_t stream);
+int sgic_dists_moments_u8(const uint8_t *d_a, const uint8_t *d_b, int B, int H, int W, int64_t *d_sums, sgic_stream_t stream);
+int sgic_relu_l2pool_halo_split3(const float *d_in, int B, int H, int W, int C, uint16_t *d_halo_planes, sgic_stream_t stream);
+int sgic_dists_moments_work_bytes(int B, int H, int W, int C, size_t *bytes);
+int sgic_dists_moments(const float *d_feat, int B, int H, int W, int C, uint8_t *d_work, size_t work_bytes, double *d_sums,
+                       sgic_stream_t stream);
+int sgic_dists_head(const double *d_sums, const float *d_alpha, const float *d_beta, int B, int H, int W, int C, double *d_terms,
+                    sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

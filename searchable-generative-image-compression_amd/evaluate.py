@@ -15,6 +15,9 @@
                                                                 with the VGG16 trunk (lpips.LpipsVGG) on the same u8 tensors; P: one
                                                                 or more state dict files that together hold the trunk and the lin
                                                                 layers (lpips.load_weights)
+  evaluate.py ... --dists_ckpt P [P ...]                        adds "dists" in the same places (after "lpips" where both are asked
+                                                                for): DISTS with the VGG16 trunk (dists.DistsVGG); P: state dict
+                                                                file(s) with the trunk, alpha and beta (dists.load_weights)
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -61,7 +64,7 @@ def _json_number(v):
 
 def summarise(records):
     """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
-    lpips when the records carry it"""
+    lpips and of dists when the records carry them"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
@@ -71,6 +74,8 @@ def summarise(records):
            "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
     if any("lpips" in r for r in records):
         out["lpips"] = mean([r["lpips"] for r in records if r.get("lpips") is not None])
+    if any("dists" in r for r in records):
+        out["dists"] = mean([r["dists"] for r in records if r.get("dists") is not None])
     anchors = [r["anchor"] for r in records if "anchor" in r]
     if anchors:      # the same means over the anchors; over_rate counts the images whose smallest JPEG is larger than the container
         ams = mean([a["ms_ssim"] for a in anchors if a["ms_ssim"] is not None])
@@ -81,15 +86,18 @@ def summarise(records):
                     "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
         if any("lpips" in a for a in anchors):
             out["anchor_lpips"] = mean([a["lpips"] for a in anchors if a.get("lpips") is not None])
+        if any("dists" in a for a in anchors):
+            out["anchor_dists"] = mean([a["dists"] for a in anchors if a.get("dists") is not None])
     return out
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None):
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
     on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back.
-    lpips_model (lpips.LpipsVGG): every record also carries "lpips" of the decoded anchor against the original."""
+    lpips_model (lpips.LpipsVGG), dists_model (dists.DistsVGG): every record also carries "lpips" / "dists" of the decoded anchor
+    against the original."""
     from . import jpeg, jpeg_enc, quality
     B, H, W, _ = a_u8.shape
     if fixed_quality is None:
@@ -101,6 +109,7 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
     decoded = jpeg.JpegBatch(files).decode(a_u8.device)
     m = quality.measure(a_u8, decoded)
     lp = lpips_model.measure(a_u8, decoded) if lpips_model is not None else None
+    ds = dists_model.measure(a_u8, decoded) if dists_model is not None else None
     out = []
     for j, ((q, over), data) in enumerate(zip(picks, files)):
         if over is None:      # a fixed quality: over the rate if the container is known and smaller
@@ -110,6 +119,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
             rec[k] = None if m[k] is None else _json_number(m[k][j])
         if lpips_model is not None:
             rec["lpips"] = None if lp is None else float(lp[0][j])
+        if dists_model is not None:
+            rec["dists"] = None if ds is None else float(ds[0][j])
         rec["over_rate"] = bool(over)
         out.append(rec)
     return out
@@ -132,6 +143,8 @@ def main(argv=None):
     ap.add_argument("--anchor_quality", type=int, default=None, help="fix the anchor's quality instead of searching (implies --anchor jpeg)")
     ap.add_argument("--lpips_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) with the VGG16 trunk and the lin layers of LPIPS: adds \"lpips\" to every record")
+    ap.add_argument("--dists_ckpt", type=str, nargs="+", default=None,
+                    help="state dict file(s) with the VGG16 trunk and alpha, beta of DISTS: adds \"dists\" to every record")
     args = ap.parse_args(argv)
     if not args.bitstreams and not args.recon_dir:
         ap.error("give --bitstreams, --recon_dir or both")
@@ -152,6 +165,10 @@ def main(argv=None):
     if args.lpips_ckpt:
         from .lpips import LpipsVGG
         lpips_model = LpipsVGG(args.lpips_ckpt, dev)
+    dists_model = None
+    if args.dists_ckpt:
+        from .dists import DistsVGG
+        dists_model = DistsVGG(args.dists_ckpt, dev)
     originals = by_stem(glob(os.path.join(args.originals, "*.*")))
     containers = by_stem(glob(os.path.join(args.bitstreams, "*.c2df"))) if args.bitstreams else {}
     recons = by_stem(glob(os.path.join(args.recon_dir, "*.*"))) if args.recon_dir else None
@@ -184,8 +201,9 @@ def main(argv=None):
             b = torch.stack([m[2] for m in members])
             m = quality.measure(a, b)
             lp = lpips_model.measure(a, b) if lpips_model is not None else None
+            ds = dists_model.measure(a, b) if dists_model is not None else None
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
-            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model) if anchor else None
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model) if anchor else None
             for j, (stem, _, _) in enumerate(members):
                 nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
@@ -193,6 +211,8 @@ def main(argv=None):
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
                 if lpips_model is not None:
                     rec["lpips"] = None if lp is None else float(lp[0][j])
+                if dists_model is not None:
+                    rec["dists"] = None if ds is None else float(ds[0][j])
                 if anchors:
                     rec["anchor"] = anchors[j]
                 records.append(rec)

@@ -1266,6 +1266,75 @@ def lpips_head(feat, w, B, H, W, out=None):
     return out
 
 
+def dists_input(img_u8, hp, image_offset=0):
+    """the DISTS input layer (csrc/dists.hip): img_u8 (B, H, W, 3) u8 -> (u / 255 - mean) / std in the interior of images image_offset
+    .. image_offset+B-1 of hp, a HaloPlanes of (total images, H, W, 32) from halo_planes_buffer; channels 3..31 are zero.  No
+    synchronisation."""
+    require_gpu()
+    assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3
+    B, H, W, _ = img_u8.shape
+    assert (hp.H, hp.W, hp.C) == (H, W, 32) and 0 <= image_offset and image_offset + B <= hp.B, ((hp.B, hp.H, hp.W, hp.C), img_u8.shape)
+    call("sgic_dists_input_split3", _p(img_u8), B, H, W, hp.B, int(image_offset), _p(hp.t))
+    return hp
+
+
+def dists_moments_u8(a, b, out=None):
+    """tap 0 of DISTS (csrc/dists.hip): a, b (B, H, W, 3) u8, contiguous on one device -> (B, 3, 5) int64: the exact sums of a, b, a^2,
+    b^2 and a b over the pixels of every pair and channel.  No synchronisation."""
+    require_gpu()
+    for t in (a, b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a.device
+    assert a.dim() == 4 and a.shape[3] == 3 and a.shape == b.shape
+    B, H, W, _ = a.shape
+    if out is None:
+        out = torch.empty(B, 3, 5, dtype=torch.int64, device=a.device)
+    assert out.shape == (B, 3, 5) and out.dtype == torch.int64 and out.is_contiguous()
+    call("sgic_dists_moments_u8", _p(a), _p(b), B, H, W, _p(out))
+    return out
+
+
+def relu_l2pool_halo(x, B, H, W, C):
+    """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU, then DISTS's L2 pool sqrt(hanning3x3(f^2) + 1e-12) at stride
+    2 with zero padding 1 (an odd last row or column is kept: ceil(n / 2)) -> the next 3x3 convolution's zero-halo operand planes
+    (HaloPlanes; csrc/dists.hip).  C % 32 == 0."""
+    require_gpu()
+    x, ldx = _rows(x)
+    assert ldx == C and x.shape == (B * H * W, C), (x.shape, (B, H, W, C))
+    hp = halo_planes_buffer(x.device, B, (H + 1) // 2, (W + 1) // 2, C)
+    call("sgic_relu_l2pool_halo_split3", _p(x), B, H, W, C, _p(hp.t))
+    return hp
+
+
+def dists_moments(feat, B, H, W):
+    """one DISTS tap (csrc/dists.hip): feat (2*B*H*W, C) fp32 before its ReLU, the first B images against the last B -> (B, 5, C)
+    float64: the sums of x, y, x^2, y^2 and x y over the pixels, x and y the ReLU'd sides.  No synchronisation."""
+    require_gpu()
+    feat, ldf = _rows(feat)
+    C = feat.shape[1]
+    assert ldf == C and feat.shape[0] == 2 * B * H * W and feat.dtype == torch.float32
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_dists_moments_work_bytes", B, H, W, C, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=feat.device)
+    sums = torch.empty(B, 5, C, dtype=torch.float64, device=feat.device)
+    call("sgic_dists_moments", _p(feat), B, H, W, C, _p(work), ctypes.c_size_t(nbytes.value), _p(sums))
+    return sums
+
+
+def dists_head(sums, alpha, beta, H, W, out=None):
+    """sums (B, 5, C) float64 of dists_moments over H*W pixels, alpha, beta (C,) fp32 -> (B, 2) float64: the tap's structure term
+    sum_c alpha_c (1 - S1_c) and texture term sum_c beta_c (1 - S2_c), not yet divided by sum alpha + sum beta.  No synchronisation."""
+    require_gpu()
+    B, five, C = sums.shape
+    assert five == 5 and sums.dtype == torch.float64 and sums.is_contiguous()
+    for t in (alpha, beta):
+        assert t.shape == (C,) and t.is_contiguous() and t.dtype == torch.float32 and t.device == sums.device
+    if out is None:
+        out = torch.empty(B, 2, dtype=torch.float64, device=sums.device)
+    assert out.shape == (B, 2) and out.dtype == torch.float64 and out.is_contiguous()
+    call("sgic_dists_head", _p(sums), _p(alpha), _p(beta), B, H, W, C, _p(out))
+    return out
+
+
 def jpeg_encode(rgb_u8, tables, subsampling):
     """baseline JPEG encode of B equal-size images (csrc/jpeg_enc.hip): rgb_u8 (B, H, W, 3) u8, contiguous on the device; tables
     (B, 2, 64) u16 numpy array on the host (luma and chroma quantisation table of every image, natural order); subsampling 0 / 1 / 2
