@@ -488,6 +488,30 @@ int sgic_dists_moments(const float *d_feat, int B, int H, int W, int C, uint8_t 
 int sgic_dists_head(const double *d_sums, const float *d_alpha, const float *d_beta, int B, int H, int W, int C, double *d_terms,
                     sgic_stream_t stream);
 
+/* LPIPS with the AlexNet trunk (lpips_alex.LpipsAlex, evaluate.py --lpips_alex_ckpt; lpips.LPIPS(net="alex")):
+ * the producers of the operands that the 3x3 path cannot take.  All planes are slice-major bf16x3 (a_packed = 1).
+ *
+ * sgic_lpips_alex_conv1_patches_split3: d_img (B, H, W, 3) u8 -> rows image_offset h1 w1 .. of the A operand [3][12][total_images h1
+ * w1][32] of the 11x11 / stride 4 / pad 2 convolution as a GEMM, h1 = (H - 7) / 4 + 1, w1 = (W - 7) / 4 + 1.  Row (img, oy, ox),
+ * column k = (ky 11 + kx) 3 + c, k < 363: the input layer of sgic_lpips_input_split3 at pixel (4 oy - 2 + ky, 4 ox - 2 + kx), 0 when
+ * that pixel is outside the image; columns 363..383 are 0.  Two calls fill one buffer with both sides of the pairs; the rows of
+ * other images are not touched.
+ *
+ * sgic_relu_maxpool3_patches5_split3: d_in (B H W, C) fp32 BEFORE relu -> relu -> max over 3 x 3, stride 2, no padding, floor, to PH
+ * x PW (PH = (H - 3) / 2 + 1) -> the A operand [3][25 C / 32][B PH PW][32] of the 5x5 / pad 2 convolution as a GEMM: column k = (ky 5
+ * + kx) C + c of row (b, oy, ox) is the pooled value at (oy + ky - 2, ox + kx - 2), 0 outside the pooled map.  Every element is
+ * written.
+ *
+ * sgic_relu_maxpool3_halo_split3: the same relu and pool -> the interior of the zero-halo planes [3][C / 32][B (PH+2) (PW+2)][32], the
+ * input of sgic_conv3x3_split3_f32; only the interior is written (the sgic_halo_copy_split3 contract).
+ *
+ * SGIC_EINVAL before any launch: a null pointer, B < 1, H or W < 7 (the pools: < 3), C % 32 != 0, a buffer that is not 16-byte
+ * aligned (the u8 image may sit anywhere), image slots outside total_images, 2^31 or more rows. */
+int sgic_lpips_alex_conv1_patches_split3(const uint8_t *d_img, int B, int H, int W, int total_images, int image_offset,
+                                         uint16_t *d_planes, sgic_stream_t stream);
+int sgic_relu_maxpool3_patches5_split3(const float *d_in, int B, int H, int W, int C, uint16_t *d_planes, sgic_stream_t stream);
+int sgic_relu_maxpool3_halo_split3(const float *d_in, int B, int H, int W, int C, uint16_t *d_halo_planes, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

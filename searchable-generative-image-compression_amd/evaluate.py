@@ -15,6 +15,10 @@
                                                                 with the VGG16 trunk (lpips.LpipsVGG) on the same u8 tensors; P: one
                                                                 or more state dict files that together hold the trunk and the lin
                                                                 layers (lpips.load_weights)
+  evaluate.py ... --lpips_alex_ckpt P [P ...]                   adds "lpips_alex" in the same places (directly after "lpips" where
+                                                                both are asked for): LPIPS with the AlexNet trunk, the `lpips` of the
+                                                                reference's Quality_Model (lpips_alex.LpipsAlex); P: state dict
+                                                                file(s) with the trunk and the lin layers (lpips_alex.load_weights)
   evaluate.py ... --dists_ckpt P [P ...]                        adds "dists" in the same places (after "lpips" where both are asked
                                                                 for): DISTS with the VGG16 trunk (dists.DistsVGG); P: state dict
                                                                 file(s) with the trunk, alpha and beta (dists.load_weights)
@@ -64,7 +68,7 @@ def _json_number(v):
 
 def summarise(records):
     """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
-    lpips and of dists when the records carry them"""
+    lpips, lpips_alex and dists when the records carry them"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
@@ -74,6 +78,8 @@ def summarise(records):
            "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
     if any("lpips" in r for r in records):
         out["lpips"] = mean([r["lpips"] for r in records if r.get("lpips") is not None])
+    if any("lpips_alex" in r for r in records):
+        out["lpips_alex"] = mean([r["lpips_alex"] for r in records if r.get("lpips_alex") is not None])
     if any("dists" in r for r in records):
         out["dists"] = mean([r["dists"] for r in records if r.get("dists") is not None])
     anchors = [r["anchor"] for r in records if "anchor" in r]
@@ -86,18 +92,20 @@ def summarise(records):
                     "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
         if any("lpips" in a for a in anchors):
             out["anchor_lpips"] = mean([a["lpips"] for a in anchors if a.get("lpips") is not None])
+        if any("lpips_alex" in a for a in anchors):
+            out["anchor_lpips_alex"] = mean([a["lpips_alex"] for a in anchors if a.get("lpips_alex") is not None])
         if any("dists" in a for a in anchors):
             out["anchor_dists"] = mean([a["dists"] for a in anchors if a.get("dists") is not None])
     return out
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None):
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None, lpips_alex_model=None):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
     on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back.
-    lpips_model (lpips.LpipsVGG), dists_model (dists.DistsVGG): every record also carries "lpips" / "dists" of the decoded anchor
-    against the original."""
+    lpips_model (lpips.LpipsVGG), dists_model (dists.DistsVGG), lpips_alex_model (lpips_alex.LpipsAlex): every record also carries
+    "lpips" / "dists" / "lpips_alex" of the decoded anchor against the original."""
     from . import jpeg, jpeg_enc, quality
     B, H, W, _ = a_u8.shape
     if fixed_quality is None:
@@ -109,6 +117,7 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
     decoded = jpeg.JpegBatch(files).decode(a_u8.device)
     m = quality.measure(a_u8, decoded)
     lp = lpips_model.measure(a_u8, decoded) if lpips_model is not None else None
+    la = lpips_alex_model.measure(a_u8, decoded) if lpips_alex_model is not None else None
     ds = dists_model.measure(a_u8, decoded) if dists_model is not None else None
     out = []
     for j, ((q, over), data) in enumerate(zip(picks, files)):
@@ -119,6 +128,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
             rec[k] = None if m[k] is None else _json_number(m[k][j])
         if lpips_model is not None:
             rec["lpips"] = None if lp is None else float(lp[0][j])
+        if lpips_alex_model is not None:
+            rec["lpips_alex"] = None if la is None else float(la[0][j])
         if dists_model is not None:
             rec["dists"] = None if ds is None else float(ds[0][j])
         rec["over_rate"] = bool(over)
@@ -143,6 +154,8 @@ def main(argv=None):
     ap.add_argument("--anchor_quality", type=int, default=None, help="fix the anchor's quality instead of searching (implies --anchor jpeg)")
     ap.add_argument("--lpips_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) with the VGG16 trunk and the lin layers of LPIPS: adds \"lpips\" to every record")
+    ap.add_argument("--lpips_alex_ckpt", type=str, nargs="+", default=None,
+                    help="state dict file(s) with the AlexNet trunk and the lin layers of LPIPS: adds \"lpips_alex\" to every record")
     ap.add_argument("--dists_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) with the VGG16 trunk and alpha, beta of DISTS: adds \"dists\" to every record")
     args = ap.parse_args(argv)
@@ -165,6 +178,10 @@ def main(argv=None):
     if args.lpips_ckpt:
         from .lpips import LpipsVGG
         lpips_model = LpipsVGG(args.lpips_ckpt, dev)
+    lpips_alex_model = None
+    if args.lpips_alex_ckpt:
+        from .lpips_alex import LpipsAlex
+        lpips_alex_model = LpipsAlex(args.lpips_alex_ckpt, dev)
     dists_model = None
     if args.dists_ckpt:
         from .dists import DistsVGG
@@ -201,9 +218,11 @@ def main(argv=None):
             b = torch.stack([m[2] for m in members])
             m = quality.measure(a, b)
             lp = lpips_model.measure(a, b) if lpips_model is not None else None
+            la = lpips_alex_model.measure(a, b) if lpips_alex_model is not None else None
             ds = dists_model.measure(a, b) if dists_model is not None else None
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
-            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model) if anchor else None
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model,
+                                   lpips_alex_model) if anchor else None
             for j, (stem, _, _) in enumerate(members):
                 nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
@@ -211,6 +230,8 @@ def main(argv=None):
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
                 if lpips_model is not None:
                     rec["lpips"] = None if lp is None else float(lp[0][j])
+                if lpips_alex_model is not None:
+                    rec["lpips_alex"] = None if la is None else float(la[0][j])
                 if dists_model is not None:
                     rec["dists"] = None if ds is None else float(ds[0][j])
                 if anchors:

@@ -1335,6 +1335,46 @@ def dists_head(sums, alpha, beta, H, W, out=None):
     return out
 
 
+def lpips_alex_conv1_patches(img_u8, planes, image_offset=0):
+    """the operand of AlexNet's first convolution (11x11, stride 4, pad 2) as a GEMM (csrc/lpips_alex.hip): img_u8 (B, H, W, 3) u8 ->
+    rows image_offset*h1*w1 .. of `planes`, a Planes(total_images*h1*w1, 384) with h1 = (H - 7) // 4 + 1, w1 = (W - 7) // 4 + 1: column
+    (ky*11 + kx)*3 + c of row (img, oy, ox) is the LPIPS input layer at pixel (4*oy - 2 + ky, 4*ox - 2 + kx), zero outside the image;
+    columns 363..383 are zero.  The rows of other images are not touched.  No synchronisation."""
+    require_gpu()
+    assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3
+    B, H, W, _ = img_u8.shape
+    assert H >= 7 and W >= 7, img_u8.shape
+    per = ((H - 7) // 4 + 1) * ((W - 7) // 4 + 1)
+    assert isinstance(planes, Planes) and planes.cols == 384 and planes.rows % per == 0, (planes.shape, img_u8.shape)
+    total = planes.rows // per
+    assert 0 <= image_offset and image_offset + B <= total, (image_offset, B, total)
+    call("sgic_lpips_alex_conv1_patches_split3", _p(img_u8), B, H, W, total, int(image_offset), _p(planes.t))
+    return planes
+
+
+def relu_maxpool3_patches5(x, B, H, W, C):
+    """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU -> max-pool 3x3, stride 2, no padding (floor) to PH x PW ->
+    the 5x5, pad-2, stride-1 patches of the pooled map as a Planes(B*PH*PW, 25*C): column (ky*5 + kx)*C + c, zero where the tap is
+    outside the pooled map (csrc/lpips_alex.hip).  C % 32 == 0."""
+    require_gpu()
+    x, ldx = _rows(x)
+    assert ldx == C and x.shape == (B * H * W, C) and H >= 3 and W >= 3, (x.shape, (B, H, W, C))
+    pl = Planes(B * ((H - 3) // 2 + 1) * ((W - 3) // 2 + 1), 25 * C, x.device)
+    call("sgic_relu_maxpool3_patches5_split3", _p(x), B, H, W, C, _p(pl.t))
+    return pl
+
+
+def relu_maxpool3_halo(x, B, H, W, C):
+    """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU -> max-pool 3x3, stride 2, no padding (floor) -> the next 3x3
+    convolution's zero-halo operand planes (HaloPlanes from halo_planes_buffer; csrc/lpips_alex.hip).  C % 32 == 0."""
+    require_gpu()
+    x, ldx = _rows(x)
+    assert ldx == C and x.shape == (B * H * W, C) and H >= 3 and W >= 3, (x.shape, (B, H, W, C))
+    hp = halo_planes_buffer(x.device, B, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C)
+    call("sgic_relu_maxpool3_halo_split3", _p(x), B, H, W, C, _p(hp.t))
+    return hp
+
+
 def jpeg_encode(rgb_u8, tables, subsampling):
     """baseline JPEG encode of B equal-size images (csrc/jpeg_enc.hip): rgb_u8 (B, H, W, 3) u8, contiguous on the device; tables
     (B, 2, 64) u16 numpy array on the host (luma and chroma quantisation table of every image, natural order); subsampling 0 / 1 / 2
