@@ -244,7 +244,9 @@ int sgic_l2norm_u8(const float *d_x, int ldx, int M, int D, float *d_unit, uint8
  *   whole rounds walked persistently, 14 / 15 = 256x128 tiles (plain / persistent), 16 / 17 = 2 / 11 with LDS-DMA staging,
  *   18-25 = the ring kernel's small tiles (32x32 ... 80x64: single-image sized launches), 26 / 27 = 8 / 12 with the ring kernel's
  *   80x64 tiles for the remaining rows, 28 / 29 = 128x192 tiles (plain / persistent; N = 768: 8192 rows = one whole round), 30 = 256x256 tiles
- *   (W single-buffered in LDS), 31 = 30 for the rows that fill whole rounds + 1 for the rest.
+ *   (W single-buffered in LDS), 31 = 30 for the rows that fill whole rounds + 1 for the rest, 32 = 160x256 tiles (M = 9 248 x
+ *   N = 1024: 232 tiles, one round).  26 takes ONE launch of 32 instead when the product is not a convolution, 128x256 tiles need
+ *   more than one round of the 256 CUs and 160x256 tiles fit in one; 27 never does.
  *   The 128x256 and 256x128 tiles (1, 10, 14, 15 and the whole-round part of 6, 8, 12) stage their operands by LDS-DMA
  *   (global_load_lds: no register pass, no ds_write), the other tiles through registers; all modes are bitwise identical. */
 int sgic_split3_f32(const float *d_x, int ld, int rows, int cols, int seg, int seg_stride, uint16_t *d_planes,
@@ -256,6 +258,10 @@ int sgic_gemm_split3_f32(const float *d_A, int lda, int a_seg, int a_seg_stride,
                          const uint16_t *d_Wplanes, const float *d_bias, const float *d_R, int ldr, float *d_C, int ldc,
                          uint16_t *d_Cplanes, int M, int N, int K, int act, int c_seg, int c_seg_stride,
                          const sgic_launch_opts *opts, sgic_stream_t stream);
+/* What tile_mode does with an M x N product (conv != 0: as sgic_conv3x3_split3_f32 with M = B H W, N = Cout) -- the very function the
+ * dispatcher runs; host only, no GPU call.  *tile_m x *tile_n: the nominal workgroup tile of the first launch; *split_row: the row
+ * at which a second launch starts (0: there is one launch); *tail_mode: the single-launch mode of that second launch (0: none). */
+int sgic_gemm_split3_plan(int M, int N, int conv, int tile_mode, int *tile_m, int *tile_n, int *split_row, int *tail_mode);
 /* sgic_conv3x3_f32 as an implicit split GEMM: d_in_planes = bf16x3 planes of the zero-halo NHWC input, [3][B (H+2) (W+2)][Cin]
  * (sgic_split3_f32 over the halo buffer's rows; opts->a_packed = 0) or slice-major [3][Cin / 32][B (H+2) (W+2)][32]
  * (sgic_split3_pack_f32, sgic_groupnorm_nhwc_split3, sgic_halo_copy_split3; a_packed = 1); d_Wplanes = planes [3][Cout][9 Cin]

@@ -593,9 +593,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 1)
 void gemm_split3_dma_kernel(S3Args g) {
   constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW, TM = 16 * BM * WAVES_M, TN = 16 * BN * WAVES_N;
   constexpr int ROWB = 64;
-  // 1 KiB pieces per plane: of the tile / of one wave.  When NW does not divide a count (the 128x192 tile: 12 W pieces, 8 waves) the last
-  // requests wrap around to pieces 0 .. -- the same bytes to the same LDS address twice, harmless -- so every wave issues the same count
-  constexpr int PA = TM / 16, PW = TN / 16, CA = (PA + NW - 1) / NW, CW = (PW + NW - 1) / NW;
+  // 1 KiB pieces per plane (PA, PW) and requests per wave and plane (CA, CW): wave w moves pieces w, w + NW, ... of each plane.
+  // FLATA / FLATW -- NW does not divide the operand's count (the 128x192 tile: 12 W pieces, the 160x256 tile: 10 A pieces, 8 waves):
+  // that operand's pieces of a slice are dealt as ONE list over (plane, piece), wave w taking flat pieces w, w + NW, ... (CA / CW then
+  // count per SLICE); only the last requests of the list wrap around to pieces 0 .. -- the same bytes to the same LDS address twice,
+  // harmless -- so every wave issues the same count: 128x192: 3 + 5 per wave, 64 requests for 60 pieces where a wrap per plane made 72;
+  // 160x256: 4 + 6, 80 for 78.  The plane of a flat request goes into its per-lane offset, which s3_mode checks to fit.
+  constexpr int PA = TM / 16, PW = TN / 16;
+  constexpr bool FLATA = PA % NW != 0, FLATW = PW % NW != 0;
+  constexpr int CA = FLATA ? (3 * PA + NW - 1) / NW : PA / NW, CW = FLATW ? (3 * PW + NW - 1) / NW : PW / NW;
   constexpr int APLANE = TM * ROWB, WPLANE = TN * ROWB, STAGE = 3 * (APLANE + WPLANE);
   // WS1 (the 256x256 tile: two whole stages would be 192 KB): A double-buffered, W SINGLE-buffered -- a wave holds its W fragments of a
   // slice in registers for the whole slice, so once every wave has read them (a second barrier, behind row 0's first MFMAs) the W region
@@ -604,8 +610,12 @@ void gemm_split3_dma_kernel(S3Args g) {
   constexpr int LDS_TOTAL = WS1 ? 6 * APLANE + 3 * WPLANE : 2 * STAGE;
   static_assert(!(WS1 && PERSIST), "the single W buffer has no room for the next tile's first slice during the epilogue");
   constexpr int HB = BN / 2;
-  static_assert(BN >= 2 && (BM % 2) == 0, "rotating fragment schedule");
-  static_assert(NW * (16 * BM / 2) * (16 * BN + 4) * 4 <= (WS1 ? LDS_TOTAL : STAGE), "the two-pass epilogue must fit one staging buffer (WS1: the whole LDS)");
+  // Odd BM: row i of slice kt holds its A fragment in register set (i + kt) & 1 instead of i & 1, so that row 0 of the next slice still
+  // lands in the set the last row is not using; the slice takes its parity as a compile-time argument and the K loop walks two slices
+  // at a time.  The epilogue then goes through LDS one block row at a time (BM passes) instead of in two halves.
+  constexpr int EPASS = BM % 2 == 0 ? 2 : BM;
+  static_assert(BN >= 2 && BM >= 2, "rotating fragment schedule");
+  static_assert(NW * (16 * BM / EPASS) * (16 * BN + 4) * 4 <= (WS1 ? LDS_TOTAL : STAGE), "one epilogue pass must fit one staging buffer (WS1: the whole LDS)");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef S3_STAMPS
   const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime(), st_c0 = __builtin_amdgcn_s_memtime();
@@ -634,6 +644,7 @@ void gemm_split3_dma_kernel(S3Args g) {
   const int prow = lane >> 2, pslot = (lane & 3) ^ swz(prow);
   unsigned voffA[CA], voffW[CW];          // byte offsets from the tile's uniform bases
   const unsigned short *baseA, *baseW;    // uniform: plane 0, K offset 0, tile row 0
+  unsigned dstA[FLATA ? CA : 1], dstW[FLATW ? CW : 1];   // flat dealing: uniform LDS offset of a request's piece inside a stage (plane included)
   auto conv_off = [&](int am) __attribute__((always_inline)) {   // element offset of logical row am's top-left halo pixel
     const int hw = g.conv_H * g.conv_W, b = am / hw, r = am - b * hw, y = r / g.conv_W, x = r - y * g.conv_W;
     return (((size_t)b * (g.conv_H + 2) + y) * (g.conv_W + 2) + x) * (g.a_packed ? 32 : g.conv_C);
@@ -656,9 +667,29 @@ void gemm_split3_dma_kernel(S3Args g) {
       voffW[i] = (unsigned)(((size_t)(wr - n0) * (g.w_packed ? 32 : g.K)) * 2 + pslot * 16);
       if (S3_ABLATE & 64) voffW[i] = (unsigned)(((wave + NW * i) % PW) * 1024 + lane * 16);
     }
+    // flat dealing: request i = flat piece (wave + NW i) % (3 pieces per plane) -> (plane, piece); replaces the operand's map above
+    if constexpr (FLATA) {
+#pragma unroll
+      for (int i = 0; i < CA; i++) {
+        const int f = (wave + NW * i) % (3 * PA), p = f / PA, r = f - p * PA;
+        const int am = min(m0 + r * 16 + prow, g.M - 1);
+        const size_t off = g.conv_C ? conv_off(am) : (size_t)am * astride;
+        voffA[i] = (unsigned)((off - a0) * 2 + pslot * 16) + (unsigned)p * (unsigned)(g.a_plane * 2);
+        dstA[i] = (unsigned)(p * APLANE + r * 1024);
+      }
+    }
+    if constexpr (FLATW) {
+#pragma unroll
+      for (int i = 0; i < CW; i++) {
+        const int f = (wave + NW * i) % (3 * PW), p = f / PW, r = f - p * PW;
+        const int wr = min(n0 + r * 16 + prow, g.N - 1);
+        voffW[i] = (unsigned)(((size_t)(wr - n0) * (g.w_packed ? 32 : g.K)) * 2 + pslot * 16) + (unsigned)p * (unsigned)(g.w_plane * 2);
+        dstW[i] = (unsigned)(p * WPLANE + r * 1024);
+      }
+    }
   };
   setup();
-  // request K slice k0 of the current tile into LDS stage `buf`: 3 (CA + CW) instructions per wave
+  // request K slice k0 of the current tile into LDS stage `buf`: 3 (CA + CW) instructions per wave (a flat-dealt operand: CA / CW)
   auto dma = [&](int k0, int buf) __attribute__((always_inline)) {
     if ((S3_ABLATE & 1) && k0 > 0) return;
     size_t ka = g.a_packed ? (size_t)k0 * g.a_rows : (size_t)k0;
@@ -667,16 +698,27 @@ void gemm_split3_dma_kernel(S3Args g) {
       ka = g.a_packed ? ((size_t)(c0 >> 5) * g.a_rows + ky * (g.conv_W + 2) + kx) * 32 : (size_t)((ky * (g.conv_W + 2) + kx) * g.conv_C + c0);
     }
     unsigned char *stageA = smem + buf * ASTAGE, *stageW = smem + WOFF + buf * WSTAGE;
+    // a flat-dealt operand: CA / CW instructions per wave and slice (the ablations of bits 6-8 exist for the evenly dealt operands only)
+    if constexpr (FLATA) {
+      const char *pa = reinterpret_cast<const char *>(baseA + ka);
+#pragma unroll
+      for (int i = 0; i < CA; i++) __builtin_amdgcn_global_load_lds((s3_glb_void *)(pa + voffA[i]), (s3_lds_void *)(stageA + dstA[i]), 16, 0, 0);
+    }
+    if constexpr (FLATW) {
+      const char *pw = reinterpret_cast<const char *>(baseW + (g.w_packed ? (size_t)k0 * g.N : (size_t)k0));
+#pragma unroll
+      for (int i = 0; i < CW; i++) __builtin_amdgcn_global_load_lds((s3_glb_void *)(pw + voffW[i]), (s3_lds_void *)(stageW + dstW[i]), 16, 0, 0);
+    }
 #pragma unroll
     for (int p = 0; p < 3; p++) {
       if ((S3_ABLATE & 256) && p == 2 && k0 > 0) continue;   // diagnostic: bit 8 = a third fewer operand bytes per slice (what a 256x256 tile would move per flop)
       const char *pa = reinterpret_cast<const char *>(baseA + p * g.a_plane + (((S3_ABLATE & 192) == 64) ? (size_t)(k0 / 32) * (TM * 32) : ka));
       const char *pw = reinterpret_cast<const char *>(baseW + p * g.w_plane + ((S3_ABLATE & 64) ? (size_t)(k0 / 32) * (TN * 32) : (g.w_packed ? (size_t)k0 * g.N : (size_t)k0)));
 #pragma unroll
-      for (int i = 0; i < CA; i++)
+      for (int i = 0; i < (FLATA ? 0 : CA); i++)
         __builtin_amdgcn_global_load_lds((s3_glb_void *)(pa + voffA[i]), (s3_lds_void *)(stageA + p * APLANE + ((wave + NW * i) % PA) * 1024), 16, 0, 0);
 #pragma unroll
-      for (int i = 0; i < CW; i++)
+      for (int i = 0; i < (FLATW ? 0 : CW); i++)
         __builtin_amdgcn_global_load_lds((s3_glb_void *)(pw + voffW[i]), (s3_lds_void *)(stageW + p * WPLANE + ((wave + NW * i) % PW) * 1024), 16, 0, 0);
     }
   };
@@ -725,14 +767,16 @@ void gemm_split3_dma_kernel(S3Args g) {
   // one K slice: [request slice kt + 1 into the other stage] MFMAs in the rotating order of the kernel above; the ONE barrier sits
   // 6 BN / 2 MFMAs before the slice's end, behind this wave's vmcnt(0) (its pieces of slice kt + 1 are in LDS) and lgkmcnt(0) (its
   // reads of the current stage are done), and the MFMAs left cover the first fragment reads of the next stage
-  auto slice = [&](int kt, bool more) __attribute__((always_inline)) {
+  // PAR (odd BM only): the parity of kt, which A register set row 0 of this slice was read into
+  auto slice = [&](int kt, bool more, auto par_c) __attribute__((always_inline)) {
+    constexpr int PAR = (BM & 1) ? decltype(par_c)::value : 0;
     const int cur = kt & 1, nxt = cur ^ 1;
     if (!WS1 && more) dma((kt + 1) * 32, nxt);
 #pragma unroll
     for (int j = 0; j < BN - HB; j++) read_w(cur, j);       // Wlo: needed after the Whi blocks of row 0
 #pragma unroll
     for (int i = 0; i < BM; i++) {
-      const int set = i & 1;
+      const int set = (i + PAR) & 1;
       if (i + 1 < BM) read_a(cur, i + 1, set ^ 1);
 #pragma unroll
       for (int j = BN - HB; j < BN; j++) block(i, j, set);
@@ -744,7 +788,7 @@ void gemm_split3_dma_kernel(S3Args g) {
         if (more) dma((kt + 1) * 32, nxt);
       }
       if (i == BM - 1) {
-        constexpr int NMF1 = 6 * (BM * BN - (BN - HB)), NDMA = 3 * (CA + CW), NDR1 = 3 * (BN - HB) + 3 * (BM - 1);
+        constexpr int NMF1 = 6 * (BM * BN - (BN - HB)), NDMA = (FLATA ? CA : 3 * CA) + (FLATW ? CW : 3 * CW), NDR1 = 3 * (BN - HB) + 3 * (BM - 1);
         if constexpr (!(S3_DMA_VARIANT & 1)) {
 #pragma unroll
           for (int q = 0; q < NMF1; q++) {
@@ -758,7 +802,7 @@ void gemm_split3_dma_kernel(S3Args g) {
         if (more) {
 #pragma unroll
           for (int j = BN - HB; j < BN; j++) read_w(nxt, j);
-          read_a(nxt, 0, 0);
+          read_a(nxt, 0, (BM & 1) ? PAR ^ 1 : 0);   // the set row BM-1 is not using
         }
       }
 #pragma unroll
@@ -776,8 +820,22 @@ void gemm_split3_dma_kernel(S3Args g) {
 #ifdef S3_STAMPS
     const unsigned long long ph1 = __builtin_amdgcn_s_memtime();
 #endif
-    for (int kt = 0; kt + 1 < nk; ++kt) slice(kt, true);
-    slice(nk - 1, false);
+    if constexpr (BM % 2 == 0) {
+      for (int kt = 0; kt + 1 < nk; ++kt) slice(kt, true, IntC<0>{});
+      slice(nk - 1, false, IntC<0>{});
+    } else {   // two slices per trip: the register-set parity is a compile-time constant; 1 (nk odd) or 2 slices are left for the tail
+      int kt = 0;
+      for (; kt + 2 < nk; kt += 2) {
+        slice(kt, true, IntC<0>{});
+        slice(kt + 1, true, IntC<1>{});
+      }
+      if (kt + 1 < nk) {
+        slice(kt, true, IntC<0>{});
+        slice(kt + 1, false, IntC<1>{});
+      } else {
+        slice(kt, false, IntC<0>{});
+      }
+    }
 #ifdef S3_STAMPS
     const unsigned long long ph2 = __builtin_amdgcn_s_memtime();
 #endif
@@ -793,7 +851,7 @@ void gemm_split3_dma_kernel(S3Args g) {
       }
     }
     // the epilogue's LDS slice lives in the stage-1 region (stage 0 may be receiving the next tile)
-    s3_tile_epilogue<BM, BN, 2>(g, acc, reinterpret_cast<float *>(smem + (WS1 ? 0 : STAGE)) + wave * ((16 * BM / 2) * (16 * BN + 4)), em0, en0, wm, wn, lane);
+    s3_tile_epilogue<BM, BN, EPASS>(g, acc, reinterpret_cast<float *>(smem + (WS1 ? 0 : STAGE)) + wave * ((16 * BM / EPASS) * (16 * BN + 4)), em0, en0, wm, wn, lane);
 #ifdef S3_STAMPS
     {
       const unsigned long long ph3 = __builtin_amdgcn_s_memtime();
@@ -979,7 +1037,7 @@ extern "C" int sgic_split3_pack_f32(const float *d_x, int ld, int rows, int cols
   return sgic::check_launch("split3_rows_kernel<pack>");
 }
 
-#define SGIC_SPLIT3_TILE_MODES 31
+#define SGIC_SPLIT3_TILE_MODES 32
 
 template <int WAVES_M, int WAVES_N, int BM, int BN, int NS, int KS = 1, bool PERSIST = false>
 static int s3_launch(const S3Args &g, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
@@ -1058,6 +1116,9 @@ static int s3_mode(const S3Args &g, int mode, hipStream_t st, hipEvent_t e0, hip
   // a DMA piece is addressed by per-lane 32-bit byte offsets from the tile's base: true for every tile below unless rows are absurdly long
   const bool dma_ok = (size_t)(g.a_packed ? 32 : g.K) * 2 * 256 < (1ull << 31) && (size_t)(g.w_packed ? 32 : g.K) * 2 * 256 < (1ull << 31) &&
                       (!g.conv_C || (size_t)(g.conv_W + 2) * (g.a_packed ? 32 : g.conv_C) * 2 * 1024 < (1ull << 31));
+  // an operand whose pieces are dealt over the planes (W of the 128x192 tile, A of the 160x256 tile) carries the plane in that offset as
+  // well: two planes' worth of bytes
+  const bool flatw_ok = dma_ok && g.w_plane < (1l << 29), flata_ok = dma_ok && g.a_plane < (1l << 29);
   switch (mode) {
     case 1: return dma_ok ? s3_launch_dma<2, 4, 4, 4>(g, st, e0, e1) : s3_launch<2, 4, 2, 2, 1>(g, st, e0, e1);
     case 10: return dma_ok ? s3_launch_dma<2, 4, 4, 4, true>(g, st, e0, e1) : s3_launch<2, 4, 2, 2, 1>(g, st, e0, e1);
@@ -1066,10 +1127,13 @@ static int s3_mode(const S3Args &g, int mode, hipStream_t st, hipEvent_t e0, hip
     case 15: return dma_ok ? s3_launch_dma<4, 2, 4, 4, true>(g, st, e0, e1) : s3_launch<2, 4, 2, 2, 1>(g, st, e0, e1);
     // 28 / 29: 128x192 (plain / persistent): N = 768 = 4 x 192 -- M = 8 192 is 64 x 4 = 256 tiles, ONE whole round, where 128x256 tiles
     // are 192 (a quarter of the chip idle).  LDS-DMA staging only; otherwise the 128x128 register tile
-    case 28: return dma_ok ? s3_launch_dma<2, 4, 4, 3>(g, st, e0, e1) : s3_launch<2, 4, 4, 2, 1>(g, st, e0, e1);
-    case 29: return dma_ok ? s3_launch_dma<2, 4, 4, 3, true>(g, st, e0, e1) : s3_launch<2, 4, 4, 2, 1>(g, st, e0, e1);
+    case 28: return flatw_ok ? s3_launch_dma<2, 4, 4, 3>(g, st, e0, e1) : s3_launch<2, 4, 4, 2, 1>(g, st, e0, e1);
+    case 29: return flatw_ok ? s3_launch_dma<2, 4, 4, 3, true>(g, st, e0, e1) : s3_launch<2, 4, 4, 2, 1>(g, st, e0, e1);
     // 30: 256x256 (W single-buffered: 144 KB): a third fewer operand bytes per flop than 128x256
     case 30: return dma_ok ? s3_launch_dma<2, 4, 8, 4, false, true>(g, st, e0, e1) : s3_launch<2, 4, 2, 2, 1>(g, st, e0, e1);
+    // 32: 160x256 (156 KB of LDS): M = 9 248 x N = 1024 is 58 x 4 = 232 tiles, ONE round, where 128x256 tiles are 292 (a round and a
+    // remainder); 11 % fewer operand bytes per flop than 128x256
+    case 32: return flata_ok ? s3_launch_dma<2, 4, 5, 4>(g, st, e0, e1) : s3_launch<2, 4, 2, 2, 1>(g, st, e0, e1);
     case 16: return dma_ok ? s3_launch_dma<2, 4, 4, 2>(g, st, e0, e1) : s3_launch<2, 4, 4, 2, 1>(g, st, e0, e1);
     case 17: return dma_ok ? s3_launch_dma<2, 4, 4, 2, true>(g, st, e0, e1) : s3_launch<2, 4, 4, 2, 1, 1, true>(g, st, e0, e1);
     case 2: return s3_launch<2, 4, 4, 2, 1>(g, st, e0, e1);
@@ -1097,35 +1161,50 @@ static int s3_mode(const S3Args &g, int mode, hipStream_t st, hipEvent_t e0, hip
   }
 }
 
-static int s3_dispatch(const S3Args &g, const sgic_launch_opts *opts, hipStream_t st) {
-  const int M = g.M, N = g.N, K = g.K;
-  int mode = opts ? opts->tile_mode : 0;
-  SGIC_REQUIRE(mode >= 0 && mode <= SGIC_SPLIT3_TILE_MODES, "tile_mode");
+// What a launch mode does with an M x N product (host only; s3_dispatch runs exactly this, sgic_gemm_split3_plan exports it):
+// the single-launch mode of the first launch with its nominal tile, and -- for the modes that finish the rows beyond the last
+// WHOLE round of the 256 CUs with another tile -- the row at which the second launch starts (0: one launch) and that launch's mode.
+struct S3Plan {
+  int mode, tile_m, tile_n, split_row, tail_mode;
+};
+
+static void s3_tile_of(int mode, int &tm, int &tn) {   // nominal tile of a single-launch mode (s3_mode; its fallbacks for operands a kernel cannot address are not reflected)
+  switch (mode) {
+    case 1: case 10: tm = 128, tn = 256; break;
+    case 14: case 15: tm = 256, tn = 128; break;
+    case 28: case 29: tm = 128, tn = 192; break;
+    case 30: tm = 256, tn = 256; break;
+    case 32: tm = 160, tn = 256; break;
+    case 2: case 11: case 16: case 17: tm = 128, tn = 128; break;
+    case 3: case 21: case 22: tm = 64, tn = 64; break;
+    case 4: case 18: tm = 32, tn = 32; break;
+    case 19: tm = 64, tn = 32; break;
+    case 20: tm = 32, tn = 64; break;
+    case 23: tm = 80, tn = 64; break;
+    case 24: tm = 80, tn = 48; break;
+    case 25: tm = 32, tn = 48; break;
+    default: tm = 64, tn = 128; break;   // 5
+  }
+}
+
+static S3Plan s3_plan(int M, int N, bool conv, int mode) {
+  S3Plan p{mode, 0, 0, 0, 0};
+  const long tm128 = (M + 127) / 128;
   if (!mode) {
     // the largest tile whose grid still fills the 256 CUs ~twice over; launches that cannot fill the chip take the small tiles
-    const long t256 = (long)((M + 127) / 128) * ((N + 255) / 256), t128 = (long)((M + 127) / 128) * ((N + 127) / 128),
-               t64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-    mode = t256 >= 512 ? 1 : (t128 >= 384 ? 2 : (t64 >= 256 ? 3 : 4));
-  }
-  const auto *evp = prof_next(opts);
-  hipEvent_t e0 = evp ? evp->first : nullptr, e1 = evp ? evp->second : nullptr;
-  if (mode == 31) {
+    const long t256 = tm128 * ((N + 255) / 256), t128 = tm128 * ((N + 127) / 128), t64 = (long)((M + 63) / 64) * ((N + 63) / 64);
+    p.mode = t256 >= 512 ? 1 : (t128 >= 384 ? 2 : (t64 >= 256 ? 3 : 4));
+  } else if (mode == 26 && !conv && tm128 * ((N + 255) / 256) > 256 && (long)((M + 159) / 160) * ((N + 255) / 256) <= 256) {
+    // 26 by arithmetic: 128x256 tiles need more than one round where 160x256 tiles (mode 32) make exactly one -- one launch, no
+    // remainder (M = 9 248 x N = 1024: 58 x 4 = 232 workgroups instead of 256 + a tail launch for 1 056 rows)
+    p.mode = 32;
+  } else if (mode == 31) {
     // 31: 256x256 tiles (mode 30) for the rows that fill WHOLE rounds of the 256 CUs + 128x256 tiles (mode 1) for the rest
     const long tiles_n = (N + 255) / 256, tiles_m = (M + 255) / 256;
     const long m_full = (tiles_m * tiles_n / 256) * 256 / tiles_n, m_split = m_full * 256;
-    if (m_full > 0 && m_split < M && !g.conv_C) {
-      S3Args g1 = g, g2 = g;
-      g1.M = (int)m_split;
-      g2.M = M - (int)m_split;
-      g2.A += g.a_packed ? m_split * 32 : m_split * K;
-      g2.m_base = (int)m_split;
-      int rc = s3_mode(g1, 30, st, e0, nullptr);
-      if (rc) return rc;
-      return s3_mode(g2, 1, st, nullptr, e1);
-    }
-    mode = 30;
-  }
-  if ((mode >= 6 && mode <= 9) || mode == 12 || mode == 13 || mode == 26 || mode == 27) {
+    p.mode = 30;
+    if (m_full > 0 && m_split < M && !conv) p.split_row = (int)m_split, p.tail_mode = 1;
+  } else if ((mode >= 6 && mode <= 9) || mode == 12 || mode == 13 || mode == 26 || mode == 27) {
     // modes 6 / 7 = modes 1 / 2 for the rows that fill WHOLE rounds of the 256 CUs + the 64x128 two-per-CU tiles for the rest,
     // as two launches (the first ends on a full round, so nothing idles at the seam): a last round of big tiles that covers a
     // fraction of the chip costs a whole tile time, the small tiles finish it in about half.  One profiler record spans both.
@@ -1140,19 +1219,38 @@ static int s3_dispatch(const S3Args &g, const sgic_launch_opts *opts, hipStream_
     const long tiles_n = (N + TN - 1) / TN, tiles_m = (M + TM - 1) / TM;
     const long m_full = (tiles_m * tiles_n / 256) * 256 / tiles_n;   // m-tiles inside whole rounds
     const long m_split = m_full * TM;
-    if (m_full > 0 && m_split < M && !g.conv_C) {
-      S3Args g1 = g, g2 = g;
-      g1.M = (int)m_split;
-      g2.M = M - (int)m_split;
-      g2.A += g.a_packed ? m_split * 32 : m_split * K;   // the planes keep their strides (a_plane, a_rows); C / R / Cp rows are addressed through m_base
-      g2.m_base = (int)m_split;
-      int rc = s3_mode(g1, big_mode, st, e0, nullptr);
-      if (rc) return rc;
-      return s3_mode(g2, tail, st, nullptr, e1);
-    }
-    mode = big_mode;
+    p.mode = big_mode;
+    if (m_full > 0 && m_split < M && !conv) p.split_row = (int)m_split, p.tail_mode = tail;
   }
-  return s3_mode(g, mode, st, e0, e1);
+  s3_tile_of(p.mode, p.tile_m, p.tile_n);
+  return p;
+}
+
+extern "C" int sgic_gemm_split3_plan(int M, int N, int conv, int tile_mode, int *tile_m, int *tile_n, int *split_row, int *tail_mode) {
+  SGIC_REQUIRE(M > 0 && N > 0 && tile_m && tile_n && split_row && tail_mode, "null/empty");
+  SGIC_REQUIRE(tile_mode >= 0 && tile_mode <= SGIC_SPLIT3_TILE_MODES, "tile_mode");
+  const S3Plan p = s3_plan(M, N, conv != 0, tile_mode);
+  *tile_m = p.tile_m, *tile_n = p.tile_n, *split_row = p.split_row, *tail_mode = p.tail_mode;
+  return SGIC_OK;
+}
+
+static int s3_dispatch(const S3Args &g, const sgic_launch_opts *opts, hipStream_t st) {
+  const int mode = opts ? opts->tile_mode : 0;
+  SGIC_REQUIRE(mode >= 0 && mode <= SGIC_SPLIT3_TILE_MODES, "tile_mode");
+  const S3Plan p = s3_plan(g.M, g.N, g.conv_C != 0, mode);
+  const auto *evp = prof_next(opts);
+  hipEvent_t e0 = evp ? evp->first : nullptr, e1 = evp ? evp->second : nullptr;
+  if (!p.split_row) return s3_mode(g, p.mode, st, e0, e1);
+  // two launches; one profiler record spans both
+  const long m_split = p.split_row;
+  S3Args g1 = g, g2 = g;
+  g1.M = (int)m_split;
+  g2.M = g.M - (int)m_split;
+  g2.A += g.a_packed ? m_split * 32 : m_split * g.K;   // the planes keep their strides (a_plane, a_rows); C / R / Cp rows are addressed through m_base
+  g2.m_base = (int)m_split;
+  int rc = s3_mode(g1, p.mode, st, e0, nullptr);
+  if (rc) return rc;
+  return s3_mode(g2, p.tail_mode, st, nullptr, e1);
 }
 
 // C[M,N] = act(A . W^T + bias) + R with both operands as bf16x3 planes (see the header of this file).
@@ -1165,7 +1263,8 @@ static int s3_dispatch(const S3Args &g, const sgic_launch_opts *opts, hipStream_
 // of the chip + mode 5 for the remaining rows (two launches), 8 / 9 = the same with mode 4 for the remaining rows, 10 / 11 = 1 / 2
 // as a persistent launch (256 resident workgroups walk the tiles, the next tile's first loads fly during the epilogue), 12 / 13 =
 // 8 / 9 with the whole rounds walked persistently, 14 / 15 = 256x128 tiles (plain / persistent: the 3x3 convolutions with 128
-// output channels); bitwise identical results.
+// output channels), 16-31 as listed in include/sgic.h, 32 = 160x256 tiles (one launch of them is also what 26 becomes when s3_plan
+// finds that they cover the product in one round where 128x256 tiles do not); bitwise identical results.
 extern "C" int sgic_gemm_split3_f32(const float *d_A, int lda, int a_seg, int a_seg_stride, uint16_t *d_Aplanes,
                                     const uint16_t *d_Wplanes, const float *d_bias, const float *d_R, int ldr, float *d_C,
                                     int ldc, uint16_t *d_Cplanes, int M, int N, int K, int act, int c_seg, int c_seg_stride,

@@ -6,6 +6,10 @@ Writes gpurun_out/retune_big.json = {"picks": {key: mode}, "table": {key: {mode:
 --attn: the attention launches instead (attn_modes 1-7, both arithmetics) -> gpurun_out/retune_attn.json.
 --small: the split GEMMs of single-image sized launches instead (M <= ops.SPLIT3_SMALL_M: the small register-staged tiles against the
 ring kernel's modes 18-22) -> gpurun_out/retune_small.json.
+--keys K1,K2,...: only these keys of the in-tree cache (e.g. "gemm3|9248|1024|4096|1|0").
+--merge writes no gemm3 / conv3 pick above INTREE_MAX_SPLIT3 into the in-tree file: tests/test_tile_cache_cpu.py pins the in-tree
+picks of these kinds to 0..31.  Mode 32 (160x256 tiles) is raced here for the table; in the tree it is reached through mode 26,
+which takes it by arithmetic (csrc/gemm_split.hip: s3_plan).
 (Replaces the round-2 one-off scripts gemm_big_modes.py / conv_modes.py / gemm_shapes_modes.py.)"""
 import json
 import os
@@ -17,14 +21,25 @@ SMALL = "--small" in sys.argv
 ATTN = "--attn" in sys.argv
 OUT = os.path.join(ROOT, "gpurun_out", "retune_attn.json" if ATTN else ("retune_small.json" if SMALL else "retune_big.json"))
 SMALL_MODES = (3, 4, 5, 18, 19, 20, 21, 22, 23, 24, 25)
-GEMM_MODES = (1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 16, 17, 26, 27, 28, 29, 30, 31)
-CONV_MODES = (1, 2, 3, 5, 10, 11, 14, 15, 16, 17, 30)
+GEMM_MODES = (1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 16, 17, 26, 27, 28, 29, 30, 31, 32)
+CONV_MODES = (1, 2, 3, 5, 10, 11, 14, 15, 16, 17, 30, 32)
+INTREE_MAX_SPLIT3 = 31
+KEYS = set(sys.argv[sys.argv.index("--keys") + 1].split(",")) if "--keys" in sys.argv else None
+
+
+def mergeable(new):
+    """(picks that may go into the in-tree cache, picks refused)"""
+    refused = {k: v for k, v in new.items() if k.split("|")[0] in ("gemm3", "conv3") and v > INTREE_MAX_SPLIT3}
+    return {k: v for k, v in new.items() if k not in refused}, refused
 
 
 def merge():
     import sgic_amd  # noqa: F401
     from sgic_amd import ops
-    new = json.load(open(OUT))["picks"]
+    new, refused = mergeable(json.load(open(OUT))["picks"])
+    if refused:
+        print(f"NOT merged (the in-tree cache holds gemm3 / conv3 picks 0..{INTREE_MAX_SPLIT3} only -- tests/test_tile_cache_cpu.py; "
+              f"these shapes keep their in-tree pick):", refused)
     d = json.load(open(ops._INTREE_CACHE))
     changed = {k: (d["picks"].get(k), v) for k, v in new.items() if d["picks"].get(k) != v}
     d["picks"].update(new)
@@ -58,6 +73,8 @@ def main():
     for key, old in sorted(cache.items()):
         kind, *nums = key.split("|")
         nums = [int(x) for x in nums]
+        if KEYS is not None and key not in KEYS:
+            continue
         if ATTN:
             if kind not in ("attn", "attn3"):
                 continue
@@ -93,7 +110,7 @@ def main():
             r = torch.randn(M, N, device=dev, generator=g) if res else None
             ap = ops.split3_planes(a)
             out = torch.empty(M, N, device=dev)
-            modes = list(SMALL_MODES) if SMALL else [m for m in GEMM_MODES if not (m in (1, 6, 8, 10, 12, 26, 27, 30, 31) and N < 256) and not (m in (28, 29) and N < 192)]
+            modes = list(SMALL_MODES) if SMALL else [m for m in GEMM_MODES if m <= ops._MAX_MODE["gemm3"] and not (m in (1, 6, 8, 10, 12, 26, 27, 30, 31, 32) and N < 256) and not (m in (28, 29) and N < 192)]
             t = race(lambda m: ops.gemm(ap, w, b, residual=r, act=act, out=out, tile=m, precision="split3"), modes)
             fl = 2.0 * M * N * K
         elif kind == "conv3":
@@ -109,7 +126,7 @@ def main():
             hp = ops.halo_planes_buffer(dev, B, H, W, Cin)
             ops.split3_planes(halo.view(-1, Cin), out=ops.Planes(halo.numel() // Cin, Cin, dev, buf=hp.t))
             out = torch.empty(M, Cout, device=dev)
-            modes = [m for m in CONV_MODES if not (m in (1, 10, 30) and Cout < 256)]
+            modes = [m for m in CONV_MODES if m <= ops._MAX_MODE["conv3"] and not (m in (1, 10, 30, 32) and Cout < 256)]
             t = race(lambda m: ops.conv3x3(hp, w, b, B, H, W, Cin, Cout, residual=r, act=act, out=out, tile=m, precision="split3"), modes)
             fl = 2.0 * M * Cout * 9 * Cin
             del halo
