@@ -872,7 +872,7 @@ def groupnorm(x, gamma, beta, B, H, W, swish=True, halo=False, groups=32, eps=1e
     C = x.shape[1]
     assert ldx == C
     dev = x.device
-    key = (str(dev), B, C)
+    key = (str(dev), B, C, groups)     # the statistics buffer is sized by `groups`
     if key not in _GN_WS:
         _GN_WS[key] = (torch.empty(B * 64 * C * 2, dtype=torch.float64, device=dev),
                        torch.empty(B * groups * 2, dtype=torch.float32, device=dev))

@@ -1,7 +1,9 @@
 """CPU restatements of the glue, layout and entropy-index kernels (csrc/misc.hip, csrc/decode.hip, csrc/entropy.hip), built from
 library operations (F.unfold, F.pixel_shuffle, reshape / permute, torch.sort, torch.argmax, torch.clamp, torch.where) and fp64
 arithmetic, not from the kernels' index arithmetic.  tests/test_kernels_ref_cpu.py checks them against each other and against the C
-oracle; tests/test_gpu_kernels.py and tests/test_gpu_kernels_entropy.py compare the kernels with them.
+oracle; tests/test_gpu_kernels.py and tests/test_gpu_kernels_entropy.py compare the kernels with them.  The fp64 attention with
+Swin-shaped bias variants, the window partition and the fp64 3x3 convolution serve tests/test_gpu_attention_rowmap.py,
+tests/test_swin_rowmap_cpu.py and tests/test_gpu_conv_chain.py.
 
 Tolerance rules used by those tests:
   * half-integer band (l2norm_u8): the u8 code must equal the fp64 code wherever (u * 0.5 + 0.5) * 255 is farther than Q_BAND from a
@@ -359,6 +361,56 @@ def half_even_rows(n=16, D=64):
         if len(rows) == n:
             break
     return np.stack(rows), np.array(ks)
+
+
+# ---- attention and the Swin window layout ---------------------------------------------------------------------------------------
+def window_grid(L):
+    """(rows, cols) of the token grid of an L-token window: square when L is a square (256 -> 16 x 16), else 8 rows"""
+    r = int(round(L ** 0.5))
+    return (r, r) if r * r == L else (8, L // 8)
+
+
+def attn_bias_variants(L, g):
+    """(4, L, L) additive bias [plain | +upper-lower | +left-right | both] shaped like Swin's shift masks on the window's token grid
+    (token t = (i, j)): with the grid cut at its lower half of rows (right half of columns), a query and a key on different sides
+    of the cut are masked with -inf.  Every query keeps the keys of its own side, itself among them: no row is fully masked."""
+    gh, gw = window_grid(L)
+    assert gh * gw == L and gh >= 2 and gw >= 2
+    i, j = torch.arange(L) // gw, torch.arange(L) % gw
+    low, right = i >= gh - gh // 2, j >= gw - gw // 2
+    ul = torch.zeros(L, L).masked_fill(low[:, None] != low[None, :], float("-inf"))
+    lr = torch.zeros(L, L).masked_fill(right[:, None] != right[None, :], float("-inf"))
+    pos = torch.randn(L, L, generator=g)
+    b = torch.stack([pos, pos + ul, pos + lr, (pos + ul) + lr])
+    assert bool(torch.isfinite(b).any(dim=-1).all())
+    return b
+
+
+def attention64(qkv, L, nseq, heads, bias, var, scale):
+    """qkv (nseq * L, 3 * heads * 64) dense -> fp64 softmax(scale q k^T + bias[var[s]]) v as (nseq * L, heads * 64)"""
+    D = heads * 64
+    q, k, v = (qkv[:, i * D:(i + 1) * D].reshape(nseq, L, heads, 64).permute(0, 2, 1, 3).double() for i in range(3))
+    s = q @ k.transpose(-1, -2) * scale
+    if bias is not None:
+        s = s + bias[var.long()].double()[:, None]
+    return (torch.softmax(s, dim=-1) @ v).permute(0, 2, 1, 3).reshape(nseq * L, D)
+
+
+def window_partition(x, win):
+    """(B, H, W, C) -> (B * H/win * W/win, win * win, C): windows in raster order, tokens of a window in raster order"""
+    B, H, W, C = x.shape
+    return x.reshape(B, H // win, win, W // win, win, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, win * win, C)
+
+
+def conv3x3_64(x, w, bias, res, act):
+    """x (B, Cin, H, W), w (Cout, Cin, 3, 3), res (B, Cout, H, W) or None -> (pre-activation, result) as fp64 rows (B*H*W, Cout);
+    act 0 / 2 (SiLU), the residual added after the activation"""
+    pre = F.conv2d(x.double(), w.double(), bias.double(), padding=1)
+    out = F.silu(pre) if act == 2 else pre
+    if res is not None:
+        out = out + res.double()
+    rows = lambda t: t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])  # noqa: E731
+    return rows(pre), rows(out)
 
 
 def gemm_batched64(a, w, bias, res, act):

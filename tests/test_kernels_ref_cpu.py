@@ -107,3 +107,38 @@ def test_half_even_rows_have_the_property_they_are_built_for():
     assert np.array_equal(q[:, 3], ks) and np.array_equal(np.floor(t + np.float32(0.5)), ks + 1)
     _, q64, band = kr.l2norm_u8_64(x)
     kr.u8_check(q, q64, band)
+
+
+def test_attention_and_conv_refs_against_direct_loops():
+    """attention64 against a per-(sequence, head) loop with the mask applied by DROPPING the masked keys (no -inf arithmetic);
+    the bias variants: plain is finite, every row keeps its own key, UL / LR mask different key sets and variant 3 their union;
+    conv3x3_64 against a direct sum over the nine taps at two pixels"""
+    g = torch.Generator().manual_seed(4)
+    L, nseq, heads = 64, 4, 2
+    b = kr.attn_bias_variants(L, g)
+    fin = torch.isfinite(b)
+    assert bool(fin[0].all()) and bool(fin[:, torch.arange(L), torch.arange(L)].all())
+    assert not torch.equal(fin[1], fin[2]) and torch.equal(fin[3], fin[1] & fin[2])
+    assert int((~fin[1]).sum()) == 2 * 32 * 32 and int((~fin[2]).sum()) == 2 * 32 * 32      # half the keys of every query
+    assert bool(fin[1, 0, :32].all()) and not bool(fin[1, 0, 32:].any())                    # token 0: upper rows only
+    assert bool(fin[2, 0].reshape(8, 8)[:, :4].all()) and not bool(fin[2, 0].reshape(8, 8)[:, 4:].any())   # ... left columns only
+    qkv = torch.randn(nseq * L, 3 * heads * 64, generator=g)
+    var = torch.tensor([1, 2, 3, 0], dtype=torch.int32)
+    got = kr.attention64(qkv, L, nseq, heads, b, var, 0.2)
+    D = heads * 64
+    for s in range(nseq):
+        for h in range(heads):
+            q, k, v = (qkv[s * L:(s + 1) * L, i * D + h * 64:i * D + (h + 1) * 64].double() for i in range(3))
+            for t in (0, 31, 63):
+                keep = fin[var[s], t]
+                w = torch.softmax((k[keep] @ q[t]) * 0.2 + b[var[s], t][keep].double(), dim=0)
+                assert float((w @ v[keep] - got[s * L + t, h * 64:(h + 1) * 64]).abs().max()) < 1e-12
+    x, w4 = torch.randn(2, 4, 5, 6, generator=g), torch.randn(3, 4, 3, 3, generator=g)
+    bias, res = torch.randn(3, generator=g), torch.randn(2, 3, 5, 6, generator=g)
+    pre, out = kr.conv3x3_64(x, w4, bias, res, 2)
+    xp = torch.nn.functional.pad(x.double(), (1, 1, 1, 1))
+    for (n, y, xx) in [(0, 0, 0), (1, 4, 5)]:
+        want = (xp[n, :, y:y + 3, xx:xx + 3][None] * w4.double()).sum(dim=(1, 2, 3)) + bias.double()
+        row = (n * 5 + y) * 6 + xx
+        assert float((pre[row] - want).abs().max()) < 1e-12
+        assert float((out[row] - (want * torch.sigmoid(want) + res[n, :, y, xx].double())).abs().max()) < 1e-12
