@@ -518,6 +518,47 @@ int sgic_lpips_alex_conv1_patches_split3(const uint8_t *d_img, int B, int H, int
 int sgic_relu_maxpool3_patches5_split3(const float *d_in, int B, int H, int W, int C, uint16_t *d_planes, sgic_stream_t stream);
 int sgic_relu_maxpool3_halo_split3(const float *d_in, int B, int H, int W, int C, uint16_t *d_halo_planes, sgic_stream_t stream);
 
+/* FID and KID (fid.InceptionFID, evaluate.py --fid_ckpt; pytorch-fid's InceptionV3 at pool3).  Every convolution
+ * of the graph is sgic_gemm_split3_f32 over the planes that sgic_patches_split3 writes (slice-major bf16x3, a_packed = 1); every
+ * activation is stored BEFORE its ReLU and its consumers apply it on read.
+ *
+ * sgic_fid_resize299: d_canvas (B, H, W, 3) u8 and n descriptors (image, y0, x0, h, w), int32, once on the host (h_desc: checked here)
+ * and once on the device (d_desc: read by the kernel; the same values) -> d_out (n, 299, 299, 3) fp32: x = u / 255, the h x w window
+ * at (y0, x0) of the image resized bilinearly to 299 x 299 with src = max((dst + 0.5) in / 299 - 0.5, 0) (the position exactly, in
+ * integers: floor and remainder of ((2 dst + 1) in - 299) / 598), the neighbour clamped to in - 1, within rows first, then between
+ * rows, with weights (1 - lambda, lambda); then 2 x - 1.
+ *
+ * sgic_patches_split3: d_in fp32 NHWC rows of leading dimension ld, columns col0 .. col0 + C - 1 (a slice of a concat buffer) ->
+ * relu when `relu` -> the kh x kw patches at stride (sh, sw) with zero padding (ph, pw), OH = (H + 2 ph - kh) / sh + 1, as the A
+ * operand [3][Kp / 32][B OH OW][32], Kp = ceil(kh kw C / 32) 32: column k = (ky kw + kx) C + c of row (b, oy, ox) is the input at
+ * (oy sh - ph + ky, ox sw - pw + kx), 0 outside the map and for k >= kh kw C.  Every element is written.  Any C >= 1; C % 8 == 0 with
+ * ld % 4 == 0, col0 % 4 == 0 and a 16-byte aligned d_in takes the vector path.  kh = kw = 1: relu + pack.
+ *
+ * sgic_relu_maxpool3s2 / sgic_relu_avgpool3s1p1 / sgic_relu_maxpool3s1p1: d_in (B H W, C) fp32 -> relu -> max over 3 x 3 at stride
+ * 2 without padding (floor) / the mean over the taps of a 3 x 3 window at stride 1, padding 1, that lie inside the map (summed in
+ * row-major order in fp32, divided once by their number) / max over the same window -> fp32 rows of leading dimension ldo at column
+ * co (a slice of a concat buffer).  C % 4 == 0, ldo % 4 == 0, co % 4 == 0.
+ *
+ * sgic_relu_mean_rows: d_in (B R, C) fp32 -> d_out (B, C): (relu(row 0) + relu(row 1) + ... + relu(row R - 1), one fp32 accumulator,
+ * in that order) / R.  The order does not depend on B.
+ *
+ * sgic_gram_f64: d_c[i][j] (n x m, leading dimension ldc, fp64) = sum_k A[ia[i]][k] B[ib[j]][k], k = 0 .. K - 1 in order in one fp64
+ * accumulator per element, from fp32 rows (leading dimensions lda, ldb).  d_ia / d_ib: int32 row indices on the device or NULL (row
+ * i itself); an index outside [0, rows_a) (resp. rows_b) reads as a row of zeros, never memory.
+ *
+ * SGIC_EINVAL before any launch: a null pointer, an empty extent, planes or pool buffers that are not 16-byte aligned, a descriptor
+ * outside the canvas, a column slice outside its leading dimension, 2^31 or more rows. */
+int sgic_fid_resize299(const uint8_t *d_canvas, int B, int H, int W, const int32_t *h_desc, const int32_t *d_desc, int n, float *d_out,
+                       sgic_stream_t stream);
+int sgic_patches_split3(const float *d_in, int ld, int col0, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                        int relu, uint16_t *d_planes, sgic_stream_t stream);
+int sgic_relu_maxpool3s2(const float *d_in, int B, int H, int W, int C, float *d_out, int ldo, int co, sgic_stream_t stream);
+int sgic_relu_avgpool3s1p1(const float *d_in, int B, int H, int W, int C, float *d_out, int ldo, int co, sgic_stream_t stream);
+int sgic_relu_maxpool3s1p1(const float *d_in, int B, int H, int W, int C, float *d_out, int ldo, int co, sgic_stream_t stream);
+int sgic_relu_mean_rows(const float *d_in, int B, int R, int C, float *d_out, sgic_stream_t stream);
+int sgic_gram_f64(const float *d_a, long lda, const int32_t *d_ia, int rows_a, int n, const float *d_b, long ldb, const int32_t *d_ib,
+                  int rows_b, int m, int K, double *d_c, long ldc, sgic_stream_t stream);
+
 /* F.pad(x, (pl, pr, pt, pb), mode="replicate") on (BC, H, W) fp32 planes -> (BC, H+pt+pb, W+pl+pr)
  * (compress.py:258-261: every image is padded to a multiple of 256 before the encoder). */
 int sgic_pad_replicate(const float *d_in, float *d_out, int BC, int H, int W, int pl, int pr, int pt, int pb,

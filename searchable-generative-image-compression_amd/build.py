@@ -10,9 +10,10 @@ LIB = os.path.join(HERE, "libsgic.so")
 # -ffp-contract=off only for the entropy file: its float ops must be single IEEE operations (bit parity
 # with the CPU oracle); the GEMM/attention files keep fma contraction.  quality.hip: its fp64 maps are compared with a CPU
 # restatement that has no fma either.  lpips.hip, dists.hip: their input layers are compared with single fp32 operations for
-# equality; the DISTS head needs x == y to give exactly 0.  lpips_alex.hip: the same input layer, compared the same way.
+# equality; the DISTS head needs x == y to give exactly 0.  lpips_alex.hip: the same input layer, compared the same way.  fid.hip: its
+# producers and pools are compared for equality, its resize and Gram with restatements that have no fma.
 FLAGS = {"entropy.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "quality.hip": ["-ffp-contract=off"],
-         "lpips.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "lpips_alex.hip": ["-ffp-contract=off"]}
+         "lpips.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "lpips_alex.hip": ["-ffp-contract=off"], "fid.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src_list, out):

@@ -22,6 +22,14 @@
   evaluate.py ... --dists_ckpt P [P ...]                        adds "dists" in the same places (after "lpips" where both are asked
                                                                 for): DISTS with the VGG16 trunk (dists.DistsVGG); P: state dict
                                                                 file(s) with the trunk, alpha and beta (dists.load_weights)
+  evaluate.py ... --fid_ckpt P [P ...] [--fid_patch 256]        adds "fid", "kid", "kid_std", "fid_patches" and "fid_skipped" to the
+                                                                summary (and "anchor_fid", "anchor_kid", "anchor_kid_std" with an
+                                                                anchor): FID and KID between the set of originals and the set of
+                                                                reconstructions on pytorch-fid's Inception-v3 (fid.InceptionFID), over
+                                                                the 256 x 256 windows of the HiFiC protocol (fid.patch_grid;
+                                                                --fid_patch 0: whole images); P: state dict file(s) of the Inception
+                                                                (torchvision's or pytorch-fid's keys, fid.load_weights).  The
+                                                                per-image lines do not change
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -66,9 +74,9 @@ def _json_number(v):
     return ("inf" if v > 0 else "-inf") if math.isinf(v) else v
 
 
-def summarise(records):
+def summarise(records, fid_sets=None):
     """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
-    lpips, lpips_alex and dists when the records carry them"""
+    lpips, lpips_alex and dists when the records carry them; fid_sets (FidSets, --fid_ckpt): its keys after all the others"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
@@ -96,16 +104,63 @@ def summarise(records):
             out["anchor_lpips_alex"] = mean([a["lpips_alex"] for a in anchors if a.get("lpips_alex") is not None])
         if any("dists" in a for a in anchors):
             out["anchor_dists"] = mean([a["dists"] for a in anchors if a.get("dists") is not None])
+    if fid_sets is not None:
+        out.update(fid_sets.summary())
     return out
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None, lpips_alex_model=None):
+class FidSets:
+    """--fid_ckpt: the Inception features of the originals, the reconstructions and (with an anchor) the decoded anchors over the same
+    windows (fid.patch_grid of every image), accumulated on the device; FID and KID once at the end"""
+
+    def __init__(self, ckpt, patch, device):
+        from . import fid
+        self.fid, self.patch = fid, int(patch)
+        self.model = fid.InceptionFID(ckpt, device)
+        self.orig, self.recon, self.anchor = fid.FeatureStats(), fid.FeatureStats(), fid.FeatureStats()
+        self.skipped = 0
+
+    def windows(self, a):
+        """a (B, H, W, 3) -> the descriptors of the batch, None when the images give no window (counted as skipped)"""
+        B, H, W, _ = a.shape
+        desc = self.fid.descriptors(B, H, W, self.patch)
+        if not len(desc):
+            self.skipped += B
+            return None
+        return desc
+
+    def add(self, which, images, desc):
+        getattr(self, which).add(self.model.features(images, desc))
+
+    def _pair(self, x, y):
+        if x.n < 2 or y.n < 2:
+            return None, None, None
+        X, Y = x.features(), y.features()
+        k, k_std = self.fid.kid(X, Y)
+        return self.fid.fid(X, Y), k, k_std
+
+    def summary(self):
+        n = self.orig.n
+        if 0 < n < self.fid.DIM:
+            print(f"[WARN] FID over {n} windows: with fewer than {self.fid.DIM} samples the covariances are rank-deficient and the number "
+                  "is biased; compare it only with numbers over the same count", file=sys.stderr)
+        f, k, k_std = self._pair(self.orig, self.recon)
+        out = {"fid": f, "kid": k, "kid_std": k_std, "fid_patches": n, "fid_skipped": self.skipped}
+        if self.anchor.n:
+            f, k, k_std = self._pair(self.orig, self.anchor)
+            out.update({"anchor_fid": f, "anchor_kid": k, "anchor_kid_std": k_std})
+        return out
+
+
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None, lpips_alex_model=None,
+                 decoded_out=None):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
     on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back.
     lpips_model (lpips.LpipsVGG), dists_model (dists.DistsVGG), lpips_alex_model (lpips_alex.LpipsAlex): every record also carries
-    "lpips" / "dists" / "lpips_alex" of the decoded anchor against the original."""
+    "lpips" / "dists" / "lpips_alex" of the decoded anchor against the original.  decoded_out: a list that receives the decoded anchors
+    (B, H, W, 3) u8 on the device (the FID of the anchor set)."""
     from . import jpeg, jpeg_enc, quality
     B, H, W, _ = a_u8.shape
     if fixed_quality is None:
@@ -115,6 +170,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
         picks = [(int(fixed_quality), None)] * B
     files = jpeg_enc.encode_batch(a_u8, [q for q, _ in picks], subsampling)
     decoded = jpeg.JpegBatch(files).decode(a_u8.device)
+    if decoded_out is not None:
+        decoded_out.append(decoded)
     m = quality.measure(a_u8, decoded)
     lp = lpips_model.measure(a_u8, decoded) if lpips_model is not None else None
     la = lpips_alex_model.measure(a_u8, decoded) if lpips_alex_model is not None else None
@@ -158,6 +215,10 @@ def main(argv=None):
                     help="state dict file(s) with the AlexNet trunk and the lin layers of LPIPS: adds \"lpips_alex\" to every record")
     ap.add_argument("--dists_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) with the VGG16 trunk and alpha, beta of DISTS: adds \"dists\" to every record")
+    ap.add_argument("--fid_ckpt", type=str, nargs="+", default=None,
+                    help="state dict file(s) of the Inception-v3 of FID: adds \"fid\", \"kid\", \"kid_std\" to the summary")
+    ap.add_argument("--fid_patch", type=int, default=256,
+                    help="side of the windows FID and KID are computed on (the HiFiC protocol); 0: whole images")
     args = ap.parse_args(argv)
     if not args.bitstreams and not args.recon_dir:
         ap.error("give --bitstreams, --recon_dir or both")
@@ -168,6 +229,8 @@ def main(argv=None):
     anchor = args.anchor or ("jpeg" if args.anchor_quality is not None else None)
     if args.batch_size < 1:
         ap.error("--batch_size must be at least 1")
+    if args.fid_patch < 0:
+        ap.error("--fid_patch must be 0 (whole images) or a window side")
 
     from concurrent.futures import ThreadPoolExecutor
     from . import quality
@@ -186,6 +249,7 @@ def main(argv=None):
     if args.dists_ckpt:
         from .dists import DistsVGG
         dists_model = DistsVGG(args.dists_ckpt, dev)
+    fid_sets = FidSets(args.fid_ckpt, args.fid_patch, dev) if args.fid_ckpt else None
     originals = by_stem(glob(os.path.join(args.originals, "*.*")))
     containers = by_stem(glob(os.path.join(args.bitstreams, "*.c2df"))) if args.bitstreams else {}
     recons = by_stem(glob(os.path.join(args.recon_dir, "*.*"))) if args.recon_dir else None
@@ -221,8 +285,15 @@ def main(argv=None):
             la = lpips_alex_model.measure(a, b) if lpips_alex_model is not None else None
             ds = dists_model.measure(a, b) if dists_model is not None else None
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
+            decoded = [] if fid_sets is not None else None
             anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model,
-                                   lpips_alex_model) if anchor else None
+                                   lpips_alex_model, decoded) if anchor else None
+            desc = fid_sets.windows(a) if fid_sets is not None else None
+            if desc is not None:
+                fid_sets.add("orig", a, desc)
+                fid_sets.add("recon", b, desc)
+                if anchor:
+                    fid_sets.add("anchor", decoded[0], desc)
             for j, (stem, _, _) in enumerate(members):
                 nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
@@ -283,7 +354,7 @@ def main(argv=None):
                     measure_chunk(chunk, pending)
 
     records.sort(key=lambda r: r["name"])
-    summary = json.dumps(summarise(records))
+    summary = json.dumps(summarise(records, fid_sets))
     lines = [json.dumps(r) for r in records]
     if args.out:
         with open(args.out, "w") as f:

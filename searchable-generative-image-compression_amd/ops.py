@@ -1375,6 +1375,107 @@ def relu_maxpool3_halo(x, B, H, W, C):
     return hp
 
 
+def fid_resize299(canvas_u8, desc, out=None):
+    """the input step of the FID Inception (csrc/fid.hip): canvas_u8 (B, H, W, 3) u8 on the device, desc (n, 5) int32 numpy on the host,
+    rows (image, y0, x0, h, w) -> (n, 299, 299, 3) fp32: 2 * bilinear299(u / 255) - 1 of every window.  Only the descriptors leave the
+    host.  No synchronisation."""
+    require_gpu()
+    assert canvas_u8.is_cuda and canvas_u8.dtype == torch.uint8 and canvas_u8.is_contiguous() and canvas_u8.dim() == 4 and canvas_u8.shape[3] == 3
+    desc = np.ascontiguousarray(desc, dtype=np.int32)
+    assert desc.ndim == 2 and desc.shape[1] == 5 and desc.shape[0] >= 1, desc.shape
+    B, H, W, _ = canvas_u8.shape
+    n = desc.shape[0]
+    if out is None:
+        out = torch.empty(n, 299, 299, 3, dtype=torch.float32, device=canvas_u8.device)
+    assert out.shape == (n, 299, 299, 3) and out.dtype == torch.float32 and out.is_contiguous()
+    d_desc = torch.from_numpy(desc).to(canvas_u8.device)
+    call("sgic_fid_resize299", _p(canvas_u8), B, H, W, desc, _p(d_desc), n, _p(out))
+    return out
+
+
+def conv_out(n, k, s, p):
+    """output extent of a convolution or pool: input extent n, kernel k, stride s, padding p (floor)"""
+    return (n + 2 * p - k) // s + 1
+
+
+def patches_split3(x, B, H, W, kh, kw, sh=1, sw=1, ph=0, pw=0, relu=True, cols=None, out=None):
+    """x (B*H*W, ld) fp32, contiguous; cols = (col0, C): the column slice that is the map (default: all of it, a slice of a concat buffer
+    otherwise) -> ReLU when `relu` -> the kh x kw patches at stride (sh, sw) with zero padding (ph, pw) as a Planes(B*OH*OW, Kp), Kp =
+    kh*kw*C rounded up to 32: column (ky*kw + kx)*C + c, zero outside the map and in the padding columns (csrc/fid.hip).  The A operand
+    of that convolution as ops.gemm(planes, w (Cout, Kp), bias).  Any C >= 1.  out: a Planes of that shape to write into."""
+    require_gpu()
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda and x.shape[0] == B * H * W, (x.shape, (B, H, W))
+    ld = x.shape[1]
+    col0, C = (0, ld) if cols is None else cols
+    rows, Kp = B * conv_out(H, kh, sh, ph) * conv_out(W, kw, sw, pw), (kh * kw * C + 31) // 32 * 32
+    pl = out if out is not None else Planes(rows, Kp, x.device)
+    assert isinstance(pl, Planes) and pl.shape == (rows, Kp), (pl.shape, (rows, Kp))
+    call("sgic_patches_split3", _p(x), ld, int(col0), B, H, W, int(C), kh, kw, sh, sw, ph, pw, int(bool(relu)), _p(pl.t))
+    return pl
+
+
+def _relu_pool3(name, x, B, H, W, OH, OW, out, col0):
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda and x.shape[0] == B * H * W, (x.shape, (B, H, W))
+    C = x.shape[1]
+    if out is None:
+        out = torch.empty(B * OH * OW, C, dtype=torch.float32, device=x.device)
+    assert out.dim() == 2 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == B * OH * OW and col0 + C <= out.shape[1]
+    call(name, _p(x), B, H, W, C, _p(out), out.shape[1], int(col0))
+    return out
+
+
+def relu_maxpool3s2(x, B, H, W, out=None, col0=0):
+    """x (B*H*W, C) fp32 before its ReLU -> ReLU -> max-pool 3x3, stride 2, no padding (floor) -> columns col0 .. col0+C-1 of `out`
+    (B*OH*OW, ld) fp32, a concat buffer (default: a new (B*OH*OW, C) tensor); csrc/fid.hip.  C % 4 == 0."""
+    require_gpu()
+    assert H >= 3 and W >= 3, (H, W)
+    return _relu_pool3("sgic_relu_maxpool3s2", x, B, H, W, (H - 3) // 2 + 1, (W - 3) // 2 + 1, out, col0)
+
+
+def relu_avgpool3s1p1(x, B, H, W, out=None, col0=0):
+    """as relu_maxpool3s2, the pool being the 3x3 / stride 1 / padding 1 average with count_include_pad=False: the taps inside the map,
+    summed in row-major order in fp32, divided once by their number"""
+    require_gpu()
+    return _relu_pool3("sgic_relu_avgpool3s1p1", x, B, H, W, H, W, out, col0)
+
+
+def relu_maxpool3s1p1(x, B, H, W, out=None, col0=0):
+    """as relu_maxpool3s2, the pool being the 3x3 / stride 1 / padding 1 maximum"""
+    require_gpu()
+    return _relu_pool3("sgic_relu_maxpool3s1p1", x, B, H, W, H, W, out, col0)
+
+
+def relu_mean_rows(x, B, R, out=None):
+    """x (B*R, C) fp32 before its ReLU -> (B, C) fp32: the mean over the R rows of every image of relu(x), summed in row order in one
+    fp32 accumulator per (image, channel) and divided once (csrc/fid.hip): independent of B."""
+    require_gpu()
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda and x.shape[0] == B * R, (x.shape, (B, R))
+    if out is None:
+        out = torch.empty(B, x.shape[1], dtype=torch.float32, device=x.device)
+    assert out.shape == (B, x.shape[1]) and out.dtype == torch.float32 and out.is_contiguous()
+    call("sgic_relu_mean_rows", _p(x), B, R, x.shape[1], _p(out))
+    return out
+
+
+def gram_f64(a, b=None, ia=None, ib=None, out=None):
+    """out[i][j] = sum_k a[ia[i]][k] * b[ib[j]][k] in fp64 from fp32 rows (csrc/fid.hip), k in order: a (ra, K), b (rb, K) fp32 (b
+    defaults to a), ia / ib int32 row indices on the device (default: every row in order) -> (n, m) float64.  No synchronisation."""
+    require_gpu()
+    b = a if b is None else b
+    a, lda = _rows(a)
+    b, ldb = _rows(b)
+    assert a.shape[1] == b.shape[1] and a.device == b.device
+    for ix in (ia, ib):
+        assert ix is None or (ix.dtype == torch.int32 and ix.is_cuda and ix.is_contiguous() and ix.dim() == 1 and ix.numel() >= 1)
+    n = a.shape[0] if ia is None else ia.numel()
+    m = b.shape[0] if ib is None else ib.numel()
+    if out is None:
+        out = torch.empty(n, m, dtype=torch.float64, device=a.device)
+    assert out.shape == (n, m) and out.dtype == torch.float64 and out.is_contiguous()
+    call("sgic_gram_f64", _p(a), _cl(lda), _p(ia), a.shape[0], n, _p(b), _cl(ldb), _p(ib), b.shape[0], m, a.shape[1], _p(out), _cl(m))
+    return out
+
+
 def jpeg_encode(rgb_u8, tables, subsampling):
     """baseline JPEG encode of B equal-size images (csrc/jpeg_enc.hip): rgb_u8 (B, H, W, 3) u8, contiguous on the device; tables
     (B, 2, 64) u16 numpy array on the host (luma and chroma quantisation table of every image, natural order); subsampling 0 / 1 / 2
