@@ -392,6 +392,28 @@ int sgic_search_range_f32q(const float *d_q, const uint8_t *d_db, const float *d
                            int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,
                            float *d_out_score, sgic_stream_t stream);
 
+/* Rank of a target row (CodeIndex.rank / rank_vectors, search.py recall): for query q and database row t = d_target[q], with the
+ * ranking key of sgic_search_codes_u8 (float32(N) * r_d), resp. of sgic_search_codes_f32q (float32(M) * r_d),
+ *   d_rank[q]  = #{ d in [0, n) : key(q, d) > key(q, t)  or  (key(q, d) == key(q, t) and d < t) }
+ *   d_score[q] = key(q, t) * r_q, resp. key(q, t) * 2^-22: the fp32 bits the top-k entry point reports for the pair,
+ * so d_rank is the position of t in the full ordering the top-k search truncates at k: for every k, d_rank[q] < k exactly when t is
+ * among the k results, and then out_idx[q][d_rank[q]] == t and out_scores[q][d_rank[q]] has the bits of d_score[q].  A pre-pass
+ * computes the target's integer N / M in plain integer code (it is exact, so it is the scan's integer) and takes it through the
+ * scan's one conversion and one multiply; the scan keeps integer counters and combines them with integer adds only (registers,
+ * shuffles, LDS, one 32-bit atomic add per query and workgroup), so two runs give equal bits.  No candidate buffers, no merge.
+ * d_target (nq) int32 is read on the DEVICE: the call cannot refuse a target outside [0, n), it clamps it into the range for the
+ * loads and the outputs of that query then describe the clamped row.  Callers check the range first (ops.search_codes_rank does).
+ * d_q, d_rq, d_db, d_rdb, D and `splits` as in sgic_search_codes_u8 / _f32q (D % 64 == 0; D <= 4096, fp32 queries D <= 2048);
+ * d_work: 4-byte aligned, sgic_search_rank_work_bytes bytes (host-only, takes no stream: nq * 4, the target keys).  A null
+ * pointer, nq < 1, n < 1, a bad D, splits > 2048, a misaligned pointer or a workspace that is too small is SGIC_EINVAL before any
+ * launch: the outputs stay untouched. */
+int sgic_search_rank_work_bytes(int nq, size_t *bytes);
+int sgic_search_rank_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb, const int32_t *d_target,
+                        int nq, int n, int D, int splits, uint8_t *d_work, size_t work_bytes, int32_t *d_rank, float *d_score,
+                        sgic_stream_t stream);
+int sgic_search_rank_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, const int32_t *d_target, int nq, int n, int D,
+                          int splits, uint8_t *d_work, size_t work_bytes, int32_t *d_rank, float *d_score, sgic_stream_t stream);
+
 /* Clustering over the same u8 codes (CodeIndex.assign / kmeans): for every database row the best of K fp32 centroids.  d_cent
  * (K, D) fp32 rows of norm <= 1 and d_db (n, D) u8, both 16-byte aligned.  The centroid goes to 2^-22 fixed point and three balanced
  * base-256 digit planes exactly as the query of sgic_search_codes_f32q (Q, d0, d1, d2, S_p and the int64

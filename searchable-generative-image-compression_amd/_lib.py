@@ -86,7 +86,7 @@ def ptr(t):
 
 _NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profiler_create", "sgic_profiler_begin", "sgic_profiler_end",
               "sgic_clip_preprocess_ragged_workspace", "sgic_clip_preprocess_u8canvas_workspace", "sgic_search_codes_u8_work_bytes",
-              "sgic_search_codes_f32q_work_bytes", "sgic_assign_codes_f32c_work_bytes", "sgic_quality_u8_work_bytes", "sgic_jpeg_encode_cap",
+              "sgic_search_codes_f32q_work_bytes", "sgic_search_rank_work_bytes", "sgic_assign_codes_f32c_work_bytes", "sgic_quality_u8_work_bytes", "sgic_jpeg_encode_cap",
               "sgic_jpeg_encode_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes"}
 
 

@@ -23,7 +23,8 @@
 // candidate buffers at k = 128 take 120 KiB of the CU's 160 KiB of LDS, D = 4096 would not fit.
 //
 // The two query types (U8Query, F32Query) own the prologue, the step loop and the integer of a score; what happens to a score is
-// one of two kernels, each compiled for both: search_topk_kernel (candidate buffers) and search_range_kernel (append to a list).
+// one of three kernels, each compiled for both: search_topk_kernel (candidate buffers), search_range_kernel (append to a list) and
+// search_rank_kernel (count the rows that come before one given target row).
 #include <math.h>
 
 #include <type_traits>
@@ -190,6 +191,19 @@ struct U8Query {
   }
 
   static __device__ __forceinline__ float scale(const float *__restrict__ r_q, int gq) { return r_q[gq]; }
+
+  // a lane's share of N for one (query row, database row) pair in plain integer code: the 16-byte chunks lane, lane + 64, ...
+  static __device__ __forceinline__ int pair(const T *__restrict__ q, const uint8_t *__restrict__ d, int D, int lane) {
+    int s = 0;
+    for (int c = lane; c < (D >> 4); c += 64) {
+      const uint4 a = reinterpret_cast<const uint4 *>(q)[c], b = reinterpret_cast<const uint4 *>(d)[c];
+      const unsigned aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 16; j++)
+        s += (2 * (int)((aw[j >> 2] >> (8 * (j & 3))) & 255u) - 255) * (2 * (int)((bw[j >> 2] >> (8 * (j & 3))) & 255u) - 255);
+    }
+    return s;
+  }
 };
 
 // No byte sums of the database rows are needed (v_d = 2 a_d + 1 turns into the `+ sum Q` term), and no self-join: fp32 queries are
@@ -248,6 +262,26 @@ struct F32Query {
   }
 
   static __device__ __forceinline__ float scale(const float *__restrict__, int) { return 1.0f / kQScale; }
+
+  // a lane's share of M for one (query row, database row) pair in plain integer code, from the digits quantise16 makes
+  static __device__ __forceinline__ long long pair(const T *__restrict__ q, const uint8_t *__restrict__ d, int D, int lane) {
+    long long m = 0;
+    for (int c = lane; c < (D >> 4); c += 64) {
+      v4i p0, p1, p2;
+      const int sumq = quantise16(reinterpret_cast<const float4 *>(q + 16 * c), p0, p1, p2);
+      const v4i b = to_i8x16(reinterpret_cast<const uint4 *>(d)[c]);
+      int s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const int sh = 8 * (j & 3), a = (signed char)(b[j >> 2] >> sh);
+        s0 += (signed char)(p0[j >> 2] >> sh) * a;
+        s1 += (signed char)(p1[j >> 2] >> sh) * a;
+        s2 += (signed char)(p2[j >> 2] >> sh) * a;
+      }
+      m += 2 * (65536LL * s2 + 256LL * s1 + s0) + sumq;
+    }
+    return m;
+  }
 };
 
 // Top-k: r_q is read for u8 queries only (fp32 queries pass nullptr).  LDS: the query tile, the candidate buffers, then the sums.
@@ -483,6 +517,105 @@ __global__ __launch_bounds__(256, 4) void search_range_kernel(const typename Que
   }
 }
 
+// Rank of a target row: search_topk_kernel's tiles, integer score and tie rule, no candidates.  For query q with target row t
+//   rank(q, t) = #{ d in [0, n) : beats(key(q, d), d, key(q, t), t) },
+// the position of t in the full ordering the top-k search truncates at k.  search_rank_target_kernel (one wave per query) computes
+// the pair's integer in plain integer code -- N and M are exact, so any route to them gives the same integer -- and takes it
+// through the scan's float step (one conversion, one multiply): the key goes to the workspace, key * scale to d_score, and d_rank
+// is zeroed.  search_rank_kernel then keeps one int32 counter per (fragment, register) in every lane over the whole scan of its
+// split; at the end the sixteen lanes of a query are summed by shuffles, the four waves through LDS, and a workgroup with a
+// non-zero count takes one global atomic add per query.  Integer adds only: the result does not depend on the schedule.  Targets
+// are clamped into [0, n) for the loads (the callers refuse others); query rows >= nq and database rows >= row_end are clamped
+// and masked as in the other sinks.  LDS: the query tile, its sums, one counter per query.
+template <class Query>
+__global__ __launch_bounds__(256) void search_rank_target_kernel(const typename Query::T *__restrict__ q, const float *__restrict__ r_q,
+                                                                 const uint8_t *__restrict__ db, const float *__restrict__ r_db,
+                                                                 const int *__restrict__ target, int nq, int n, int D,
+                                                                 float *__restrict__ tkey, int *__restrict__ rank,
+                                                                 float *__restrict__ score) {
+  const int lane = threadIdx.x & 63, gq = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (gq >= nq) return;
+  int t = target[gq];
+  t = t < 0 ? 0 : (t < n ? t : n - 1);
+  auto N = Query::pair(q + (size_t)gq * D, db + (size_t)t * D, D, lane);
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) N += __shfl_xor(N, m);
+  if (lane == 0) {
+    const float key = (float)N * r_db[t];
+    tkey[gq] = key;
+    rank[gq] = 0;
+    score[gq] = key * Query::scale(r_q, gq);
+  }
+}
+
+template <class Query, int QF, int U>
+__global__ __launch_bounds__(256, 4) void search_rank_kernel(const typename Query::T *__restrict__ q, const uint8_t *__restrict__ db,
+                                                             const float *__restrict__ r_db, const int *__restrict__ target,
+                                                             const float *__restrict__ tkey, int nq, int n, int D, int rows_per_split,
+                                                             int *__restrict__ rank) {
+  constexpr int QT = 16 * QF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  v4i *A = reinterpret_cast<v4i *>(smem);
+  typename Query::Sum *sq = reinterpret_cast<typename Query::Sum *>(smem + (size_t)Query::kPlanes * QT * D);
+  int *wcnt = reinterpret_cast<int *>(sq + QT);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qbase = blockIdx.x * QT, split = blockIdx.y;
+  const int row0 = split * rows_per_split;
+  const int row_end = (n - row0 < rows_per_split) ? n : row0 + rows_per_split;
+
+  if (tid < QT) wcnt[tid] = 0;   // stage() has the barriers
+  Query::template stage<QF>(q, nq, qbase, D, tid, A, sq);
+
+  typename Query::Term tq[QF][4];
+  float tk[QF][4];
+  int tt[QF][4], cnt[QF][4];
+  const int gq0 = qbase + 4 * (lane >> 4);   // this lane's query of (f, r) is gq0 + 16 f + r
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      int gq = gq0 + 16 * f + r;
+      gq = gq < nq ? gq : nq - 1;
+      const int t = target[gq];
+      tq[f][r] = Query::term(sq, f * 16 + 4 * (lane >> 4) + r, D);
+      tk[f][r] = tkey[gq];
+      tt[f][r] = t < 0 ? 0 : (t < n ? t : n - 1);
+      cnt[f][r] = 0;
+    }
+
+  for (int base = row0; base < row_end; base += kCandPerIter) {
+    const int my = base + wave * 16 + (lane & 15);
+    v4i acc[Query::kPlanes][QF];   // zeroed here, not in accumulate(): through its reference that costs registers (an occupancy step)
+#pragma unroll
+    for (int p = 0; p < Query::kPlanes; p++)
+#pragma unroll
+      for (int f = 0; f < QF; f++) acc[p][f] = v4i{0, 0, 0, 0};
+    const int myc = my < n ? my : n - 1;   // rows >= n are clamped for the loads and masked below
+    const uint4 *bp = reinterpret_cast<const uint4 *>(db + (size_t)myc * D) + (lane >> 4);
+    const int td = Query::template accumulate<QF, U>(A, bp, D, lane, acc);
+    const float rd = r_db[myc];
+    const bool valid = my < row_end;
+#pragma unroll
+    for (int f = 0; f < QF; f++)
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        cnt[f][r] += (valid && beats(Query::key(acc, f, r, tq[f][r], td, rd), my, tk[f][r], tt[f][r])) ? 1 : 0;
+  }
+
+#pragma unroll
+  for (int f = 0; f < QF; f++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      int c = cnt[f][r];
+#pragma unroll
+      for (int m = 1; m < 16; m <<= 1) c += __shfl_xor(c, m);   // the sixteen database columns of this query
+      if ((lane & 15) == 0 && c) atomicAdd(&wcnt[f * 16 + 4 * (lane >> 4) + r], c);
+    }
+  __syncthreads();
+  if (tid < QT && qbase + tid < nq && wcnt[tid]) atomicAdd(&rank[qbase + tid], wcnt[tid]);
+}
+
 struct Plan {
   int qf, qtiles, splits, rows_per_split;
   size_t lds, work_bytes;
@@ -590,7 +723,48 @@ int search_topk(const Plan &p, const typename Query::T *d_q, const float *d_rq, 
   return SGIC_OK;
 }
 
+// the pre-pass (target keys into the workspace, scores, zeroed ranks), then the scan
+template <class Query>
+int search_rank(int nq, int n, int D, int splits, bool f32q, const typename Query::T *d_q, const float *d_rq, const uint8_t *d_db,
+                const float *d_rdb, const int32_t *d_target, uint8_t *d_work, size_t work_bytes, int32_t *d_rank, float *d_score,
+                sgic_stream_t stream) {
+  Plan p;
+  const int rc = make_plan(nq, n, D, 0, splits, f32q, &p);
+  if (rc != SGIC_OK) return rc;
+  SGIC_REQUIRE(d_q && (f32q || d_rq) && d_db && d_rdb && d_target && d_work && d_rank && d_score, "null pointer");
+  SGIC_REQUIRE(((uintptr_t)d_q | (uintptr_t)d_db) % 16 == 0 && (uintptr_t)d_work % 4 == 0, "queries and codes must be 16-byte aligned");
+  SGIC_REQUIRE(work_bytes >= (size_t)nq * 4, "workspace (sgic_search_rank_work_bytes)");
+  p.lds += (size_t)16 * p.qf * sizeof(int);   // the per-query counters
+  hipStream_t st = to_stream(stream);
+  float *tkey = reinterpret_cast<float *>(d_work);
+  search_rank_target_kernel<Query><<<cdiv((size_t)nq, 4), 256, 0, st>>>(d_q, d_rq, d_db, d_rdb, d_target, nq, n, D, tkey, d_rank, d_score);
+  const int prc = sgic::check_launch("search_rank_target_kernel");
+  if (prc != SGIC_OK) return prc;
+  return dispatch<Query>(p, D, [&](auto qf, auto u) {
+    return launch<search_rank_kernel<Query, qf, u>>(p, "search_rank_kernel", st, d_q, d_db, d_rdb, d_target, tkey, nq, n, D,
+                                                   p.rows_per_split, d_rank);
+  });
+}
+
 }  // namespace
+
+extern "C" int sgic_search_rank_work_bytes(int nq, size_t *bytes) {
+  SGIC_REQUIRE(nq > 0 && bytes, "sizes");
+  *bytes = (size_t)nq * 4;   // one target key per query
+  return SGIC_OK;
+}
+
+extern "C" int sgic_search_rank_u8(const uint8_t *d_q, const float *d_rq, const uint8_t *d_db, const float *d_rdb,
+                                   const int32_t *d_target, int nq, int n, int D, int splits, uint8_t *d_work, size_t work_bytes,
+                                   int32_t *d_rank, float *d_score, sgic_stream_t stream) {
+  return search_rank<U8Query>(nq, n, D, splits, false, d_q, d_rq, d_db, d_rdb, d_target, d_work, work_bytes, d_rank, d_score, stream);
+}
+
+extern "C" int sgic_search_rank_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, const int32_t *d_target, int nq, int n,
+                                     int D, int splits, uint8_t *d_work, size_t work_bytes, int32_t *d_rank, float *d_score,
+                                     sgic_stream_t stream) {
+  return search_rank<F32Query>(nq, n, D, splits, true, d_q, nullptr, d_db, d_rdb, d_target, d_work, work_bytes, d_rank, d_score, stream);
+}
 
 extern "C" int sgic_search_range_f32q(const float *d_q, const uint8_t *d_db, const float *d_rdb, int nq, int n, int D, float threshold,
                                       int splits, long long capacity, uint64_t *d_count, int32_t *d_out_q, int32_t *d_out_d,

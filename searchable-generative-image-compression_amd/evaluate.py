@@ -30,6 +30,17 @@
                                                                 --fid_patch 0: whole images); P: state dict file(s) of the Inception
                                                                 (torchvision's or pytorch-fid's keys, fid.load_weights).  The
                                                                 per-image lines do not change
+  evaluate.py ... --clip_ckpt P                                 retrieval fidelity: adds "clip_sim" to every record (and to its
+                                                                anchor), the cosine between the CLIP image tower's vectors of the
+                                                                original and of the reconstruction, and "clip_sim", "clip_recall@1",
+                                                                "clip_recall@5", "clip_recall@10", "clip_mrr", "clip_median_rank" to
+                                                                the summary ("anchor_clip_*" with an anchor): every reconstruction
+                                                                searches the u8 codes of all evaluated originals for its own original
+                                                                (search.CodeIndex.rank_vectors).  With --bitstreams also
+                                                                "clip_code_match" per record and "clip_code_mismatch" in the summary:
+                                                                whether the code in the container is the code P gives the original.
+                                                                P: the state dict compress.py --clip_ckpt takes (--small: the TINY
+                                                                tower)
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -74,9 +85,10 @@ def _json_number(v):
     return ("inf" if v > 0 else "-inf") if math.isinf(v) else v
 
 
-def summarise(records, fid_sets=None):
+def summarise(records, fid_sets=None, clip_sets=None):
     """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
-    lpips, lpips_alex and dists when the records carry them; fid_sets (FidSets, --fid_ckpt): its keys after all the others"""
+    lpips, lpips_alex and dists when the records carry them; clip_sets (ClipSets, --clip_ckpt): its keys after the perceptual means
+    (the anchor's after the anchor's); fid_sets (FidSets, --fid_ckpt): its keys after all the others"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
@@ -90,6 +102,11 @@ def summarise(records, fid_sets=None):
         out["lpips_alex"] = mean([r["lpips_alex"] for r in records if r.get("lpips_alex") is not None])
     if any("dists" in r for r in records):
         out["dists"] = mean([r["dists"] for r in records if r.get("dists") is not None])
+    if clip_sets is not None:
+        out["clip_sim"] = mean([r["clip_sim"] for r in records])
+        out.update(clip_sets.summary("recon", records, "clip_"))
+        if any("clip_code_match" in r for r in records):
+            out["clip_code_mismatch"] = sum(1 for r in records if r.get("clip_code_match") is False)
     anchors = [r["anchor"] for r in records if "anchor" in r]
     if anchors:      # the same means over the anchors; over_rate counts the images whose smallest JPEG is larger than the container
         ams = mean([a["ms_ssim"] for a in anchors if a["ms_ssim"] is not None])
@@ -104,6 +121,9 @@ def summarise(records, fid_sets=None):
             out["anchor_lpips_alex"] = mean([a["lpips_alex"] for a in anchors if a.get("lpips_alex") is not None])
         if any("dists" in a for a in anchors):
             out["anchor_dists"] = mean([a["dists"] for a in anchors if a.get("dists") is not None])
+        if clip_sets is not None:
+            out["anchor_clip_sim"] = mean([a["clip_sim"] for a in anchors])
+            out.update(clip_sets.summary("anchor", [r for r in records if "anchor" in r], "anchor_clip_"))
     if fid_sets is not None:
         out.update(fid_sets.summary())
     return out
@@ -150,6 +170,57 @@ class FidSets:
             f, k, k_std = self._pair(self.orig, self.anchor)
             out.update({"anchor_fid": f, "anchor_kid": k, "anchor_kid_std": k_std})
         return out
+
+
+class ClipSets:
+    """--clip_ckpt: the CLIP image tower over the u8 tensors the other measures see.  Every original gives a unit vector and the u8
+    code of it (ClipCodec.u8_to_codes: the decoded bytes as they are, the route of `search.py build-images`), every reconstruction and
+    decoded anchor a unit vector; they are kept per image name, and at the end the reconstructions (anchors) search the codes of all
+    originals for their own (search.CodeIndex.rank_vectors, the rank kernel).  stored_route_codes: the code compress.py writes into
+    a container, which goes through the fp32 image (ClipCodec.batch_to_codes on u / 255 * 2 - 1) -- what a container's
+    code is compared with"""
+
+    def __init__(self, ckpt, small, device):
+        from . import weights as W
+        from .codec import ClipCodec
+        from .compress import load_state
+        from .config import CLIP_B32, CLIP_TINY
+        ccfg = CLIP_TINY if small else CLIP_B32
+        csd = load_state(ckpt, W.clip_spec, ccfg, 4321)
+        if ckpt and not any(k.startswith("clip.") for k in csd):
+            csd = {f"clip.{k}": v for k, v in csd.items()}
+        self.clipc = ClipCodec(csd, ccfg, device)
+        self.codes, self.units = {}, {"recon": {}, "anchor": {}}
+
+    def embed(self, images):
+        """(B, H, W, 3) u8 on the device -> (unit (B, D) fp32, codes (B, D) u8), both on the host"""
+        B, H, W, _ = images.shape
+        unit, codes = self.clipc.u8_to_codes(images.contiguous(), np.array([(H, W)] * B, dtype=np.int64))
+        return unit.cpu().numpy(), codes.cpu().numpy()
+
+    def stored_route_codes(self, images):
+        from . import ops
+        B, H, W, _ = images.shape
+        return self.clipc.batch_to_codes(ops.u8hwc_to_f32chw_pad(images.contiguous()), H, W)[1].cpu().numpy()
+
+    @staticmethod
+    def cosine(u, v):
+        """fp64 cosine per row of two (B, D) fp32 arrays"""
+        u, v = u.astype(np.float64), v.astype(np.float64)
+        return (u * v).sum(axis=1) / (np.sqrt((u * u).sum(axis=1)) * np.sqrt((v * v).sum(axis=1)))
+
+    def summary(self, which, records, prefix):
+        """the queries of set `which` for `records` against the codes of ALL evaluated originals, rows in name order"""
+        from .search import CodeIndex, retrieval_summary
+        names = sorted(self.codes)
+        row = {n: j for j, n in enumerate(names)}
+        asked = [r["name"] for r in records]
+        if not asked:
+            return {}
+        ci = CodeIndex(np.stack([self.codes[n] for n in names]), names)
+        rank, score = ci.rank_vectors(np.stack([self.units[which][n] for n in asked]), np.array([row[n] for n in asked], dtype=np.int64))
+        s = retrieval_summary(rank, score, (1, 5, 10))
+        return {prefix + k: s[k] for k in ("recall@1", "recall@5", "recall@10", "mrr", "median_rank")}
 
 
 def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None, lpips_alex_model=None,
@@ -217,6 +288,9 @@ def main(argv=None):
                     help="state dict file(s) with the VGG16 trunk and alpha, beta of DISTS: adds \"dists\" to every record")
     ap.add_argument("--fid_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) of the Inception-v3 of FID: adds \"fid\", \"kid\", \"kid_std\" to the summary")
+    ap.add_argument("--clip_ckpt", type=str, default=None,
+                    help="state dict of the CLIP image tower (as compress.py --clip_ckpt): adds \"clip_sim\" to every record and the "
+                         "retrieval figures clip_recall@k, clip_mrr, clip_median_rank to the summary")
     ap.add_argument("--fid_patch", type=int, default=256,
                     help="side of the windows FID and KID are computed on (the HiFiC protocol); 0: whole images")
     args = ap.parse_args(argv)
@@ -250,6 +324,7 @@ def main(argv=None):
         from .dists import DistsVGG
         dists_model = DistsVGG(args.dists_ckpt, dev)
     fid_sets = FidSets(args.fid_ckpt, args.fid_patch, dev) if args.fid_ckpt else None
+    clip_sets = ClipSets(args.clip_ckpt, args.small, dev) if args.clip_ckpt else None
     originals = by_stem(glob(os.path.join(args.originals, "*.*")))
     containers = by_stem(glob(os.path.join(args.bitstreams, "*.c2df"))) if args.bitstreams else {}
     recons = by_stem(glob(os.path.join(args.recon_dir, "*.*"))) if args.recon_dir else None
@@ -285,9 +360,18 @@ def main(argv=None):
             la = lpips_alex_model.measure(a, b) if lpips_alex_model is not None else None
             ds = dists_model.measure(a, b) if dists_model is not None else None
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
-            decoded = [] if fid_sets is not None else None
+            decoded = [] if fid_sets is not None or clip_sets is not None else None
             anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model,
                                    lpips_alex_model, decoded) if anchor else None
+            if clip_sets is not None:
+                from .search import embedded_clip_codes
+                ua, qa = clip_sets.embed(a)
+                ub, _ = clip_sets.embed(b)
+                sim = clip_sets.cosine(ua, ub)
+                stored = clip_sets.stored_route_codes(a) if containers else None
+                if anchor:
+                    uj, _ = clip_sets.embed(decoded[0])
+                    asim = clip_sets.cosine(ua, uj)
             desc = fid_sets.windows(a) if fid_sets is not None else None
             if desc is not None:
                 fid_sets.add("orig", a, desc)
@@ -305,6 +389,19 @@ def main(argv=None):
                     rec["lpips_alex"] = None if la is None else float(la[0][j])
                 if dists_model is not None:
                     rec["dists"] = None if ds is None else float(ds[0][j])
+                if clip_sets is not None:
+                    rec["clip_sim"] = float(sim[j])
+                    clip_sets.codes[stem], clip_sets.units["recon"][stem] = qa[j], ub[j]
+                    if containers:      # is --clip_ckpt the tower the archive was written with?
+                        try:
+                            rec["clip_code_match"] = bool(np.array_equal(embedded_clip_codes(containers[stem])[0], stored[j]))
+                        except Exception:   # noqa: BLE001 -- no container for this image, or one without a code
+                            rec["clip_code_match"] = None
+                    if anchors:
+                        over = anchors[j].pop("over_rate")
+                        anchors[j]["clip_sim"] = float(asim[j])
+                        anchors[j]["over_rate"] = over
+                        clip_sets.units["anchor"][stem] = uj[j]
                 if anchors:
                     rec["anchor"] = anchors[j]
                 records.append(rec)
@@ -354,7 +451,7 @@ def main(argv=None):
                     measure_chunk(chunk, pending)
 
     records.sort(key=lambda r: r["name"])
-    summary = json.dumps(summarise(records, fid_sets))
+    summary = json.dumps(summarise(records, fid_sets, clip_sets))
     lines = [json.dumps(r) for r in records]
     if args.out:
         with open(args.out, "w") as f:

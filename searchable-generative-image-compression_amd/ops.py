@@ -1164,6 +1164,49 @@ def search_codes_range_f32q(q, db_codes, r_db, threshold, capacity=None, splits=
     return _range_collect(launch_into, q.shape[0], db_codes.shape[0], db_codes.device, threshold, capacity, max_pairs)
 
 
+def _search_rank(q, r_q, db_codes, r_db, targets, splits):
+    """sgic_search_rank_u8, or with r_q None sgic_search_rank_f32q: the checks, the workspace and the call.  The ABI reads the
+    targets on the device and cannot refuse them, so their length and range are checked here, before the launch"""
+    require_gpu()
+    if not isinstance(targets, torch.Tensor):
+        targets = torch.from_numpy(np.ascontiguousarray(np.asarray(targets).reshape(-1), dtype=np.int64))
+    if targets.dim() != 1 or targets.shape[0] != q.shape[0]:
+        raise ValueError(f"{tuple(targets.shape)} targets for {q.shape[0]} queries: one target row per query is needed")
+    if targets.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"targets must be int32 or int64 row indices, got {targets.dtype}")
+    n = db_codes.shape[0]
+    if targets.numel():
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(targets)).tolist())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"targets span [{lo}, {hi}], outside the {n} rows [0, {n}) of the database")
+    targets = targets.to(device=db_codes.device, dtype=torch.int32).contiguous()
+    nq, n, D = _search_inputs(q, r_q, db_codes, r_db, ((targets, torch.int32),))
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_search_rank_work_bytes", nq, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=db_codes.device)
+    rank = torch.empty(nq, dtype=torch.int32, device=db_codes.device)
+    score = torch.empty(nq, dtype=torch.float32, device=db_codes.device)
+    call("sgic_search_rank_f32q" if r_q is None else "sgic_search_rank_u8", _p(q), *(() if r_q is None else (_p(r_q),)), _p(db_codes),
+         _p(r_db), _p(targets), nq, n, D, 0 if splits is None else int(splits), _p(work), ctypes.c_size_t(nbytes.value), _p(rank), _p(score))
+    return rank, score
+
+
+def search_codes_rank(q_codes, r_q, db_codes, r_db, targets, splits=0):
+    """rank of one target row per query over u8 codes (csrc/search.hip, search_rank_kernel): inputs as for search_codes, `targets`
+    (nq,) row indices (a tensor on either side, or an array) -> (rank (nq,) int32, score (nq,) fp32) on the device.  rank = the
+    number of rows that search_codes orders before the target (higher key, or equal key and lower index), i.e. the target's
+    position in the full result list; score = the fp32 bits search_codes reports for the pair.  Targets of another length or
+    outside [0, n) are a ValueError before the launch (range check of a device tensor: one read-back; host targets: none).  No
+    synchronisation otherwise; `splits` forces the number of database splits (tests)."""
+    return _search_rank(q_codes, r_q, db_codes, r_db, targets, splits)
+
+
+def search_codes_rank_f32q(q, db_codes, r_db, targets, splits=0):
+    """search_codes_rank for fp32 queries (F32Query): inputs as for search_codes_f32q (D % 64 == 0, D <= 2048), the order and the
+    score bits those of search_codes_f32q -> (rank (nq,) int32, score (nq,) fp32) on the device."""
+    return _search_rank(q, None, db_codes, r_db, targets, splits)
+
+
 def assign_codes(centroids, db_codes, r_db, return_int=False):
     """for every row of the u8 codes the best of K fp32 centroids (csrc/search.hip, assign_codes_kernel): centroids (K, D) fp32 rows
     of norm <= 1, db_codes (n, D) u8, r_db (n,) fp32 (search.code_rnorm), all contiguous on one device -> (cluster (n,) int32, score

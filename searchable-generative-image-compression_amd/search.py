@@ -18,7 +18,10 @@ score, exact integer sums per cluster, the corpus never leaving its one byte per
 representative and best members.
 `build-images` (the reference's `build.py build-images`) indexes a folder of ordinary images with the CLIP tower alone: no codec, no
 container.  The decoded bytes go to the tower as they are (clip.py preprocess_u8), and the index directory carries the same files
-as `build`, the tower's own u8 codes included."""
+as `build`, the tower's own u8 codes included.
+`recall --index_dir CORPUS --queries_dir QUERIES` measures retrieval between two index directories: every query row is paired
+with the corpus row of the same file stem, the rank kernel (csrc/search.hip, search_rank_kernel) gives the position of that row
+in the query's full result list, and one JSON line reports recall@k, MRR and the mean / median rank."""
 import argparse
 import json
 import os
@@ -215,6 +218,49 @@ def cluster_report(assign, score):
     return out
 
 
+def retrieval_summary(rank, score, ks=(1, 5, 10)):
+    """what a set of target ranks says about retrieval, in fp64: rank (nq,) the 0-based position of each query's target in the
+    full result list (CodeIndex.rank), score (nq,) the pairs' scores -> {"queries", "recall@k" for every k of ks, "mrr",
+    "mean_rank", "median_rank", "mean_score"}.  recall@k: the share of rank < k; mrr: the mean of 1 / (rank + 1); the median of
+    an even count is the mean of the two middle ranks.  No queries: "queries" is 0 and everything else None"""
+    rank, score = np.asarray(rank).reshape(-1), np.asarray(score).reshape(-1)
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError(f"recall@k needs k >= 1, got {ks}")
+    if rank.shape != score.shape:
+        raise ValueError(f"{rank.size} ranks and {score.size} scores")
+    if rank.size and int(rank.min()) < 0:
+        raise ValueError(f"ranks are positions >= 0, got {int(rank.min())}")
+    out = {"queries": int(rank.size)}
+    r = rank.astype(np.float64)
+    for k in ks:
+        out[f"recall@{k}"] = float(np.mean(rank < k)) if rank.size else None
+    out["mrr"] = float(np.mean(1.0 / (r + 1.0))) if rank.size else None
+    out["mean_rank"] = float(np.mean(r)) if rank.size else None
+    out["median_rank"] = float(np.median(r)) if rank.size else None
+    out["mean_score"] = float(np.mean(score.astype(np.float64))) if rank.size else None
+    return out
+
+
+def pair_by_stem(query_ids, corpus_ids):
+    """the pairing of `recall`: a query row belongs to the corpus row whose id has the same file stem (the name without
+    directories and without its last extension) -> (query rows int64, target rows int64, unmatched query count).  Two corpus ids
+    with one stem would make the target ambiguous: a ValueError that names them"""
+    rows = {}
+    for j, cid in enumerate(corpus_ids):
+        stem = Path(cid).stem
+        if stem in rows:
+            raise ValueError(f"corpus ids {corpus_ids[rows[stem]]!r} and {cid!r} share the stem {stem!r}: the target of a query of that name is ambiguous")
+        rows[stem] = j
+    qrows, targets = [], []
+    for i, qid in enumerate(query_ids):
+        j = rows.get(Path(qid).stem)
+        if j is not None:
+            qrows.append(i)
+            targets.append(j)
+    return np.asarray(qrows, dtype=np.int64), np.asarray(targets, dtype=np.int64), len(query_ids) - len(qrows)
+
+
 class CodeIndex:
     """an index of the u8 CLIP codes themselves: `codes` (n, D) u8, `ids` [n].  Searched with the fused i8 kernel
     (ops.search_codes) for u8 query codes and with its fp32-query sibling (ops.search_codes_f32q) for text / image vectors: scores
@@ -322,6 +368,47 @@ class CodeIndex:
         k = max(1, min(int(k), len(self)))
         s, i = ops.search_codes_f32q(t.to(db.device).contiguous(), db, r_db, k)
         return s.cpu().numpy(), i.cpu().numpy()
+
+    def _targets(self, targets, nq):
+        """one row of the index per query, checked on the host before anything is loaded or launched -> (nq,) int32"""
+        t = np.asarray(targets)
+        if t.ndim != 1 or t.shape[0] != nq or not (np.issubdtype(t.dtype, np.integer) or t.size == 0):
+            raise ValueError(f"targets of shape {t.shape} ({t.dtype}) for {nq} queries: one integer row index per query is needed")
+        if t.size and (int(t.min()) < 0 or int(t.max()) >= len(self)):
+            raise ValueError(f"targets span [{int(t.min())}, {int(t.max())}], outside the {len(self)} rows of the index")
+        return t.astype(np.int32)
+
+    def rank(self, q_codes, targets):
+        """where each query's target row stands in the full result list of `search`: q_codes (nq, D) u8, targets (nq,) rows of
+        the index -> (rank (nq,) int32, score (nq,) fp32).  rank = the number of rows `search` orders before the target (higher
+        score key, or the same key and a lower index), so rank < k exactly when the target is among the k results; score = the
+        bits `search` reports for the pair.  One fused launch over all rows (ops.search_codes_rank), no top-k limit"""
+        from . import ops
+        q = np.ascontiguousarray(np.atleast_2d(q_codes), dtype=np.uint8)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query codes of dim {q.shape[1]} against an index of dim {self.dim}")
+        t = self._targets(targets, q.shape[0])
+        if q.shape[0] == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32)
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        r, s = ops.search_codes_rank(torch.from_numpy(q).to(db.device), torch.from_numpy(code_rnorm(q)).to(db.device), db, r_db, t)
+        return r.cpu().numpy(), s.cpu().numpy()
+
+    def rank_vectors(self, q, targets):
+        """`rank` for fp32 unit queries: q as for search_vectors (and refused like there), the order and the score bits those of
+        `search_vectors` -> (rank (nq,) int32, score (nq,) fp32)"""
+        from . import ops
+        v = self._unit_queries(q, "rank_vectors")
+        t = self._targets(targets, v.shape[0])
+        if v.shape[0] == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32)
+        if self._dev is None:
+            self.to()
+        db, r_db = self._dev
+        r, s = ops.search_codes_rank_f32q(v.to(db.device).contiguous(), db, r_db, t)
+        return r.cpu().numpy(), s.cpu().numpy()
 
     def range_search_vectors(self, q, threshold, max_pairs=None):
         """every database row whose score against an fp32 unit query is >= threshold (fp32, the bits `search_vectors` reports), the
@@ -728,6 +815,53 @@ def write_clusters(index_dir, k, iters=10, seed=0, members=20, save_dir=None, ou
     return res
 
 
+def _missing_index_files(index_dir, vectors):
+    """what `recall` needs of an index directory and does not find -> message or None, without reading a file"""
+    root = Path(index_dir)
+    if vectors:
+        if not any((root / a).exists() and (root / b).exists() for a, b, _ in _INDEX_LAYOUTS):
+            return f"no FAISS index in {root}: expected " + " or ".join(f"{a} + {b}" for a, b, _ in _INDEX_LAYOUTS)
+    elif not (root / "codes.npy").exists() or not (root / "ids.txt").exists():
+        return f"no code index in {root}: expected codes.npy + ids.txt (sub-commands `build` / `build-images`)"
+    return None
+
+
+def write_recall(index_dir, queries_dir, vectors=False, ks=(1, 5, 10), out=None):
+    """`recall`: how well the rows of one index directory (the queries) find their partners in another (the corpus).  A query row
+    is paired with the corpus row whose id has the same file stem (pair_by_stem); queries without a partner are counted and left
+    out.  Default: the queries' u8 codes (codes.npy) through CodeIndex.rank; vectors: their fp32 vectors (load_index) through
+    CodeIndex.rank_vectors.  Prints one JSON line, retrieval_summary plus "corpus", "unmatched", "policy"; `out`: one JSON line
+    per matched query {"query", "target", "rank", "score"}, in query order.  -> the summary"""
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError(f"recall@k needs k >= 1, got {ks}")
+    for d, v in ((index_dir, False), (queries_dir, vectors)):      # both directories, before a file of either is read
+        why = _missing_index_files(d, v)
+        if why:
+            raise FileNotFoundError(why)
+    ci = CodeIndex.load(index_dir)
+    if vectors:
+        q, qids = load_index(queries_dir)
+    else:
+        qi = CodeIndex.load(queries_dir)
+        q, qids = qi.codes, qi.ids
+    if q.shape[1] != ci.dim:
+        raise ValueError(f"queries of dim {q.shape[1]} ({queries_dir}) against a corpus of dim {ci.dim} ({index_dir})")
+    qrows, targets, unmatched = pair_by_stem(qids, ci.ids)
+    if qrows.size:
+        rank, score = (ci.rank_vectors if vectors else ci.rank)(q[qrows], targets)
+    else:
+        rank, score = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32)
+    if out:
+        with open(out, "w", encoding="utf-8") as fh:
+            for i, t, r, s in zip(qrows.tolist(), targets.tolist(), rank.tolist(), score.tolist()):
+                fh.write(json.dumps({"query": qids[i], "target": ci.ids[t], "rank": r, "score": s}, ensure_ascii=False) + "\n")
+    rec = retrieval_summary(rank, score, ks)
+    rec.update({"corpus": len(ci), "unmatched": int(unmatched), "policy": "f32q" if vectors else "u8"})
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 _THRESHOLD_HELP = ("score threshold (cosine of the dequantised codes, fp32).  Measured on quantised unit codes at D = 512: a row scores "
                    "1 +- 2^-23 against itself (so 1.0 can miss it), one code off by one step <= 0.99997, 64 codes off about 0.998, all 512 "
                    "off about 0.985, unrelated rows < 0.2.  About 0.99999 selects identical codes only, 0.98-0.99 re-encodes of one "
@@ -747,7 +881,7 @@ _MAX_PAIRS_HELP = "with --min_score: refuse (and name the count) when more hits 
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours / duplicates / clusters")
+    ap = argparse.ArgumentParser(description="query-text / query-image / query-c2df / build / build-images / neighbours / duplicates / clusters / recall")
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name, arg in (("query-text", "--text"), ("query-image", "--image"), ("query-c2df", "--c2df")):
         p = sub.add_parser(name)
@@ -808,7 +942,22 @@ def main(argv=None):
     p.add_argument("--members", type=int, default=20, help="members listed per cluster, best first; -1 lists all")
     p.add_argument("--save_dir", type=Path, default=None, help="also write centroids.npy, assign.npy and clusters.json here")
     p.add_argument("--out", type=Path, default=None)
+    p = sub.add_parser("recall", help="how well the rows of one index directory retrieve their partners (same file stem) in another")
+    p.add_argument("--index_dir", type=Path, required=True, help="the corpus: an index directory with codes.npy + ids.txt")
+    p.add_argument("--queries_dir", type=Path, required=True, help="the queries: another index directory (`build` / `build-images`)")
+    p.add_argument("--vectors", action="store_true", help="take the queries' fp32 vectors (the fp32-query kernel) instead of their u8 codes")
+    p.add_argument("--k", type=int, nargs="+", default=[1, 5, 10], help="the k of the recall@k figures")
+    p.add_argument("--out", type=Path, default=None, help="one JSON line per matched query: query, target, rank, score")
     args = ap.parse_args(argv)
+    if args.cmd == "recall":
+        if any(k < 1 for k in args.k):      # refused before any file is read or kernel launched
+            ap.error(f"--k {' '.join(str(k) for k in args.k)}: every k must be at least 1")
+        for d, v in ((args.index_dir, False), (args.queries_dir, args.vectors)):
+            why = _missing_index_files(d, v)
+            if why:
+                ap.error(why)
+        write_recall(args.index_dir, args.queries_dir, args.vectors, args.k, args.out)
+        return 0
     for flag in ("threshold", "min_score"):      # refused before any file is read or kernel launched
         if getattr(args, flag, None) is not None and not np.isfinite(getattr(args, flag)):
             ap.error(f"--{flag} {getattr(args, flag)}: a finite score is needed")
