@@ -453,6 +453,25 @@ int sgic_quality_u8_work_bytes(int B, int H, int W, size_t *bytes);
 int sgic_quality_u8(const uint8_t *d_a, const uint8_t *d_b, int B, int H, int W, uint8_t *d_work, size_t work_bytes,
                     int64_t *d_sse, double *d_levels, sgic_stream_t stream);
 
+/* The block sums of NIQE for B u8 images (niqe.Niqe, evaluate.py --niqe_params).  d_img is (B, H, W, 3)
+ * interleaved RGB; nbh = H / 96, nbw = W / 96 (integer division) and the top-left 96 nbh x 96 nbw pixels are used.  Luma
+ * Y = 16 + round_half_even((65481 R + 128553 G + 24966 B) / 255000) in integers; the half-size plane is MATLAB's imresize(Y, 0.5)
+ * as int32 numerators over 65536 (taps [-3 -9 29 111 111 29 -9 -3] / 256 along each axis, symmetric extension); both are kept in
+ * d_work.  Per scale and pixel, over the 7 x 7 window with replicated borders and centre value c: the ten class sums
+ * s_k = sum (x - c) and q_k = sum (x - c)^2 (class (a, b), 0 <= a <= b <= 3, by {|di|, |dj|}; exact integers),
+ * m = sum_k w_k s_k, v = sum_k w_k q_k in ascending class order with separate multiply and add, sigma = sqrt(|v - m m|),
+ * mscn = (0 - m) / (sigma + 1).  h_weights: HOST array of the ten class weights w_k = g[3 + a] g[3 + b] of the normalised 7-tap
+ * Gaussian of sigma 7 / 6 (niqe.window_weights), each in (0, 1); they travel as kernel arguments.
+ * d_stats[b][ih][iw][scale][map][5] (fp64): for block (ih, iw) of 96 x 96 (scale 0) or 48 x 48 (scale 1) samples and the maps
+ * n, n roll(n, (0,1)), n roll(n, (1,0)), n roll(n, (1,1)), n roll(n, (1,-1)) (circular inside the block): the count of samples < 0,
+ * the count > 0, the sum of squares of each kind, and the sum of |.|.  d_sharp[b][ih][iw]: the mean of sigma over the scale-0 block.
+ * Three launches whatever B is; reductions in a fixed order, no float atomics: the same input gives the same bits.
+ * d_work: 16-byte aligned, at least the *bytes sgic_niqe_u8_work_bytes returns (host-only, takes no stream).  1 <= B <= 65536,
+ * 96 <= H, W <= 16384; anything else, a null pointer, a misaligned or too small workspace is SGIC_EINVAL before any launch. */
+int sgic_niqe_u8_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_niqe_u8(const uint8_t *d_img, int B, int H, int W, const double *h_weights, uint8_t *d_work, size_t work_bytes,
+                 double *d_stats, double *d_sharp, sgic_stream_t stream);
+
 /* LPIPS with the VGG16 trunk (lpips.LpipsVGG, evaluate.py --lpips_ckpt; the reference's taming/modules/losses/lpips.py): the
  * memory-bound glue around sgic_conv3x3_split3_f32, which runs the thirteen convolutions.  All planes are slice-major (a_packed = 1).
  *

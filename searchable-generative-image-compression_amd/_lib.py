@@ -21,6 +21,9 @@ c_void_p, c_int, c_float, c_size_t = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 # sgic_quality_u8 (csrc/quality.hip): (d_a, d_b, B, H, W, d_work, work_bytes, d_sse, d_levels, stream)
 lib.sgic_quality_u8_work_bytes.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_quality_u8.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
+# sgic_niqe_u8 (csrc/niqe.hip): (d_img, B, H, W, h_weights, d_work, work_bytes, d_stats, d_sharp, stream)
+lib.sgic_niqe_u8_work_bytes.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
+lib.sgic_niqe_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
 # sgic_jpeg_encode_batch (csrc/jpeg_enc.hip): (d_rgb, B, H, W, subsampling, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, stream)
 lib.sgic_jpeg_encode_cap.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_jpeg_encode_work_bytes.argtypes = [c_int, c_int, c_int, c_int, C.POINTER(c_size_t)]
@@ -87,7 +90,8 @@ def ptr(t):
 _NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profiler_create", "sgic_profiler_begin", "sgic_profiler_end",
               "sgic_clip_preprocess_ragged_workspace", "sgic_clip_preprocess_u8canvas_workspace", "sgic_search_codes_u8_work_bytes",
               "sgic_search_codes_f32q_work_bytes", "sgic_search_rank_work_bytes", "sgic_assign_codes_f32c_work_bytes", "sgic_quality_u8_work_bytes", "sgic_jpeg_encode_cap",
-              "sgic_jpeg_encode_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes"}
+              "sgic_jpeg_encode_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes",
+              "sgic_niqe_u8_work_bytes"}
 
 
 def call(name, *args):

@@ -41,6 +41,13 @@
                                                                 whether the code in the container is the code P gives the original.
                                                                 P: the state dict compress.py --clip_ckpt takes (--small: the TINY
                                                                 tower)
+  evaluate.py ... --niqe_params P                               adds "niqe" (of the reconstruction) and "niqe_orig" (of the original)
+                                                                to every record, "niqe" to its anchor and their means to the summary
+                                                                ("anchor_niqe" with an anchor): the no-reference NIQE score on the
+                                                                same u8 tensors (niqe.Niqe), null for an image with fewer than two
+                                                                usable 96 x 96 blocks; P: the pristine model, an .npz with
+                                                                mu_pris_param and cov_pris_param (BasicSR's file, or the output of
+                                                                `python -m sgic_amd.niqe fit`) or MATLAB's .mat
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -126,6 +133,11 @@ def summarise(records, fid_sets=None, clip_sets=None):
             out.update(clip_sets.summary("anchor", [r for r in records if "anchor" in r], "anchor_clip_"))
     if fid_sets is not None:
         out.update(fid_sets.summary())
+    if any("niqe" in r for r in records):      # --niqe_params: after every other key
+        out["niqe"] = mean([r["niqe"] for r in records if r.get("niqe") is not None])
+        out["niqe_orig"] = mean([r["niqe_orig"] for r in records if r.get("niqe_orig") is not None])
+        if anchors:
+            out["anchor_niqe"] = mean([a["niqe"] for a in anchors if a.get("niqe") is not None])
     return out
 
 
@@ -291,6 +303,9 @@ def main(argv=None):
     ap.add_argument("--clip_ckpt", type=str, default=None,
                     help="state dict of the CLIP image tower (as compress.py --clip_ckpt): adds \"clip_sim\" to every record and the "
                          "retrieval figures clip_recall@k, clip_mrr, clip_median_rank to the summary")
+    ap.add_argument("--niqe_params", type=str, default=None,
+                    help="the pristine model of NIQE (.npz with mu_pris_param, cov_pris_param, or .mat): adds \"niqe\" and \"niqe_orig\" "
+                         "to every record")
     ap.add_argument("--fid_patch", type=int, default=256,
                     help="side of the windows FID and KID are computed on (the HiFiC protocol); 0: whole images")
     args = ap.parse_args(argv)
@@ -305,6 +320,13 @@ def main(argv=None):
         ap.error("--batch_size must be at least 1")
     if args.fid_patch < 0:
         ap.error("--fid_patch must be 0 (whole images) or a window side")
+    niqe_model = None
+    if args.niqe_params:       # a bad file ends the command here, before any model is built
+        from .niqe import Niqe
+        try:
+            niqe_model = Niqe(args.niqe_params)
+        except (ValueError, OSError) as e:
+            ap.error(f"--niqe_params: {e}")
 
     from concurrent.futures import ThreadPoolExecutor
     from . import quality
@@ -360,7 +382,7 @@ def main(argv=None):
             la = lpips_alex_model.measure(a, b) if lpips_alex_model is not None else None
             ds = dists_model.measure(a, b) if dists_model is not None else None
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
-            decoded = [] if fid_sets is not None or clip_sets is not None else None
+            decoded = [] if fid_sets is not None or clip_sets is not None or niqe_model is not None else None
             anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model,
                                    lpips_alex_model, decoded) if anchor else None
             if clip_sets is not None:
@@ -372,6 +394,9 @@ def main(argv=None):
                 if anchor:
                     uj, _ = clip_sets.embed(decoded[0])
                     asim = clip_sets.cosine(ua, uj)
+            if niqe_model is not None:
+                nq_b, nq_a = niqe_model.measure(b), niqe_model.measure(a)
+                nq_j = niqe_model.measure(decoded[0]) if anchor else None
             desc = fid_sets.windows(a) if fid_sets is not None else None
             if desc is not None:
                 fid_sets.add("orig", a, desc)
@@ -402,6 +427,13 @@ def main(argv=None):
                         anchors[j]["clip_sim"] = float(asim[j])
                         anchors[j]["over_rate"] = over
                         clip_sets.units["anchor"][stem] = uj[j]
+                if niqe_model is not None:
+                    rec["niqe"] = None if np.isnan(nq_b[j]) else float(nq_b[j])
+                    rec["niqe_orig"] = None if np.isnan(nq_a[j]) else float(nq_a[j])
+                    if anchors:
+                        over = anchors[j].pop("over_rate")
+                        anchors[j]["niqe"] = None if np.isnan(nq_j[j]) else float(nq_j[j])
+                        anchors[j]["over_rate"] = over
                 if anchors:
                     rec["anchor"] = anchors[j]
                 records.append(rec)

@@ -1270,6 +1270,26 @@ def quality_u8(a, b):
     return sse, levels
 
 
+def niqe_blocks_u8(x):
+    """the block sums of NIQE (csrc/niqe.hip): x (B, H, W, 3) u8 RGB, contiguous, 96 <= H, W <= 16384 -> (stats, sharp) float64 on
+    x's device.  stats (B, H // 96, W // 96, 2, 5, 5): per block, scale (0: 96 x 96 luma samples, 1: 48 x 48 of the half-size plane)
+    and map (the MSCN block n, then n * roll(n, s) for s = (0,1), (1,0), (1,1), (1,-1)): cnt_neg, cnt_pos, ssq_neg, ssq_pos, sabs.
+    sharp (B, H // 96, W // 96): the mean of the local deviation sigma over the scale-0 block.  niqe.features turns stats into the
+    36 numbers per block.  No synchronisation."""
+    from .niqe import window_weights
+    require_gpu()
+    assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and x.dim() == 4 and x.shape[3] == 3
+    B, H, W, _ = x.shape
+    nbytes = ctypes.c_size_t(0)
+    call("sgic_niqe_u8_work_bytes", B, H, W, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+    stats = torch.empty(B, H // 96, W // 96, 2, 5, 5, dtype=torch.float64, device=x.device)
+    sharp = torch.empty(B, H // 96, W // 96, dtype=torch.float64, device=x.device)
+    call("sgic_niqe_u8", _p(x), B, H, W, np.array(window_weights(), dtype=np.float64), _p(work), ctypes.c_size_t(nbytes.value),
+         _p(stats), _p(sharp))
+    return stats, sharp
+
+
 def lpips_input(img_u8, hp, image_offset=0):
     """the LPIPS input layer (csrc/lpips.hip): img_u8 (B, H, W, 3) u8 -> the interior of images image_offset .. image_offset+B-1 of
     hp, a HaloPlanes of (total images, H, W, 32) from halo_planes_buffer; channels 3..31 are zero.  No synchronisation."""
