@@ -28,6 +28,16 @@ inline int check_launch(const char *what) {
     }                                                                        \
   } while (0)
 
+// for checks shared by several entry points, which report the entry point's name (func), not the helper's.  SGIC_REQUIRE is
+// SGIC_REQUIRE_AS(__func__, ...), the two written out: through a second macro #cond would see cond after macro expansion
+#define SGIC_REQUIRE_AS(func, cond, msg)                      \
+  do {                                                        \
+    if (!(cond)) {                                            \
+      sgic::set_error("%s: requirement failed: %s (%s)", func, #cond, msg); \
+      return SGIC_EINVAL;                                     \
+    }                                                         \
+  } while (0)
+
 #define SGIC_REQUIRE(cond, msg)                               \
   do {                                                        \
     if (!(cond)) {                                            \

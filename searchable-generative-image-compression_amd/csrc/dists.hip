@@ -1,73 +1,31 @@
 // DISTS (VGG16) glue around the split 3x3 convolutions (sgic_conv3x3_split3_f32): the input layer, the exact u8 moments of tap 0, ReLU
 // + L2 (Hanning) pool into the next convolution's zero-halo operand planes, and the second-order moments and head of taps 1..5
-// (include/sgic.h).  All of it is bandwidth work: every lane moves 16 bytes along the 32-channel slice of the
-// slice-major plane layout (split3.h) or along a pixel's channel row.  No float atomics: a workgroup writes one partial per channel and
-// later kernels add the partials and the channels in a fixed order, so the same input gives the same bits (the u8 moments are
-// integers; their 64-bit atomic adds are exact in any order).  Built with -ffp-contract=off: one IEEE operation per written operation.
+// (include/sgic.h).  The input layer and the pool are the shared producer kernels of producers.h with DistsNorm
+// and ReluL2Pool; the moments move 16 bytes per lane along a pixel's channel row.  No float atomics: a workgroup writes one partial
+// per channel and later kernels add the partials and the channels in a fixed order, so the same input gives the same bits (the u8
+// moments are integers; their 64-bit atomic adds are exact in any order).
 //
 // L2 pool, per channel, fp32: r_t = max(v_t, 0) for the nine taps t = (ky, kx) of the 3x3 window centred on input (2 oy, 2 ox), a tap
 // outside the image counting as 0; s = w_00 r_00^2, then s = s + w_t (r_t r_t) for t = 01, 02, 10, 11, 12, 20, 21, 22 in this order,
 // w = (1, 2, 1) x (1, 2, 1) / 16 (powers of two: the products by w are exact); out = sqrtf(s + 1e-12f).
-#include <math.h>
-
-#include "common.h"
-#include "split3.h"
+#include "producers.h"
 
 namespace {
 
-typedef unsigned ds_u32x4 __attribute__((ext_vector_type(4)));
-typedef float ds_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long ds_u64;
 
-constexpr int NT = 256;              // threads of every kernel here
-constexpr int MAX_GRID = 1 << 20;    // grid-stride launches
 constexpr int U8_PIX = 4096;         // pixels of one pair per workgroup of the u8 moments: 16 per thread, so the u32 sums cannot overflow
 constexpr int MOM_PIX = 256;         // the pixel range of a moments workgroup is a multiple of this ...
 constexpr int MOM_MAX_WG = 256;      // ... chosen so that a pair has at most this many workgroups
 constexpr int SUM_ROWS = 8;          // rows of threads that share a channel in the sum kernel
 
-inline unsigned grid_for(size_t threads) {
-  const size_t g = (threads + NT - 1) / NT;
-  return (unsigned)(g < 1 ? 1 : (g > (size_t)MAX_GRID ? (size_t)MAX_GRID : g));
-}
-
-// u8 (B, H, W, 3) -> the interior of the planes [3][1][Btot (H+2) (W+2)][32] of images img0 .. img0+B-1.  Four lanes per pixel, 16
-// bytes (8 channels) each and plane: lane 0 carries the three values, the others zeros.
-__global__ __launch_bounds__(NT) void dists_input_kernel(const unsigned char *__restrict__ img, int B, int H, int W, int Btot, int img0,
-                                                         unsigned short *__restrict__ planes) {
-  const size_t rows = (size_t)Btot * (H + 2) * (W + 2), plane = rows * 32;
-  const size_t total = (size_t)B * H * W * 4;
-  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += (size_t)gridDim.x * NT) {
-    const int q = (int)(i & 3);
-    size_t t = i >> 2;
-    const unsigned char *px = img + t * 3;
-    const int x = (int)(t % W);
-    t /= W;
-    const int y = (int)(t % H);
-    const int b = (int)(t / H);
-    const size_t prow = ((size_t)(b + img0) * (H + 2) + y + 1) * (W + 2) + x + 1;
-    ds_u32x4 o0 = {0u, 0u, 0u, 0u}, o1 = o0, o2 = o0;
-    if (q == 0) {
-      const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-      float v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float u = (float)px[c] / 255.0f;
-        v[c] = (u - mean[c]) / stdv[c];
-      }
-      unsigned a0, b0, c0, a1, b1, c1;
-      s3_split_pair(v[0], v[1], a0, b0, c0);
-      s3_split_pair(v[2], 0.0f, a1, b1, c1);
-      o0.x = a0, o0.y = a1;
-      o1.x = b0, o1.y = b1;
-      o2.x = c0, o2.y = c1;
-    }
-    const size_t dst = prow * 32 + q * 8;
-    *reinterpret_cast<ds_u32x4 *>(planes + dst) = o0;
-    *reinterpret_cast<ds_u32x4 *>(planes + plane + dst) = o1;
-    *reinterpret_cast<ds_u32x4 *>(planes + 2 * plane + dst) = o2;
+// the DISTS input layer of channel c of a u8 value
+struct DistsNorm {
+  __device__ __forceinline__ float operator()(unsigned u, int c) const {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    return ((float)u / 255.0f - mean[c]) / stdv[c];
   }
-}
+};
 
 __device__ __forceinline__ ds_u64 wave_sum(ds_u64 v) {
 #pragma unroll
@@ -116,27 +74,12 @@ __global__ __launch_bounds__(NT) void dists_moments_u8_kernel(const unsigned cha
   }
 }
 
-__device__ __forceinline__ ds_f32x4 relu4(ds_f32x4 v) { return ds_f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
-
-// fp32 (B H W, C) -> relu -> square -> 3x3 Hanning window, stride 2, zero padding 1 -> + 1e-12 -> sqrt -> the interior of the planes
-// [3][C / 32][B (OH+2) (OW+2)][32], OH = (H + 1) / 2.  A lane owns 8 channels of one output pixel; lanes run along the slice, then the
-// row, so a wave writes whole 64-byte slices of neighbouring pixels: consecutive bytes in each plane.  The order of the sum is in the
-// header comment.
-__global__ __launch_bounds__(NT) void relu_l2pool_halo_kernel(const float *__restrict__ in, int B, int H, int W, int C,
-                                                              unsigned short *__restrict__ planes) {
-  const int OH = (H + 1) >> 1, OW = (W + 1) >> 1;
-  const size_t rows = (size_t)B * (OH + 2) * (OW + 2), plane = rows * C;
-  const size_t total = (size_t)(C >> 5) * B * OH * OW * 4;
-  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += (size_t)gridDim.x * NT) {
-    const int q = (int)(i & 3);
-    size_t t = i >> 2;
-    const int ox = (int)(t % OW);
-    t /= OW;
-    const int oy = (int)(t % OH);
-    t /= OH;
-    const int b = (int)(t % B);
-    const int slice = (int)(t / B);
-    ds_f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+// halo_producer_kernel's op: relu -> square -> 3x3 Hanning window, stride 2, zero padding 1 -> + 1e-12 -> sqrt, OH = (H + 1) / 2.  The
+// order of the sum is in the header comment.
+struct ReluL2Pool {
+  __device__ __forceinline__ void operator()(const float *__restrict__ in, int b, int oy, int ox, int slice, int q, int H, int W, int C,
+                                             s3_f32x4 &o0, s3_f32x4 &o1) const {
+    s3_f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
@@ -144,11 +87,11 @@ __global__ __launch_bounds__(NT) void relu_l2pool_halo_kernel(const float *__res
         const int iy = 2 * oy - 1 + ky, ix = 2 * ox - 1 + kx;
         const bool inside = iy >= 0 && iy < H && ix >= 0 && ix < W;
         const float wgt = (ky == 1 ? 2.0f : 1.0f) * (kx == 1 ? 2.0f : 1.0f) * 0.0625f;
-        ds_f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+        s3_f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
         if (inside) {
           const float *p = in + (((size_t)b * H + iy) * W + ix) * C + slice * 32 + q * 8;
-          v0 = relu4(reinterpret_cast<const ds_f32x4 *>(p)[0]);
-          v1 = relu4(reinterpret_cast<const ds_f32x4 *>(p)[1]);
+          v0 = relu4(reinterpret_cast<const s3_f32x4 *>(p)[0]);
+          v1 = relu4(reinterpret_cast<const s3_f32x4 *>(p)[1]);
         }
         s0 = s0 + wgt * (v0 * v0);
         s1 = s1 + wgt * (v1 * v1);
@@ -156,19 +99,10 @@ __global__ __launch_bounds__(NT) void relu_l2pool_halo_kernel(const float *__res
     }
     s0 = s0 + 1e-12f;
     s1 = s1 + 1e-12f;
-    unsigned a[4], m[4], l[4];
-    s3_split_pair(sqrtf(s0.x), sqrtf(s0.y), a[0], m[0], l[0]);
-    s3_split_pair(sqrtf(s0.z), sqrtf(s0.w), a[1], m[1], l[1]);
-    s3_split_pair(sqrtf(s1.x), sqrtf(s1.y), a[2], m[2], l[2]);
-    s3_split_pair(sqrtf(s1.z), sqrtf(s1.w), a[3], m[3], l[3]);
-    const ds_u32x4 o0 = {a[0], a[1], a[2], a[3]}, o1 = {m[0], m[1], m[2], m[3]}, o2 = {l[0], l[1], l[2], l[3]};
-    const size_t prow = ((size_t)b * (OH + 2) + oy + 1) * (OW + 2) + ox + 1;
-    const size_t dst = ((size_t)slice * rows + prow) * 32 + q * 8;
-    *reinterpret_cast<ds_u32x4 *>(planes + dst) = o0;
-    *reinterpret_cast<ds_u32x4 *>(planes + plane + dst) = o1;
-    *reinterpret_cast<ds_u32x4 *>(planes + 2 * plane + dst) = o2;
+    o0 = s3_f32x4{sqrtf(s0.x), sqrtf(s0.y), sqrtf(s0.z), sqrtf(s0.w)};
+    o1 = s3_f32x4{sqrtf(s1.x), sqrtf(s1.y), sqrtf(s1.z), sqrtf(s1.w)};
   }
-}
+};
 
 // One workgroup: pixels [blockIdx.x ppw, (blockIdx.x + 1) ppw) of pair blockIdx.y, all C channels.  Thread t owns the four channels
 // 4 (t % G) .. of the pixels t / G, t / G + PL, ... with G = C / 4, PL = 256 / G (threads past PL G idle): a pass of the workgroup
@@ -184,10 +118,10 @@ __global__ __launch_bounds__(NT) void dists_moments_kernel(const float *__restri
   const long p0 = (long)blockIdx.x * ppw, p1 = p0 + ppw < HW ? p0 + ppw : HW;
   double sx[4] = {0., 0., 0., 0.}, sy[4] = {0., 0., 0., 0.}, sxx[4] = {0., 0., 0., 0.}, syy[4] = {0., 0., 0., 0.}, sxy[4] = {0., 0., 0., 0.};
   if (prow < PL) {
-    const ds_f32x4 *fa = reinterpret_cast<const ds_f32x4 *>(feat + (size_t)b * HW * C) + g;
-    const ds_f32x4 *fb = reinterpret_cast<const ds_f32x4 *>(feat + (size_t)(B + b) * HW * C) + g;
+    const s3_f32x4 *fa = reinterpret_cast<const s3_f32x4 *>(feat + (size_t)b * HW * C) + g;
+    const s3_f32x4 *fb = reinterpret_cast<const s3_f32x4 *>(feat + (size_t)(B + b) * HW * C) + g;
     for (long p = p0 + prow; p < p1; p += PL) {
-      const ds_f32x4 xv = relu4(fa[(size_t)p * G]), yv = relu4(fb[(size_t)p * G]);
+      const s3_f32x4 xv = relu4(fa[(size_t)p * G]), yv = relu4(fb[(size_t)p * G]);
       const double x[4] = {xv.x, xv.y, xv.z, xv.w}, y[4] = {yv.x, yv.y, yv.z, yv.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -278,7 +212,6 @@ __global__ __launch_bounds__(NT) void dists_head_kernel(const double *__restrict
   }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 inline bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
 inline long mom_ppw(long HW) {      // pixels per moments workgroup: a multiple of MOM_PIX that leaves at most MOM_MAX_WG workgroups
   const long per = (long)MOM_PIX * MOM_MAX_WG;
@@ -293,13 +226,7 @@ inline size_t mom_wgs(long HW) {
 
 extern "C" int sgic_dists_input_split3(const uint8_t *d_img, int B, int H, int W, int total_images, int image_offset,
                                        uint16_t *d_halo_planes, sgic_stream_t stream) {
-  SGIC_REQUIRE(d_img && d_halo_planes, "null pointer");
-  SGIC_REQUIRE(B >= 1 && H >= 1 && W >= 1, "empty batch or image");
-  SGIC_REQUIRE(image_offset >= 0 && total_images >= 1 && (long)image_offset + B <= (long)total_images, "image slots");
-  SGIC_REQUIRE((long)total_images * (H + 2) * (W + 2) < (1l << 31), "too many pixels");
-  SGIC_REQUIRE(aligned16(d_halo_planes), "planes must be 16-byte aligned");
-  dists_input_kernel<<<grid_for((size_t)B * H * W * 4), NT, 0, to_stream(stream)>>>(d_img, B, H, W, total_images, image_offset, d_halo_planes);
-  return sgic::check_launch("dists_input_kernel");
+  return input_halo_launch<DistsNorm>(__func__, "dists_input_kernel", d_img, B, H, W, total_images, image_offset, d_halo_planes, stream);
 }
 
 extern "C" int sgic_dists_moments_u8(const uint8_t *d_a, const uint8_t *d_b, int B, int H, int W, int64_t *d_sums, sgic_stream_t stream) {
@@ -321,9 +248,7 @@ extern "C" int sgic_relu_l2pool_halo_split3(const float *d_in, int B, int H, int
   SGIC_REQUIRE(C >= 32 && C % 32 == 0, "C must be a multiple of 32");
   SGIC_REQUIRE((long)B * (H + 2) * (W + 2) < (1l << 31), "too many pixels");
   SGIC_REQUIRE(aligned16(d_in) && aligned16(d_halo_planes), "buffers must be 16-byte aligned");
-  const int OH = (H + 1) / 2, OW = (W + 1) / 2;
-  relu_l2pool_halo_kernel<<<grid_for((size_t)(C / 32) * B * OH * OW * 4), NT, 0, to_stream(stream)>>>(d_in, B, H, W, C, d_halo_planes);
-  return sgic::check_launch("relu_l2pool_halo_kernel");
+  return halo_producer_launch<ReluL2Pool>("relu_l2pool_halo_kernel", d_in, B, H, W, C, (H + 1) / 2, (W + 1) / 2, d_halo_planes, stream);
 }
 
 extern "C" int sgic_dists_moments_work_bytes(int B, int H, int W, int C, size_t *bytes) {

@@ -1,45 +1,13 @@
 // FID / KID kernels (include/sgic.h): the input step of pytorch-fid's Inception-v3, the one generic patch producer
 // that writes a convolution's A operand directly as slice-major bf16x3 planes (split3.h) for sgic_gemm_split3_f32, the three pools of
 // the Inception graph with the ReLU applied on read, the final ReLU + spatial mean, and an fp64 Gram kernel for the second moments of
-// FID and the kernel sums of KID.  All bandwidth work except the Gram.  The producers use the lane pattern of
-// relu_maxpool3_patches5_kernel (lpips_alex.hip): a lane owns 8 columns of one 32-column slice and moves 16 bytes per plane; lanes run
-// along the slice, then the rows, so a wave writes 1 KiB of consecutive bytes in each plane.  Plain C++ and vector stores only, no
-// atomics.  Built with -ffp-contract=off: one IEEE operation per written operation (the producers and pools are compared for equality).
-#include <math.h>
-
-#include "common.h"
-#include "split3.h"
+// FID and the kernel sums of KID.  All bandwidth work except the Gram.  The patch producer has the lane pattern and the helpers of
+// producers.h and its own loop (its index map is generic in kernel, stride and padding).  No atomics.
+#include "producers.h"
 
 namespace {
 
-typedef unsigned fd_u32x4 __attribute__((ext_vector_type(4)));
-typedef float fd_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int NT = 256;              // threads of every kernel here
-constexpr int MAX_GRID = 1 << 20;    // grid-stride launches
 constexpr int S = 299;               // the Inception input extent
-constexpr long ROW_LIMIT = 1l << 31;
-
-inline unsigned grid_for(size_t threads) {
-  const size_t g = (threads + NT - 1) / NT;
-  return (unsigned)(g < 1 ? 1 : (g > (size_t)MAX_GRID ? (size_t)MAX_GRID : g));
-}
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ fd_f32x4 relu4(fd_f32x4 a) { return fd_f32x4{fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)}; }
-__device__ __forceinline__ fd_f32x4 max4(fd_f32x4 a, fd_f32x4 b) {
-  return fd_f32x4{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)};
-}
-
-// eight values -> 16 bytes in each of the three planes
-__device__ __forceinline__ void split8_store(unsigned short *planes, size_t plane, size_t dst, const float *v) {
-  unsigned a[4], m[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s3_split_pair(v[2 * j], v[2 * j + 1], a[j], m[j], l[j]);
-  *reinterpret_cast<fd_u32x4 *>(planes + dst) = fd_u32x4{a[0], a[1], a[2], a[3]};
-  *reinterpret_cast<fd_u32x4 *>(planes + plane + dst) = fd_u32x4{m[0], m[1], m[2], m[3]};
-  *reinterpret_cast<fd_u32x4 *>(planes + 2 * plane + dst) = fd_u32x4{l[0], l[1], l[2], l[3]};
-}
 
 // the source position of output index d of an `in` -> 299 bilinear resize, align_corners = False: src = max((d + 0.5) in / 299 - 0.5, 0)
 // = max((2 d + 1) in - 299, 0) / 598, in integers: i0 = floor(src), lambda = the remainder / 598 (one fp32 division)
@@ -102,13 +70,12 @@ __global__ __launch_bounds__(NT) void patches_split3_kernel(const float *__restr
     const int oy = (int)(t2 % OH), b = (int)(t2 / OH);
     const int k0 = slice * 32 + q * 8, iy0 = oy * sh - ph, ix0 = ox * sw - pw;
     const float *im = in + (size_t)b * H * W * ld + col0;
-    float v[8];
+    s3_f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
     if (FAST) {
       const int tap = k0 / C, c = k0 - tap * C, ky = tap / kw, kx = tap - ky * kw;
       const int iy = iy0 + ky, ix = ix0 + kx;
-      fd_f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
       if (tap < taps && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-        const fd_f32x4 *s = reinterpret_cast<const fd_f32x4 *>(im + ((size_t)iy * W + ix) * ld + c);
+        const s3_f32x4 *s = reinterpret_cast<const s3_f32x4 *>(im + ((size_t)iy * W + ix) * ld + c);
         v0 = s[0];
         v1 = s[1];
         if (relu) {
@@ -116,8 +83,8 @@ __global__ __launch_bounds__(NT) void patches_split3_kernel(const float *__restr
           v1 = relu4(v1);
         }
       }
-      v[0] = v0.x, v[1] = v0.y, v[2] = v0.z, v[3] = v0.w, v[4] = v1.x, v[5] = v1.y, v[6] = v1.z, v[7] = v1.w;
     } else {
+      float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int k = k0 + j, tap = k / C, c = k - tap * C, ky = tap / kw, kx = tap - ky * kw;
@@ -128,8 +95,10 @@ __global__ __launch_bounds__(NT) void patches_split3_kernel(const float *__restr
           v[j] = relu ? fmaxf(x, 0.f) : x;
         }
       }
+      v0 = s3_f32x4{v[0], v[1], v[2], v[3]};
+      v1 = s3_f32x4{v[4], v[5], v[6], v[7]};
     }
-    split8_store(planes, plane, ((size_t)slice * rows + row) * 32 + q * 8, v);
+    s3_store8(planes, plane, ((size_t)slice * rows + row) * 32 + q * 8, v0, v1);
   }
 }
 
@@ -149,7 +118,7 @@ __global__ __launch_bounds__(NT) void relu_pool3_kernel(const float *__restrict_
     const int ox = (int)(row % OW);
     const size_t t2 = row / OW;
     const int oy = (int)(t2 % OH), b = (int)(t2 / OH);
-    fd_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    s3_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int cnt = 0;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
@@ -158,9 +127,9 @@ __global__ __launch_bounds__(NT) void relu_pool3_kernel(const float *__restrict_
       for (int dx = 0; dx < 3; ++dx) {
         const int ix = ox * st - pad + dx;
         if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-          const fd_f32x4 s = relu4(*reinterpret_cast<const fd_f32x4 *>(in + (((size_t)b * H + iy) * W + ix) * C + c4 * 4));
+          const s3_f32x4 s = relu4(*reinterpret_cast<const s3_f32x4 *>(in + (((size_t)b * H + iy) * W + ix) * C + c4 * 4));
           if (MODE == 1) {
-            acc = fd_f32x4{acc.x + s.x, acc.y + s.y, acc.z + s.z, acc.w + s.w};
+            acc = s3_f32x4{acc.x + s.x, acc.y + s.y, acc.z + s.z, acc.w + s.w};
             ++cnt;
           } else {
             acc = max4(acc, s);
@@ -170,9 +139,9 @@ __global__ __launch_bounds__(NT) void relu_pool3_kernel(const float *__restrict_
     }
     if (MODE == 1) {
       const float d = (float)cnt;
-      acc = fd_f32x4{acc.x / d, acc.y / d, acc.z / d, acc.w / d};
+      acc = s3_f32x4{acc.x / d, acc.y / d, acc.z / d, acc.w / d};
     }
-    *reinterpret_cast<fd_f32x4 *>(out + row * ldo + co + c4 * 4) = acc;
+    *reinterpret_cast<s3_f32x4 *>(out + row * ldo + co + c4 * 4) = acc;
   }
 }
 
@@ -225,7 +194,7 @@ __global__ __launch_bounds__(NT) void gram_f64_kernel(const float *__restrict__ 
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < GK; ++k) {
-      const fd_f32x4 a4 = *reinterpret_cast<const fd_f32x4 *>(&As[k][ty * 4]), b4 = *reinterpret_cast<const fd_f32x4 *>(&Bs[k][tx * 4]);
+      const s3_f32x4 a4 = *reinterpret_cast<const s3_f32x4 *>(&As[k][ty * 4]), b4 = *reinterpret_cast<const s3_f32x4 *>(&Bs[k][tx * 4]);
       const double a[4] = {(double)a4.x, (double)a4.y, (double)a4.z, (double)a4.w};
       const double b[4] = {(double)b4.x, (double)b4.y, (double)b4.z, (double)b4.w};
 #pragma unroll

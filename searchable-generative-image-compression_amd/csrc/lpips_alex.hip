@@ -1,50 +1,14 @@
 // LPIPS (AlexNet) producers (include/sgic.h): the operands of the two convolutions that do not fit the implicit
 // 3x3 path are written as patch matrices, directly as slice-major bf16x3 planes (split3.h), and run through sgic_gemm_split3_f32;
-// the 3x3 / stride 2 max-pool in front of the third convolution writes that convolution's zero-halo planes.  All three are
-// bandwidth work with the lane pattern of relu_pool_halo_kernel (lpips.hip): a lane owns 8 columns of one 32-column slice and moves
-// 16 bytes per plane; lanes run along the slice, then the row, so a wave writes consecutive bytes in each plane.  Plain C++ and
-// vector stores only.  Built with -ffp-contract=off: one IEEE operation per written operation (compared for equality).
-#include <math.h>
-
-#include "common.h"
-#include "split3.h"
+// the 3x3 / stride 2 max-pool in front of the third convolution writes that convolution's zero-halo planes through the shared
+// halo_producer_kernel.  The lane pattern and the helpers are those of producers.h; the two patch kernels keep their own loops (their
+// index maps differ).
+#include "producers.h"
 
 namespace {
 
-typedef unsigned la_u32x4 __attribute__((ext_vector_type(4)));
-typedef float la_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int NT = 256;              // threads of every kernel here
-constexpr int MAX_GRID = 1 << 20;    // grid-stride launches
 constexpr int K1 = 363, K1P = 384;   // 11 * 11 * 3 columns of the first patch matrix, padded to whole slices
 constexpr int ROWK = 33;             // columns of one ky: 11 pixels x 3 channels, consecutive bytes of an image row
-
-inline unsigned grid_for(size_t threads) {
-  const size_t g = (threads + NT - 1) / NT;
-  return (unsigned)(g < 1 ? 1 : (g > (size_t)MAX_GRID ? (size_t)MAX_GRID : g));
-}
-
-__device__ __forceinline__ la_f32x4 max4(la_f32x4 a, la_f32x4 b) {
-  return la_f32x4{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)};
-}
-
-// eight values -> 16 bytes in each of the three planes
-__device__ __forceinline__ void split8(la_f32x4 v0, la_f32x4 v1, la_u32x4 &o0, la_u32x4 &o1, la_u32x4 &o2) {
-  unsigned a[4], m[4], l[4];
-  s3_split_pair(v0.x, v0.y, a[0], m[0], l[0]);
-  s3_split_pair(v0.z, v0.w, a[1], m[1], l[1]);
-  s3_split_pair(v1.x, v1.y, a[2], m[2], l[2]);
-  s3_split_pair(v1.z, v1.w, a[3], m[3], l[3]);
-  o0 = la_u32x4{a[0], a[1], a[2], a[3]};
-  o1 = la_u32x4{m[0], m[1], m[2], m[3]};
-  o2 = la_u32x4{l[0], l[1], l[2], l[3]};
-}
-
-__device__ __forceinline__ void store3(unsigned short *planes, size_t plane, size_t dst, la_u32x4 o0, la_u32x4 o1, la_u32x4 o2) {
-  *reinterpret_cast<la_u32x4 *>(planes + dst) = o0;
-  *reinterpret_cast<la_u32x4 *>(planes + plane + dst) = o1;
-  *reinterpret_cast<la_u32x4 *>(planes + 2 * plane + dst) = o2;
-}
 
 // u8 (B, H, W, 3) -> rows (img0 + b, oy, ox) of the A operand [3][12][Btot h1 w1][32] of the 11x11 / stride 4 / pad 2 convolution:
 // column k = (ky 11 + kx) 3 + c holds the input layer at pixel (4 oy - 2 + ky, 4 ox - 2 + kx), zero outside the image and for
@@ -54,12 +18,8 @@ __device__ __forceinline__ void store3(unsigned short *planes, size_t plane, siz
 __global__ __launch_bounds__(NT) void alex_conv1_patches_kernel(const unsigned char *__restrict__ img, int B, int H, int W, int h1, int w1,
                                                                 int Btot, int img0, unsigned short *__restrict__ planes) {
   __shared__ float lut[3 * 256];
-  {
-    const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
-    const float u = (float)threadIdx.x / 255.0f * 2.0f - 1.0f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) lut[c * 256 + threadIdx.x] = (u - shift[c]) / scale[c];
-  }
+  for (int c = 0; c < 3; ++c) lut[c * 256 + threadIdx.x] = LpipsNorm()(threadIdx.x, c);
   __syncthreads();
   const size_t rows = (size_t)Btot * h1 * w1, plane = rows * K1P;
   const size_t total = (size_t)(K1P / 32) * B * h1 * w1 * 4;
@@ -83,27 +43,30 @@ __global__ __launch_bounds__(NT) void alex_conv1_patches_kernel(const unsigned c
       v[j] = 0.0f;
       if (ok) v[j] = lut[c * 256 + im[((long)iy * W + ix0) * 3 + rem]];     // ix >= 0, so 3 ix0 + rem >= 0
     }
-    la_u32x4 o0, o1, o2;
-    split8(la_f32x4{v[0], v[1], v[2], v[3]}, la_f32x4{v[4], v[5], v[6], v[7]}, o0, o1, o2);
     const size_t row = ((size_t)(b + img0) * h1 + oy) * w1 + ox;
-    store3(planes, plane, ((size_t)slice * rows + row) * 32 + q * 8, o0, o1, o2);
+    s3_store8(planes, plane, ((size_t)slice * rows + row) * 32 + q * 8, s3_f32x4{v[0], v[1], v[2], v[3]}, s3_f32x4{v[4], v[5], v[6], v[7]});
   }
 }
 
-// relu -> max over the 3 x 3 window at (2 py, 2 px) of 8 channels; relu is monotone, so the maximum starts at 0
-__device__ __forceinline__ void relu_pool3(const float *__restrict__ p, int W, int C, la_f32x4 &v0, la_f32x4 &v1) {
-  v0 = la_f32x4{0.f, 0.f, 0.f, 0.f};
-  v1 = v0;
+// halo_producer_kernel's op: relu -> max over the 3 x 3 window at (2 oy, 2 ox) of 8 channels (3x3 / stride 2, floor); relu is
+// monotone, so the maximum starts at 0
+struct ReluMaxPool3 {
+  __device__ __forceinline__ void operator()(const float *__restrict__ in, int b, int oy, int ox, int slice, int q, int H, int W, int C,
+                                             s3_f32x4 &v0, s3_f32x4 &v1) const {
+    const float *p = in + (((size_t)b * H + 2 * oy) * W + 2 * ox) * C + slice * 32 + q * 8;
+    v0 = s3_f32x4{0.f, 0.f, 0.f, 0.f};
+    v1 = v0;
 #pragma unroll
-  for (int dy = 0; dy < 3; ++dy) {
+    for (int dy = 0; dy < 3; ++dy) {
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const la_f32x4 *s = reinterpret_cast<const la_f32x4 *>(p + ((size_t)dy * W + dx) * C);
-      v0 = max4(v0, s[0]);
-      v1 = max4(v1, s[1]);
+      for (int dx = 0; dx < 3; ++dx) {
+        const s3_f32x4 *s = reinterpret_cast<const s3_f32x4 *>(p + ((size_t)dy * W + dx) * C);
+        v0 = max4(v0, s[0]);
+        v1 = max4(v1, s[1]);
+      }
     }
   }
-}
+};
 
 // fp32 (B H W, C) -> relu -> max-pool 3x3 / 2 (floor) to PH x PW -> the A operand [3][25 C / 32][B PH PW][32] of the 5x5 / pad 2
 // convolution: column k = (ky 5 + kx) C + c of row (b, oy, ox) holds the pooled value at (oy + ky - 2, ox + kx - 2), zero outside
@@ -126,11 +89,8 @@ __global__ __launch_bounds__(NT) void relu_maxpool3_patches5_kernel(const float 
     const int b = (int)(t % B);
     const int cs = (int)(t / B);
     const int py = ey - 2, px = ex - 2;
-    la_f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
-    if ((unsigned)py < (unsigned)PH && (unsigned)px < (unsigned)PW)
-      relu_pool3(in + (((size_t)b * H + 2 * py) * W + 2 * px) * C + cs * 32 + q * 8, W, C, v0, v1);
-    la_u32x4 o0, o1, o2;
-    split8(v0, v1, o0, o1, o2);
+    s3_f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+    if ((unsigned)py < (unsigned)PH && (unsigned)px < (unsigned)PW) ReluMaxPool3()(in, b, py, px, cs, q, H, W, C, v0, v1);
     for (int ky = 0; ky < 5; ++ky) {
       const int oy = ey - ky;
       if ((unsigned)oy >= (unsigned)PH) continue;
@@ -139,37 +99,11 @@ __global__ __launch_bounds__(NT) void relu_maxpool3_patches5_kernel(const float 
         const int ox = ex - kx;
         if ((unsigned)ox >= (unsigned)PW) continue;
         const size_t row = ((size_t)b * PH + oy) * PW + ox;
-        store3(planes, plane, ((size_t)((ky * 5 + kx) * CS + cs) * rows + row) * 32 + q * 8, o0, o1, o2);
+        s3_store8(planes, plane, ((size_t)((ky * 5 + kx) * CS + cs) * rows + row) * 32 + q * 8, v0, v1);
       }
     }
   }
 }
-
-// fp32 (B H W, C) -> relu -> max-pool 3x3 / 2 (floor) -> the interior of the planes [3][C / 32][B (PH+2) (PW+2)][32]
-__global__ __launch_bounds__(NT) void relu_maxpool3_halo_kernel(const float *__restrict__ in, int B, int H, int W, int C, int PH, int PW,
-                                                                unsigned short *__restrict__ planes) {
-  const size_t rows = (size_t)B * (PH + 2) * (PW + 2), plane = rows * C;
-  const size_t total = (size_t)(C >> 5) * B * PH * PW * 4;
-  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += (size_t)gridDim.x * NT) {
-    const int q = (int)(i & 3);
-    size_t t = i >> 2;
-    const int px = (int)(t % PW);
-    t /= PW;
-    const int py = (int)(t % PH);
-    t /= PH;
-    const int b = (int)(t % B);
-    const int cs = (int)(t / B);
-    la_f32x4 v0, v1;
-    relu_pool3(in + (((size_t)b * H + 2 * py) * W + 2 * px) * C + cs * 32 + q * 8, W, C, v0, v1);
-    la_u32x4 o0, o1, o2;
-    split8(v0, v1, o0, o1, o2);
-    const size_t prow = ((size_t)b * (PH + 2) + py + 1) * (PW + 2) + px + 1;
-    store3(planes, plane, ((size_t)cs * rows + prow) * 32 + q * 8, o0, o1, o2);
-  }
-}
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-constexpr long ROW_LIMIT = 1l << 31;
 
 }  // namespace
 
@@ -208,6 +142,5 @@ extern "C" int sgic_relu_maxpool3_halo_split3(const float *d_in, int B, int H, i
   const int PH = (H - 3) / 2 + 1, PW = (W - 3) / 2 + 1;
   SGIC_REQUIRE((long)B * H * W < ROW_LIMIT && (long)B * (PH + 2) * (PW + 2) < ROW_LIMIT, "too many rows");
   SGIC_REQUIRE(aligned16(d_in) && aligned16(d_halo_planes), "buffers must be 16-byte aligned");
-  relu_maxpool3_halo_kernel<<<grid_for((size_t)(C / 32) * B * PH * PW * 4), NT, 0, to_stream(stream)>>>(d_in, B, H, W, C, PH, PW, d_halo_planes);
-  return sgic::check_launch("relu_maxpool3_halo_kernel");
+  return halo_producer_launch<ReluMaxPool3>("relu_maxpool3_halo_kernel", d_in, B, H, W, C, PH, PW, d_halo_planes, stream);
 }

@@ -5,6 +5,7 @@
 
 typedef __bf16 s3_bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned s3_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned s3_u32x4 __attribute__((ext_vector_type(4)));
 typedef float s3_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned s3_pk_bf16(float lo, float hi) {   // v_cvt_pk_bf16_f32: round to nearest even
@@ -30,6 +31,17 @@ __device__ __forceinline__ void s3_store4(unsigned short *planes, long plane_ele
   *reinterpret_cast<s3_u32x2 *>(planes + dst) = s3_u32x2{a0, a1};
   *reinterpret_cast<s3_u32x2 *>(planes + plane_elems + dst) = s3_u32x2{b0, b1};
   *reinterpret_cast<s3_u32x2 *>(planes + 2 * plane_elems + dst) = s3_u32x2{c0, c1};
+}
+// eight consecutive values (v0, v1) -> 16 bytes in each of the three planes
+__device__ __forceinline__ void s3_store8(unsigned short *planes, size_t plane_elems, size_t dst, const s3_f32x4 &v0, const s3_f32x4 &v1) {
+  unsigned a[4], m[4], l[4];
+  s3_split_pair(v0.x, v0.y, a[0], m[0], l[0]);
+  s3_split_pair(v0.z, v0.w, a[1], m[1], l[1]);
+  s3_split_pair(v1.x, v1.y, a[2], m[2], l[2]);
+  s3_split_pair(v1.z, v1.w, a[3], m[3], l[3]);
+  *reinterpret_cast<s3_u32x4 *>(planes + dst) = s3_u32x4{a[0], a[1], a[2], a[3]};
+  *reinterpret_cast<s3_u32x4 *>(planes + plane_elems + dst) = s3_u32x4{m[0], m[1], m[2], m[3]};
+  *reinterpret_cast<s3_u32x4 *>(planes + 2 * plane_elems + dst) = s3_u32x4{l[0], l[1], l[2], l[3]};
 }
 
 // ---- slice-major ("packed") plane layout [3][cols / 32][rows][32]: the 64 bytes a row contributes to a 32-k slice sit next to the

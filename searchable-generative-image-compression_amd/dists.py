@@ -3,12 +3,12 @@ definition is written out in DESIGN.md section 15.  The trunk is the thirteen 3x
 implicit bf16x3 split GEMMs; the input layer, the exact u8 moments of tap 0, ReLU + L2 pool into the next convolution's operand planes
 and the moments and head of taps 1..5 are csrc/dists.hip.  Weights are a checkpoint the user has (load_weights) or synthetic
 (synth_weights: the tests)."""
-import math
-
 import numpy as np
 import torch
 
-from .lpips import CONV_CH, CONV_IDX, MAX_PIXELS, MIN_SIDE, POOL_AFTER, TAP_AFTER
+from .lpips import MIN_SIDE
+from .perceptual import CONV_CH, CONV_IDX, MAX_PIXELS, POOL_AFTER, TAP_AFTER  # noqa: F401 -- also this module's names
+from .perceptual import checked_pair, chunked, load_state, run_vgg16, vgg_conv, vgg_synth_trunk
 
 TAP_CH = (3, 64, 128, 256, 512, 512)      # tap 0 is the image itself
 N_CH = sum(TAP_CH)                        # 1475
@@ -45,25 +45,7 @@ def load_weights(paths):
     expected_shapes().  Accepted keys: the trunk as features.{i}.{weight,bias} (torchvision), stage{s}.{i}.{weight,bias}
     (DISTS_pytorch) or model.{i}.{weight,bias} (piq); alpha and beta of shape (1, 1475, 1, 1) or (1475,).  Later files win.  Every
     shape is checked; a missing key is named in the error."""
-    if isinstance(paths, (str, bytes, dict)) or hasattr(paths, "__fspath__"):
-        paths = [paths]
-    want = expected_shapes()
-    out = {}
-    for p in paths:
-        sd = p if isinstance(p, dict) else torch.load(p, map_location="cpu", weights_only=True)
-        sd = sd.get("state_dict", sd)
-        for key, v in sd.items():
-            ck = _canonical_key(key)
-            if ck is None or ck not in want:
-                continue
-            ok = (want[ck], (1, N_CH, 1, 1)) if ck in ("alpha", "beta") else (want[ck],)
-            if tuple(v.shape) not in ok:
-                raise ValueError(f"DISTS weights: {key} has shape {tuple(v.shape)}, expected {' or '.join(str(s) for s in ok)}")
-            out[ck] = v.detach().to(torch.float32).reshape(want[ck]).contiguous()
-    missing = [k for k in want if k not in out]
-    if missing:
-        raise KeyError(f"DISTS weights: missing {', '.join(missing)}")
-    return {k: out[k] for k in want}
+    return load_state(paths, expected_shapes(), _canonical_key, "DISTS", {k: ((1, N_CH, 1, 1),) for k in ("alpha", "beta")})
 
 
 def synth_weights(seed, path=None, style="torchvision"):
@@ -72,10 +54,7 @@ def synth_weights(seed, path=None, style="torchvision"):
     also writes it as a state dict file in one of STYLES: "torchvision" (features.* and flat alpha, beta), "dists_pytorch" (stage*.*,
     alpha and beta as (1, 1475, 1, 1)) or "piq" (model.*, alpha and beta as (1, 1475, 1, 1))."""
     g = torch.Generator().manual_seed(int(seed))
-    sd = {}
-    for i, (cin, cout) in zip(CONV_IDX, CONV_CH):
-        sd[f"features.{i}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
-        sd[f"features.{i}.bias"] = torch.rand(cout, generator=g) * 0.05
+    sd = vgg_synth_trunk(g)
     sd["alpha"] = (1.0 - torch.rand(N_CH, generator=g)) * 0.2
     sd["beta"] = (1.0 - torch.rand(N_CH, generator=g)) * 0.2
     if path is not None:
@@ -126,13 +105,7 @@ class DistsVGG:
     def __init__(self, weights, device):
         sd = load_weights(weights)
         self.device = torch.device(device)
-        self.conv = []
-        for i, (cin, cout) in zip(CONV_IDX, CONV_CH):
-            w = sd[f"features.{i}.weight"].permute(0, 2, 3, 1)                    # (Cout, ky, kx, cin)
-            if cin % 32:
-                w = torch.cat([w, torch.zeros(cout, 3, 3, 32 - cin % 32)], dim=3)
-            cin_p = w.shape[3]
-            self.conv.append((w.reshape(cout, 9 * cin_p).contiguous().to(self.device), sd[f"features.{i}.bias"].to(self.device), cin_p, cout))
+        self.conv = vgg_conv(sd, self.device)
         alpha, beta = torch.split(sd["alpha"], TAP_CH), torch.split(sd["beta"], TAP_CH)
         self.alpha0, self.beta0 = alpha[0].tolist(), beta[0].tolist()
         self.alpha = [v.contiguous().to(self.device) for v in alpha[1:]]
@@ -150,39 +123,29 @@ class DistsVGG:
         hp = ops.halo_planes_buffer(self.device, 2 * Bc, H, W, 32)
         ops.dists_input(a, hp, 0)
         ops.dists_input(b, hp, Bc)
-        h, w, tap = H, W, 0
-        for j, (wt, bias, cin, cout) in enumerate(self.conv):
-            y = ops.conv3x3(hp, wt, bias, 2 * Bc, h, w, cin, cout, precision="split3")       # before its ReLU: the consumers apply it
-            if j in TAP_AFTER:
-                ops.dists_head(ops.dists_moments(y, Bc, h, w), self.alpha[tap], self.beta[tap], h, w, out=terms[tap])
-                tap += 1
-            if j + 1 < len(self.conv):
-                if j in POOL_AFTER:
-                    hp = ops.relu_l2pool_halo(y, 2 * Bc, h, w, cout)
-                    h, w = (h + 1) // 2, (w + 1) // 2
-                else:
-                    hp = ops.relu_pool_halo(y, 2 * Bc, h, w, cout, pool=False)
+        run_vgg16(self.conv, hp, 2 * Bc, H, W,
+                  lambda tap, y, h, w: ops.dists_head(ops.dists_moments(y, Bc, h, w), self.alpha[tap], self.beta[tap], h, w, out=terms[tap]),
+                  lambda y, h, w, c, pooled: ops.relu_l2pool_halo(y, 2 * Bc, h, w, c) if pooled
+                  else ops.relu_pool_halo(y, 2 * Bc, h, w, c, pool=False))
 
     def measure(self, a_u8, b_u8):
         """a_u8, b_u8: (B, H, W, 3) u8 CUDA tensors -> (dists (B,) float64, terms (B, 6, 2) float64: every tap's structure and texture
         term, already divided by W = sum alpha + sum beta; dists = the terms added in tap order, structure before texture), numpy, one
         read-back; None when min(H, W) < 16.  The batch runs in chunks of at most max_pixels = 2^21 pixels, as LpipsVGG.measure does.
         A pair's result depends neither on the chunking nor on its slot."""
-        assert a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.shape == b_u8.shape and a_u8.is_cuda and b_u8.is_cuda
-        assert a_u8.dim() == 4 and a_u8.shape[3] == 3 and a_u8.shape[0] >= 1
-        B, H, W, _ = a_u8.shape
-        if min(H, W) < MIN_SIDE:
+        pair = checked_pair(a_u8, b_u8, MIN_SIDE)
+        if pair is None:
             return None
-        a_u8, b_u8 = a_u8.contiguous(), b_u8.contiguous()
-        step = max(1, int(self.max_pixels) // (2 * H * W))
+        B, H, W, _ = a_u8.shape
         res = torch.empty(B, 25, dtype=torch.int64, device=self.device)       # per pair: 5 x 2 fp64 bit patterns, then 3 x 5 integers
-        for s in range(0, B, step):
-            n = min(step, B - s)
+
+        def one(s, n):
             terms = torch.empty(5, n, 2, dtype=torch.float64, device=self.device)
             m0 = torch.empty(n, 3, 5, dtype=torch.int64, device=self.device)
-            self._chunk(a_u8[s:s + n], b_u8[s:s + n], terms, m0)
+            self._chunk(pair[0][s:s + n], pair[1][s:s + n], terms, m0)
             res[s:s + n, :10] = terms.view(torch.int64).permute(1, 0, 2).reshape(n, 10)
             res[s:s + n, 10:] = m0.view(n, 15)
+        chunked(one, B, H, W, self.max_pixels)
         raw = res.cpu().numpy()
         out = np.empty((B, 6, 2), dtype=np.float64)
         out[:, 0] = tap0_terms(raw[:, 10:].reshape(B, 3, 5), H * W, self.alpha0, self.beta0)

@@ -64,6 +64,7 @@ import torch
 torch.set_grad_enabled(False)
 
 FIELDS = ("psnr", "ssim", "ms_ssim", "ms_ssim_db")
+PAIR_METRICS = ("lpips", "lpips_alex", "dists")      # the perceptual pair metrics, in the order of their keys in a record
 
 
 def to_u8_hwc_device(x_chw_01):
@@ -103,12 +104,9 @@ def summarise(records, fid_sets=None, clip_sets=None):
         db = None if ms is None else float(0.0 - 10.0 * np.log10(1.0 - ms))
     out = {"images": len(records), "bpp": mean([r["bpp"] for r in records if r["bpp"] is not None]),
            "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
-    if any("lpips" in r for r in records):
-        out["lpips"] = mean([r["lpips"] for r in records if r.get("lpips") is not None])
-    if any("lpips_alex" in r for r in records):
-        out["lpips_alex"] = mean([r["lpips_alex"] for r in records if r.get("lpips_alex") is not None])
-    if any("dists" in r for r in records):
-        out["dists"] = mean([r["dists"] for r in records if r.get("dists") is not None])
+    for k in PAIR_METRICS:
+        if any(k in r for r in records):
+            out[k] = mean([r[k] for r in records if r.get(k) is not None])
     if clip_sets is not None:
         out["clip_sim"] = mean([r["clip_sim"] for r in records])
         out.update(clip_sets.summary("recon", records, "clip_"))
@@ -122,12 +120,9 @@ def summarise(records, fid_sets=None, clip_sets=None):
         out.update({"anchor_bpp": mean([a["bpp"] for a in anchors]),
                     "anchor_psnr": mean([a["psnr"] for a in anchors if isinstance(a["psnr"], float)]), "anchor_ms_ssim": ams,
                     "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
-        if any("lpips" in a for a in anchors):
-            out["anchor_lpips"] = mean([a["lpips"] for a in anchors if a.get("lpips") is not None])
-        if any("lpips_alex" in a for a in anchors):
-            out["anchor_lpips_alex"] = mean([a["lpips_alex"] for a in anchors if a.get("lpips_alex") is not None])
-        if any("dists" in a for a in anchors):
-            out["anchor_dists"] = mean([a["dists"] for a in anchors if a.get("dists") is not None])
+        for k in PAIR_METRICS:
+            if any(k in a for a in anchors):
+                out["anchor_" + k] = mean([a[k] for a in anchors if a.get(k) is not None])
         if clip_sets is not None:
             out["anchor_clip_sim"] = mean([a["clip_sim"] for a in anchors])
             out.update(clip_sets.summary("anchor", [r for r in records if "anchor" in r], "anchor_clip_"))
@@ -235,14 +230,13 @@ class ClipSets:
         return {prefix + k: s[k] for k in ("recall@1", "recall@5", "recall@10", "mrr", "median_rank")}
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=None, dists_model=None, lpips_alex_model=None,
-                 decoded_out=None):
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
     on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back.
-    lpips_model (lpips.LpipsVGG), dists_model (dists.DistsVGG), lpips_alex_model (lpips_alex.LpipsAlex): every record also carries
-    "lpips" / "dists" / "lpips_alex" of the decoded anchor against the original.  decoded_out: a list that receives the decoded anchors
+    pair_metrics: [(key, model)] in record order (lpips.LpipsVGG, lpips_alex.LpipsAlex, dists.DistsVGG): every record also carries
+    `key`, the model's measure of the decoded anchor against the original.  decoded_out: a list that receives the decoded anchors
     (B, H, W, 3) u8 on the device (the FID of the anchor set)."""
     from . import jpeg, jpeg_enc, quality
     B, H, W, _ = a_u8.shape
@@ -256,9 +250,7 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
     if decoded_out is not None:
         decoded_out.append(decoded)
     m = quality.measure(a_u8, decoded)
-    lp = lpips_model.measure(a_u8, decoded) if lpips_model is not None else None
-    la = lpips_alex_model.measure(a_u8, decoded) if lpips_alex_model is not None else None
-    ds = dists_model.measure(a_u8, decoded) if dists_model is not None else None
+    pm = [(k, model.measure(a_u8, decoded)) for k, model in pair_metrics]
     out = []
     for j, ((q, over), data) in enumerate(zip(picks, files)):
         if over is None:      # a fixed quality: over the rate if the container is known and smaller
@@ -266,12 +258,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, lpips_model=Non
         rec = {"codec": "jpeg", "quality": q, "subsampling": int(subsampling), "bytes": len(data), "bpp": 8 * len(data) / (H * W)}
         for k in FIELDS:
             rec[k] = None if m[k] is None else _json_number(m[k][j])
-        if lpips_model is not None:
-            rec["lpips"] = None if lp is None else float(lp[0][j])
-        if lpips_alex_model is not None:
-            rec["lpips_alex"] = None if la is None else float(la[0][j])
-        if dists_model is not None:
-            rec["dists"] = None if ds is None else float(ds[0][j])
+        for k, v in pm:
+            rec[k] = None if v is None else float(v[0][j])
         rec["over_rate"] = bool(over)
         out.append(rec)
     return out
@@ -333,18 +321,16 @@ def main(argv=None):
 
     torch.cuda.set_device(args.gpu_idx)
     dev = torch.device("cuda", args.gpu_idx)
-    lpips_model = None
+    pair_metrics = []      # (key, model) of those asked for, in the order of PAIR_METRICS
     if args.lpips_ckpt:
         from .lpips import LpipsVGG
-        lpips_model = LpipsVGG(args.lpips_ckpt, dev)
-    lpips_alex_model = None
+        pair_metrics.append(("lpips", LpipsVGG(args.lpips_ckpt, dev)))
     if args.lpips_alex_ckpt:
         from .lpips_alex import LpipsAlex
-        lpips_alex_model = LpipsAlex(args.lpips_alex_ckpt, dev)
-    dists_model = None
+        pair_metrics.append(("lpips_alex", LpipsAlex(args.lpips_alex_ckpt, dev)))
     if args.dists_ckpt:
         from .dists import DistsVGG
-        dists_model = DistsVGG(args.dists_ckpt, dev)
+        pair_metrics.append(("dists", DistsVGG(args.dists_ckpt, dev)))
     fid_sets = FidSets(args.fid_ckpt, args.fid_patch, dev) if args.fid_ckpt else None
     clip_sets = ClipSets(args.clip_ckpt, args.small, dev) if args.clip_ckpt else None
     originals = by_stem(glob(os.path.join(args.originals, "*.*")))
@@ -378,13 +364,10 @@ def main(argv=None):
             a = torch.from_numpy(np.stack([m[1] for m in members])).to(dev)
             b = torch.stack([m[2] for m in members])
             m = quality.measure(a, b)
-            lp = lpips_model.measure(a, b) if lpips_model is not None else None
-            la = lpips_alex_model.measure(a, b) if lpips_alex_model is not None else None
-            ds = dists_model.measure(a, b) if dists_model is not None else None
+            pm = [(k, model.measure(a, b)) for k, model in pair_metrics]
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
             decoded = [] if fid_sets is not None or clip_sets is not None or niqe_model is not None else None
-            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, lpips_model, dists_model,
-                                   lpips_alex_model, decoded) if anchor else None
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded) if anchor else None
             if clip_sets is not None:
                 from .search import embedded_clip_codes
                 ua, qa = clip_sets.embed(a)
@@ -408,12 +391,8 @@ def main(argv=None):
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
                 for k in FIELDS:
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
-                if lpips_model is not None:
-                    rec["lpips"] = None if lp is None else float(lp[0][j])
-                if lpips_alex_model is not None:
-                    rec["lpips_alex"] = None if la is None else float(la[0][j])
-                if dists_model is not None:
-                    rec["dists"] = None if ds is None else float(ds[0][j])
+                for k, v in pm:
+                    rec[k] = None if v is None else float(v[0][j])
                 if clip_sets is not None:
                     rec["clip_sim"] = float(sim[j])
                     clip_sets.codes[stem], clip_sets.units["recon"][stem] = qa[j], ub[j]

@@ -7,8 +7,9 @@ split kernels, also under SGIC_GEMM=f32: the path needs the planes layout.  Weig
 synthetic (synth_weights: the tests)."""
 import math
 
-import numpy as np
 import torch
+
+from .perceptual import MAX_PIXELS, LpipsMeasure, conv_matrix, load_state, lpips_canonical_key
 
 # torchvision's alexnet().features: index of every convolution, (Cin, Cout, kernel, stride, pad); a max-pool 3x3 / 2 sits in front of
 # the convolutions at positions POOL_BEFORE; every convolution's ReLU is a tap
@@ -18,7 +19,6 @@ POOL_BEFORE = (1, 2)
 TAP_CH = (64, 192, 384, 256, 256)
 MIN_SIDE = 31                        # the stride-4 convolution and two pools must leave a pixel
 K1_PAD = 384                         # 11 * 11 * 3 = 363 columns of the first patch matrix, padded to whole 32-column slices
-MAX_PIXELS = 1 << 21                 # pixels of one chunk, both sides of its pairs counted (see LpipsAlex.measure)
 
 
 def extents(n):
@@ -39,41 +39,12 @@ def expected_shapes():
     return out
 
 
-def _canonical_key(key):
-    """a checkpoint's key -> the canonical key, or None for a key that is not part of LPIPS-Alex (scaling_layer.*, a classifier)"""
-    parts = key.split(".")
-    if len(parts) == 3 and parts[0] == "features" and parts[2] in ("weight", "bias"):
-        return key
-    if len(parts) == 4 and parts[0] == "net" and parts[1].startswith("slice") and parts[3] in ("weight", "bias"):
-        return f"features.{parts[2]}.{parts[3]}"
-    if len(parts) == 4 and parts[0].startswith("lin") and parts[1] == "model" and parts[2] in ("0", "1") and parts[3] == "weight":
-        return f"{parts[0]}.model.1.weight"
-    return None
-
-
 def load_weights(paths):
     """one or more torch.load-able state dicts (paths, or dicts already loaded) -> the canonical fp32 state dict of
     expected_shapes().  Accepted keys: features.{0,3,6,8,10}.{weight,bias} (torchvision), net.slice{1..5}.{i}.{weight,bias} and
     lin{k}.model.{0,1}.weight (the package's LPIPS.state_dict(), with or without the dropout slot).  Later files win.  Every shape is
     checked; a missing key is named in the error; keys of anything else are ignored."""
-    if isinstance(paths, (str, bytes, dict)) or hasattr(paths, "__fspath__"):
-        paths = [paths]
-    want = expected_shapes()
-    out = {}
-    for p in paths:
-        sd = p if isinstance(p, dict) else torch.load(p, map_location="cpu", weights_only=True)
-        sd = sd.get("state_dict", sd)
-        for key, v in sd.items():
-            ck = _canonical_key(key)
-            if ck is None or ck not in want:
-                continue
-            if tuple(v.shape) != want[ck]:
-                raise ValueError(f"LPIPS-Alex weights: {key} has shape {tuple(v.shape)}, expected {want[ck]}")
-            out[ck] = v.detach().to(torch.float32).contiguous()
-    missing = [k for k in want if k not in out]
-    if missing:
-        raise KeyError(f"LPIPS-Alex weights: missing {', '.join(missing)}")
-    return {k: out[k] for k in want}
+    return load_state(paths, expected_shapes(), lpips_canonical_key, "LPIPS-Alex")
 
 
 def synth_weights(seed, path=None, style="torchvision"):
@@ -102,19 +73,19 @@ def to_reference_keys(sd):
     return out
 
 
-class LpipsAlex:
+class LpipsAlex(LpipsMeasure):
     """weights: load_weights' / synth_weights' dict, or path(s) for load_weights.  The convolution weights are reordered to
-    (Cout, (ky, kx, cin)) once (the first zero-padded from 363 to 384 columns) and split into planes on first use."""
+    (Cout, (ky, kx, cin)) once (the first zero-padded from 363 to 384 columns) and split into planes on first use.  Per input pixel a
+    chunk of measure holds: the first patch operand, 384 * 6 B per 16 pixels = 144 B; the second, 1600 * 6 B per pooled pixel, of
+    which there is one per roughly 64 input pixels = 150 B; the first convolution's output, 16 B; everything behind it is smaller.
+    All are below the 384 B per pixel of lpips.LpipsVGG."""
+    min_side = MIN_SIDE
 
     def __init__(self, weights, device):
         sd = load_weights(weights)
         self.device = torch.device(device)
-        self.conv = []
-        for i, (cin, cout, k, _, _) in zip(CONV_IDX, CONV_CFG):
-            w = sd[f"features.{i}.weight"].permute(0, 2, 3, 1).reshape(cout, k * k * cin)           # (Cout, (ky, kx, cin))
-            if w.shape[1] % 32:
-                w = torch.cat([w, torch.zeros(cout, 32 - w.shape[1] % 32)], dim=1)
-            self.conv.append((w.contiguous().to(self.device), sd[f"features.{i}.bias"].to(self.device), cin, cout))
+        self.conv = [(conv_matrix(sd[f"features.{i}.weight"]).to(self.device), sd[f"features.{i}.bias"].to(self.device), cin, cout)
+                     for i, (cin, cout, _, _, _) in zip(CONV_IDX, CONV_CFG)]
         assert self.conv[0][0].shape[1] == K1_PAD
         self.lin = [sd[f"lin{k}.model.1.weight"].reshape(-1).contiguous().to(self.device) for k in range(5)]
         self.max_pixels = MAX_PIXELS
@@ -144,31 +115,3 @@ class LpipsAlex:
             ops.lpips_head(y, self.lin[j], Bc, h3, w3, out=layers[j])
             if j < 4:
                 hp = ops.relu_pool_halo(y, n, h3, w3, cout, pool=False)
-
-    def measure(self, a_u8, b_u8):
-        """a_u8, b_u8: (B, H, W, 3) u8 CUDA tensors -> (lpips (B,) float64, layers (B, 5) float64: the five taps' distances, lpips =
-        their sum in tap order), numpy, one read-back; None when min(H, W) < 31.  The batch runs in chunks of at most
-        max_pixels = 2^21 pixels (2 Bc H W, both sides counted; at least one pair), so memory does not grow with B.  Per input
-        pixel a chunk holds: the first patch operand, 384 * 6 B per 16 pixels = 144 B; the second, 1600 * 6 B per pooled pixel, of
-        which there is one per roughly 64 input pixels = 150 B; the first convolution's output, 16 B; everything behind it is smaller.
-        All are below the 384 B per pixel of lpips.LpipsVGG.  The halo planes of a geometry are cached (ops.halo_planes_buffer).  A
-        pair's result depends neither on the chunking nor on its slot."""
-        assert a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.shape == b_u8.shape and a_u8.is_cuda and b_u8.is_cuda
-        assert a_u8.dim() == 4 and a_u8.shape[3] == 3 and a_u8.shape[0] >= 1
-        B, H, W, _ = a_u8.shape
-        if min(H, W) < MIN_SIDE:
-            return None
-        a_u8, b_u8 = a_u8.contiguous(), b_u8.contiguous()
-        step = max(1, int(self.max_pixels) // (2 * H * W))
-        layers = torch.empty(5, B, dtype=torch.float64, device=self.device)
-        for s in range(0, B, step):
-            n = min(step, B - s)
-            part = layers[:, s:s + n] if n == B else torch.empty(5, n, dtype=torch.float64, device=self.device)
-            self._chunk(a_u8[s:s + n], b_u8[s:s + n], part)
-            if n != B:
-                layers[:, s:s + n] = part
-        lay = np.ascontiguousarray(layers.cpu().numpy().T)
-        total = lay[:, 0].copy()
-        for k in range(1, 5):
-            total += lay[:, k]
-        return total, lay

@@ -1290,26 +1290,35 @@ def niqe_blocks_u8(x):
     return stats, sharp
 
 
-def lpips_input(img_u8, hp, image_offset=0):
-    """the LPIPS input layer (csrc/lpips.hip): img_u8 (B, H, W, 3) u8 -> the interior of images image_offset .. image_offset+B-1 of
-    hp, a HaloPlanes of (total images, H, W, 32) from halo_planes_buffer; channels 3..31 are zero.  No synchronisation."""
+def _input_halo(symbol, img_u8, hp, image_offset):
     require_gpu()
     assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3
     B, H, W, _ = img_u8.shape
     assert (hp.H, hp.W, hp.C) == (H, W, 32) and 0 <= image_offset and image_offset + B <= hp.B, ((hp.B, hp.H, hp.W, hp.C), img_u8.shape)
-    call("sgic_lpips_input_split3", _p(img_u8), B, H, W, hp.B, int(image_offset), _p(hp.t))
+    call(symbol, _p(img_u8), B, H, W, hp.B, int(image_offset), _p(hp.t))
     return hp
+
+
+def _halo_producer(symbol, x, B, H, W, C, OH, OW, *extra):
+    """x (B*H*W, C) -> the cached HaloPlanes of (B, OH, OW, C), its interior written by `symbol` (extra: its arguments after C)"""
+    require_gpu()
+    x, ldx = _rows(x)
+    assert ldx == C and x.shape == (B * H * W, C), (x.shape, (B, H, W, C))
+    hp = halo_planes_buffer(x.device, B, OH, OW, C)
+    call(symbol, _p(x), B, H, W, C, *extra, _p(hp.t))
+    return hp
+
+
+def lpips_input(img_u8, hp, image_offset=0):
+    """the LPIPS input layer (csrc/lpips.hip): img_u8 (B, H, W, 3) u8 -> the interior of images image_offset .. image_offset+B-1 of
+    hp, a HaloPlanes of (total images, H, W, 32) from halo_planes_buffer; channels 3..31 are zero.  No synchronisation."""
+    return _input_halo("sgic_lpips_input_split3", img_u8, hp, image_offset)
 
 
 def relu_pool_halo(x, B, H, W, C, pool=False):
     """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU, a 2x2 / stride 2 max-pool when pool (an odd last row or
     column is dropped) -> the next 3x3 convolution's zero-halo operand planes (HaloPlanes; csrc/lpips.hip).  C % 32 == 0."""
-    require_gpu()
-    x, ldx = _rows(x)
-    assert ldx == C and x.shape == (B * H * W, C), (x.shape, (B, H, W, C))
-    hp = halo_planes_buffer(x.device, B, H // 2 if pool else H, W // 2 if pool else W, C)
-    call("sgic_relu_pool_halo_split3", _p(x), B, H, W, C, int(bool(pool)), _p(hp.t))
-    return hp
+    return _halo_producer("sgic_relu_pool_halo_split3", x, B, H, W, C, H // 2 if pool else H, W // 2 if pool else W, int(bool(pool)))
 
 
 def lpips_head(feat, w, B, H, W, out=None):
@@ -1333,12 +1342,7 @@ def dists_input(img_u8, hp, image_offset=0):
     """the DISTS input layer (csrc/dists.hip): img_u8 (B, H, W, 3) u8 -> (u / 255 - mean) / std in the interior of images image_offset
     .. image_offset+B-1 of hp, a HaloPlanes of (total images, H, W, 32) from halo_planes_buffer; channels 3..31 are zero.  No
     synchronisation."""
-    require_gpu()
-    assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3
-    B, H, W, _ = img_u8.shape
-    assert (hp.H, hp.W, hp.C) == (H, W, 32) and 0 <= image_offset and image_offset + B <= hp.B, ((hp.B, hp.H, hp.W, hp.C), img_u8.shape)
-    call("sgic_dists_input_split3", _p(img_u8), B, H, W, hp.B, int(image_offset), _p(hp.t))
-    return hp
+    return _input_halo("sgic_dists_input_split3", img_u8, hp, image_offset)
 
 
 def dists_moments_u8(a, b, out=None):
@@ -1360,12 +1364,7 @@ def relu_l2pool_halo(x, B, H, W, C):
     """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU, then DISTS's L2 pool sqrt(hanning3x3(f^2) + 1e-12) at stride
     2 with zero padding 1 (an odd last row or column is kept: ceil(n / 2)) -> the next 3x3 convolution's zero-halo operand planes
     (HaloPlanes; csrc/dists.hip).  C % 32 == 0."""
-    require_gpu()
-    x, ldx = _rows(x)
-    assert ldx == C and x.shape == (B * H * W, C), (x.shape, (B, H, W, C))
-    hp = halo_planes_buffer(x.device, B, (H + 1) // 2, (W + 1) // 2, C)
-    call("sgic_relu_l2pool_halo_split3", _p(x), B, H, W, C, _p(hp.t))
-    return hp
+    return _halo_producer("sgic_relu_l2pool_halo_split3", x, B, H, W, C, (H + 1) // 2, (W + 1) // 2)
 
 
 def dists_moments(feat, B, H, W):
@@ -1430,12 +1429,8 @@ def relu_maxpool3_patches5(x, B, H, W, C):
 def relu_maxpool3_halo(x, B, H, W, C):
     """x (B*H*W, C) fp32, a convolution's output before its ReLU -> ReLU -> max-pool 3x3, stride 2, no padding (floor) -> the next 3x3
     convolution's zero-halo operand planes (HaloPlanes from halo_planes_buffer; csrc/lpips_alex.hip).  C % 32 == 0."""
-    require_gpu()
-    x, ldx = _rows(x)
-    assert ldx == C and x.shape == (B * H * W, C) and H >= 3 and W >= 3, (x.shape, (B, H, W, C))
-    hp = halo_planes_buffer(x.device, B, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C)
-    call("sgic_relu_maxpool3_halo_split3", _p(x), B, H, W, C, _p(hp.t))
-    return hp
+    assert H >= 3 and W >= 3, (H, W)
+    return _halo_producer("sgic_relu_maxpool3_halo_split3", x, B, H, W, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1)
 
 
 def fid_resize299(canvas_u8, desc, out=None):
