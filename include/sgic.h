@@ -216,13 +216,7 @@ int sgic_fake2d_transpose(const float *d_in, long in_seq_stride, float *d_out, i
 /* l2-normalised nearest-code search (titok/quantizer.py:46-61). */
 int sgic_vq_argmin(const float *d_z, int ldz, const float *d_codebook, int ncodes, int dim, int M, int l2norm,
                    int32_t *d_idx, sgic_stream_t stream);
-/* CLIP preprocessing, bit-exact with ToPILImage -> PIL bicubic antialias resize -> center crop ->
- * ToTensor -> Normalize (compress.py:70-71).  Coefficient tables are Pillow's 22-bit fixed-point ints. */
-int sgic_clip_preprocess(const float *d_x, long img_stride, long ch_stride, int ldx, int B, int H, int W, int OH,
-                         int OW, int S, int top, int left, const int32_t *d_bounds_h, const int32_t *d_kk_h,
-                         int ksize_h, const int32_t *d_bounds_v, const int32_t *d_kk_v, int ksize_v,
-                         const float *mean3, const float *std3, uint8_t *d_tmp_u8, uint8_t *d_tmp_h, float *d_out,
-                         sgic_stream_t stream);
+/* (CLIP preprocessing: sgic_clip_preprocess_ragged / sgic_clip_preprocess_u8canvas below.) */
 /* unit-normalise rows + u8 quantise (compress.py:73,77). */
 int sgic_l2norm_u8(const float *d_x, int ldx, int M, int D, float *d_unit, uint8_t *d_q, sgic_stream_t stream);
 
@@ -623,12 +617,18 @@ int sgic_u8canvas_to_f32chw_pad(const uint8_t *d_in, const int32_t *h_hw, float 
  * Pillow's precompute_coeffs (sgic_amd/clip.py pil_coeffs): d_bounds (out_size x 2 int32: first input index, count), d_kk
  * (out_size x ksize 22-bit fixed-point int32, zero past the count); ksize = ceil(2 * max(in_size / out_size, 1)) * 2 + 1 (checked). */
 int sgic_clip_resize_coeffs(int in_size, int out_size, int ksize, int32_t *d_bounds, int32_t *d_kk, sgic_stream_t stream);
-/* Ragged CLIP preprocessing: image b is the top-left H x W region of d_x[b] (strides as sgic_clip_preprocess), with its own resize
- * geometry h_geo[6b .. 6b+5] = (H, W, OH, OW, top, left) (host int32, B x 6; sgic_amd/clip.py resize_geometry) -> d_out (B, 3, S, S),
- * every image bit-identical to sgic_clip_preprocess on it alone.  The coefficient tables are built on the device.  d_work: a device
- * workspace (16-byte aligned) of at least the *bytes sgic_clip_preprocess_ragged_workspace returns (host-only, takes no stream); per
- * image, in batch order: bounds_h (OW x 2 int32), kk_h (OW x ksize_h), bounds_v (OH x 2), kk_v (OH x ksize_v), the u8 image (3 x H x W)
- * and the horizontal pass over the S cropped columns (3 x H x S), each 16-byte aligned. */
+/* CLIP preprocessing of an fp32 batch, bit-exact with ToPILImage -> PIL bicubic antialias resize -> centre crop -> ToTensor ->
+ * Normalize (compress.py:70-71): u8 = trunc((clamp(x, -1, 1) * 0.5 + 0.5) * 255), Pillow's two 8-bit passes with its 22-bit
+ * fixed-point coefficients, (v / 255 - mean) / std.  Image b is the top-left H x W region of d_x[b] (element strides: img_stride
+ * between images, ch_stride between channels, ldx between rows, 1 between columns), with its own resize geometry
+ * h_geo[6b .. 6b+5] = (H, W, OH, OW, top, left) (host int32, B x 6; sgic_amd/clip.py resize_geometry; H, W <= 65535, OH, OW < 2^30)
+ * -> d_out (B, 3, S, S).  An image's bits do not depend on the rest of the batch.  The coefficient tables are built on the device.
+ * The horizontal pass covers the S cropped columns of the source rows the vertical pass reads -- bounds_v[top].first up to
+ * bounds_v[top + S - 1].first + count -- and leaves them as a 3 x rows x S u8 intermediate, rows: a bound of that window computed
+ * on the host from the geometry alone (<= H).  d_work: a device workspace (16-byte aligned) of at least the *bytes
+ * sgic_clip_preprocess_ragged_workspace returns (host-only, takes no stream); per image, in batch order: bounds_h (OW x 2 int32),
+ * kk_h (OW x ksize_h), bounds_v (OH x 2), kk_v (OH x ksize_v), the planar u8 image (3 x H x W) and the intermediate (3 x rows x S),
+ * each 16-byte aligned. */
 int sgic_clip_preprocess_ragged_workspace(int B, const int32_t *h_geo, int S, size_t *bytes);
 int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_stride, int ldx, int B, const int32_t *h_geo, int S,
                                 const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
@@ -636,11 +636,11 @@ int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_strid
 /* CLIP preprocessing straight from the u8 canvas of the ingest: d_canvas (B, Hc, Wc, 3) interleaved RGB, image b its top-left H x W
  * region with h_geo[6b .. 6b+5] = (H, W, OH, OW, top, left) as above (H <= Hc, W <= Wc; bytes of the canvas outside an image are
  * never read) -> d_out (B, 3, S, S) fp32.  The bytes are resampled as they are -- bit-identical to Pillow's
- * `Image.fromarray(u8).resize((OW, OH), BICUBIC)`, centre crop, / 255, (v - mean) / std -- where the fp32 entry points above first
- * truncate `(x * 0.5 + 0.5) * 255` back to u8.  There is no fp32 image and no planar u8 copy: the horizontal pass reads the canvas
- * and covers the S cropped columns of the source rows the vertical pass reads.  d_work: a device workspace (16-byte aligned) of at
- * least the *bytes sgic_clip_preprocess_u8canvas_workspace returns (host-only, takes no stream); per image, in batch order: the four
- * tables as above and the horizontal pass (3 x rows x S u8, rows: a bound of the row window), each 16-byte aligned. */
+ * `Image.fromarray(u8).resize((OW, OH), BICUBIC)`, centre crop, / 255, (v - mean) / std -- where the fp32 entry point above first
+ * truncates `(x * 0.5 + 0.5) * 255` back to u8.  There is no fp32 image and no planar u8 copy: the horizontal pass reads the canvas;
+ * tables, row window, intermediate and vertical pass are those of the fp32 entry point (the same kernels).  d_work: a device
+ * workspace (16-byte aligned) of at least the *bytes sgic_clip_preprocess_u8canvas_workspace returns (host-only, takes no stream);
+ * per image, in batch order: the four tables and the intermediate (3 x rows x S u8) as above, each 16-byte aligned. */
 int sgic_clip_preprocess_u8canvas_workspace(int B, const int32_t *h_geo, int S, size_t *bytes);
 int sgic_clip_preprocess_u8canvas(const uint8_t *d_canvas, int Hc, int Wc, int B, const int32_t *h_geo, int S, const float *mean3,
                                   const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out, sgic_stream_t stream);

@@ -27,7 +27,9 @@ def _bicubic(x):
 
 def pil_coeffs(in_size, out_size):
     """Pillow precompute_coeffs + normalize_coeffs_8bpc for the bicubic filter (double precision on the
-    host, like Pillow).  -> (bounds int32 (out,2), kk int32 (out,ksize), ksize)"""
+    host, like Pillow).  -> (bounds int32 (out,2), kk int32 (out,ksize), ksize)
+    The restatement the device-built tables are tested against (with _bicubic), also used by tools/bench_clip_u8.py: no runtime
+    path calls it, the kernels build their own tables."""
     scale = in_size / out_size
     fscale = max(scale, 1.0)
     support = 2.0 * fscale
@@ -64,6 +66,14 @@ def resize_geometry(H, W, S):
     return OH, OW, top, left
 
 
+def batch_geometry(hw, B, Hmax, Wmax, S, what):
+    """B extents (h, w) inside the Hmax x Wmax `what` -> the checked (B, 6) int32 rows (H, W, OH, OW, top, left) the kernels take"""
+    hw = np.asarray(hw, dtype=np.int64).reshape(B, 2)
+    if (hw <= 0).any() or (hw[:, 0] > Hmax).any() or (hw[:, 1] > Wmax).any():
+        raise ValueError(f"extents {hw.tolist()} outside the {Hmax}x{Wmax} {what}")
+    return np.array([(h, w) + resize_geometry(h, w, S) for h, w in hw.tolist()], dtype=np.int32)
+
+
 class ClipHIP:
     def __init__(self, sd, cfg: ClipConfig, device, p="clip.visual", prune_last=True):
         self.cfg, self.device = cfg, device
@@ -79,56 +89,20 @@ class ClipHIP:
         self.projT = sd[f"{p}.proj"].t().to(device).contiguous()          # (embed_dim, width)
         self.mean = np.asarray(cfg.mean, dtype=np.float32)
         self.std = np.asarray(cfg.std, dtype=np.float32)
-        self._coef = {}
-
-    def _coeffs(self, H, W):
-        key = (H, W)
-        if key not in self._coef:
-            S = self.cfg.image_size
-            OH, OW, top, left = resize_geometry(H, W, S)
-            bh, kh, ksh = pil_coeffs(W, OW)
-            bv, kv, ksv = pil_coeffs(H, OH)
-            d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-            self._coef[key] = (OH, OW, top, left, d(bh), d(kh), ksh, d(bv), d(kv), ksv)
-        return self._coef[key]
 
     def preprocess(self, x, H=None, W=None, hw=None):
         """x (B,3,Hp,Wp) fp32 in [-1,1]; the top-left HxW region of every image is the real (unpadded)
         image (compress.py:266 feeds the UNPADDED image to CLIP).  -> (B,3,S,S) normalised.
         hw: (B, 2) per-image extents instead of one H x W (images of different sizes that pad to one geometry): image b is
-        the top-left hw[b] region of x[b], on its own resize geometry -- bit-identical to preprocess(x[b:b+1], *hw[b])."""
-        if hw is not None:
-            return self._preprocess_ragged(x, hw)
+        the top-left hw[b] region of x[b], on its own resize geometry -- bit-identical to preprocess(x[b:b+1], *hw[b]).
+        The device builds every image's coefficient tables (sgic_clip_preprocess_ragged): six ints per image leave the host."""
         B, _, Hp, Wp = x.shape
-        H, W = H or Hp, W or Wp
         S = self.cfg.image_size
-        OH, OW, top, left, bh, kh, ksh, bv, kv, ksv = self._coeffs(H, W)
-        u8 = torch.empty(B * 3 * H * W, dtype=torch.uint8, device=x.device)
-        th = torch.empty(B * 3 * H * OW, dtype=torch.uint8, device=x.device)
-        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=x.device)
-        import ctypes
-        call("sgic_clip_preprocess", ops._p(x), ctypes.c_long(x.stride(0)), ctypes.c_long(x.stride(1)), int(x.stride(2)),
-             B, H, W, OH, OW, S, top, left, ops._p(bh), ops._p(kh), ksh, ops._p(bv), ops._p(kv), ksv,
-             self.mean.ctypes.data_as(ctypes.c_void_p), self.std.ctypes.data_as(ctypes.c_void_p), ops._p(u8), ops._p(th),
-             ops._p(out))
-        return out
-
-    def _preprocess_ragged(self, x, hw):
-        """the device builds every image's coefficient tables (sgic_clip_preprocess_ragged): six ints per image leave the host"""
-        import ctypes
-        B, _, Hp, Wp = x.shape
-        hw = np.asarray(hw, dtype=np.int64).reshape(B, 2)
-        if (hw <= 0).any() or (hw[:, 0] > Hp).any() or (hw[:, 1] > Wp).any():
-            raise ValueError(f"extents {hw.tolist()} outside the {Hp}x{Wp} batch")
-        S = self.cfg.image_size
-        geo = np.array([(h, w) + resize_geometry(h, w, S) for h, w in hw.tolist()], dtype=np.int32)
-        nbytes = ctypes.c_size_t(0)
-        call("sgic_clip_preprocess_ragged_workspace", B, geo, S, ctypes.byref(nbytes))
-        work = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
-        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=x.device)
-        call("sgic_clip_preprocess_ragged", ops._p(x), ctypes.c_long(x.stride(0)), ctypes.c_long(x.stride(1)), int(x.stride(2)), B, geo, S,
-             self.mean, self.std, ops._p(work), ctypes.c_size_t(nbytes.value), ops._p(out))
-        return out
+        if hw is None:      # one H x W for all: its row, B times
+            geo = np.repeat(batch_geometry((H or Hp, W or Wp), 1, Hp, Wp, S, "batch"), B, axis=0)
+        else:
+            geo = batch_geometry(hw, B, Hp, Wp, S, "batch")
+        return ops.clip_preprocess_ragged(x, geo, S, self.mean, self.std)
 
     def preprocess_u8(self, canvas, hw):
         """canvas (B,Hc,Wc,3) u8 on the device (what DeviceIngest.start leaves there), image b its top-left hw[b] region -> (B,3,S,S)
@@ -137,12 +111,8 @@ class ClipHIP:
         if canvas.dim() != 4 or canvas.shape[3] != 3 or canvas.dtype != torch.uint8:
             raise ValueError(f"canvas must be (B, Hc, Wc, 3) uint8, got {tuple(canvas.shape)} {canvas.dtype}")
         B, Hc, Wc, _ = canvas.shape
-        hw = np.asarray(hw, dtype=np.int64).reshape(B, 2)
-        if (hw <= 0).any() or (hw[:, 0] > Hc).any() or (hw[:, 1] > Wc).any():
-            raise ValueError(f"extents {hw.tolist()} outside the {Hc}x{Wc} canvas")
-        S = self.cfg.image_size
-        geo = np.array([(h, w) + resize_geometry(h, w, S) for h, w in hw.tolist()], dtype=np.int32)
-        return ops.clip_preprocess_u8canvas(canvas.contiguous(), geo, S, self.mean, self.std)
+        geo = batch_geometry(hw, B, Hc, Wc, self.cfg.image_size, "canvas")
+        return ops.clip_preprocess_u8canvas(canvas.contiguous(), geo, self.cfg.image_size, self.mean, self.std)
 
     def tower(self, pre):
         """(B,3,S,S) normalised -> (unit fp32 (B,D), u8 codes (B,D))"""

@@ -456,90 +456,6 @@ extern "C" int sgic_vq_argmin(const float *d_z, int ldz, const float *d_codebook
 }
 
 // ------------------------------------------------------------------------------------------------
-// CLIP preprocessing, bit-exact with ToPILImage -> PIL bicubic(antialias) resize -> center crop ->
-// ToTensor -> Normalize (compress.py:70-71 + open_clip's image transform).
-//   k1: fp32 [-1,1] CHW (row stride ldx) -> u8 = trunc((clamp(x)*0.5+0.5)*255)
-//   k2: horizontal pass u8 -> u8 (Pillow ImagingResampleHorizontal_8bpc, 22-bit fixed-point coeffs)
-//   k3: vertical pass + crop + (v/255 - mean)/std -> fp32 (3, S, S)
-// Coefficient tables (bounds, ints) are built on the host in double precision like Pillow does.
-// ------------------------------------------------------------------------------------------------
-__global__ void to_u8_kernel(const float *__restrict__ x, long img_stride, long ch_stride, int ldx, int B, int H, int W,
-                             uint8_t *__restrict__ out) {
-  const long total = (long)B * 3 * H * W;
-  GRID_STRIDE(i, total) {
-    const int xx = (int)(i % W);
-    long t = i / W;
-    const int yy = (int)(t % H);
-    t /= H;
-    const int c = (int)(t % 3);
-    const int b = (int)(t / 3);
-    float v = x[b * img_stride + c * ch_stride + (long)yy * ldx + xx];
-    v = fminf(fmaxf(v, -1.f), 1.f);
-    v = (v * 0.5f + 0.5f) * 255.f;
-    out[i] = (uint8_t)v;  // .byte() truncates
-  }
-}
-
-__global__ void resize_h_kernel(const uint8_t *__restrict__ in, int B3, int H, int W, int OW, const int *__restrict__ bounds,
-                                const int *__restrict__ kk, int ksize, uint8_t *__restrict__ out) {
-  const long total = (long)B3 * H * OW;
-  GRID_STRIDE(i, total) {
-    const int xx = (int)(i % OW);
-    const long row = i / OW;  // (b*3+c)*H + y
-    const int xmin = bounds[2 * xx], cnt = bounds[2 * xx + 1];
-    int ss = 1 << 21;
-    const uint8_t *p = in + row * W + xmin;
-    const int *k = kk + xx * ksize;
-    for (int x = 0; x < cnt; x++) ss += (int)p[x] * k[x];
-    ss >>= 22;
-    out[i] = (uint8_t)(ss < 0 ? 0 : (ss > 255 ? 255 : ss));
-  }
-}
-
-__global__ void resize_v_crop_norm_kernel(const uint8_t *__restrict__ in, int B, int H, int OW, int S, int top, int left,
-                                          const int *__restrict__ bounds, const int *__restrict__ kk, int ksize,
-                                          float m0, float m1, float m2, float s0, float s1, float s2,
-                                          float *__restrict__ out) {
-  const long total = (long)B * 3 * S * S;
-  GRID_STRIDE(i, total) {
-    const int xx = (int)(i % S);
-    long t = i / S;
-    const int yy = (int)(t % S);
-    t /= S;
-    const int c = (int)(t % 3);
-    const int b = (int)(t / 3);
-    const int oy = yy + top, ox = xx + left;
-    const int ymin = bounds[2 * oy], cnt = bounds[2 * oy + 1];
-    const int *k = kk + oy * ksize;
-    const uint8_t *p = in + ((long)(b * 3 + c) * H + ymin) * OW + ox;
-    int ss = 1 << 21;
-    for (int y = 0; y < cnt; y++) ss += (int)p[(long)y * OW] * k[y];
-    ss >>= 22;
-    const int u = ss < 0 ? 0 : (ss > 255 ? 255 : ss);
-    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    out[i] = ((float)u / 255.0f - mean) / sd;
-  }
-}
-
-extern "C" int sgic_clip_preprocess(const float *d_x, long img_stride, long ch_stride, int ldx, int B, int H, int W,
-                                    int OH, int OW, int S, int top, int left, const int32_t *d_bounds_h,
-                                    const int32_t *d_kk_h, int ksize_h, const int32_t *d_bounds_v, const int32_t *d_kk_v,
-                                    int ksize_v, const float *mean3, const float *std3, uint8_t *d_tmp_u8,
-                                    uint8_t *d_tmp_h, float *d_out, sgic_stream_t stream) {
-  SGIC_REQUIRE(d_x && d_tmp_u8 && d_tmp_h && d_out && mean3 && std3 && B > 0 && H > 0 && W > 0 && S > 0, "args");
-  SGIC_REQUIRE(top >= 0 && left >= 0 && top + S <= OH && left + S <= OW, "crop window");
-  SGIC_REQUIRE(d_bounds_h && d_kk_h && d_bounds_v && d_kk_v, "coefficient tables");
-  hipStream_t st = to_stream(stream);
-  to_u8_kernel<<<ew_grid((long)B * 3 * H * W), 256, 0, st>>>(d_x, img_stride, ch_stride, ldx, B, H, W, d_tmp_u8);
-  resize_h_kernel<<<ew_grid((long)B * 3 * H * OW), 256, 0, st>>>(d_tmp_u8, B * 3, H, W, OW, d_bounds_h, d_kk_h, ksize_h,
-                                                                d_tmp_h);
-  resize_v_crop_norm_kernel<<<ew_grid((long)B * 3 * S * S), 256, 0, st>>>(d_tmp_h, B, H, OW, S, top, left, d_bounds_v,
-                                                                          d_kk_v, ksize_v, mean3[0], mean3[1], mean3[2],
-                                                                          std3[0], std3[1], std3[2], d_out);
-  return sgic::check_launch("clip_preprocess");
-}
-
-// ------------------------------------------------------------------------------------------------
 // CLIP head: unit-normalise each row and u8-quantise  q = clip(rint((z*0.5+0.5)*255), 0, 255)
 // (compress.py:73,77)
 // ------------------------------------------------------------------------------------------------
@@ -735,11 +651,17 @@ extern "C" int sgic_u8canvas_to_f32chw_pad(const uint8_t *d_in, const int32_t *h
 }
 
 // ------------------------------------------------------------------------------------------------
-// Ragged CLIP preprocessing: every image of the batch has its own resize geometry (H, W, OH, OW, top, left) and its own
-// Pillow bicubic tables, BUILT ON THE DEVICE in double precision in the operation order of Pillow's precompute_coeffs +
+// CLIP preprocessing, bit-exact with ToPILImage -> PIL bicubic(antialias) resize -> centre crop -> ToTensor -> Normalize
+// (compress.py:70-71 + open_clip's image transform).  Every image of the batch has its own resize geometry (H, W, OH, OW, top, left)
+// and its own Pillow bicubic tables, BUILT ON THE DEVICE in double precision in the operation order of Pillow's precompute_coeffs +
 // normalize_coeffs_8bpc (clip.py pil_coeffs; this file is built with -ffp-contract=off and the divisions are correctly
-// rounded), so only six ints per image leave the host.  The pixel passes are those of sgic_clip_preprocess, per image, the
-// horizontal one restricted to the S columns the centre crop keeps: bit-identical to sgic_clip_preprocess on the image alone.
+// rounded), so only six ints per image leave the host.  Per chunk of RAGGED_CHUNK images:
+//   tables:     bounds (first input index, count) and 22-bit fixed-point coefficients of both passes
+//   horizontal: u8 -> u8 (Pillow's ImagingResampleHorizontal_8bpc) over the S columns the centre crop keeps and only the source rows
+//               the vertical pass reads, bounds_v[top].xmin up to bounds_v[top + S - 1].xmin + count (both ends are non-decreasing in
+//               the output index): the intermediate is 3 x rows x S u8.  The one stage that depends on where the pixels come from:
+//               an fp32 image in [-1, 1] (truncated to a planar u8 copy first, as ToPILImage does) or the u8 canvas of the ingest
+//   vertical:   u8 -> (v / 255 - mean) / std fp32 (3, S, S)
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double pil_bicubic(double x) {
   const double a = -0.5;
@@ -794,25 +716,47 @@ extern "C" int sgic_clip_resize_coeffs(int in_size, int out_size, int ksize, int
   return sgic::check_launch("pil_coeffs_kernel");
 }
 
-struct ClipRaggedImg {
+#define U8C_TILE_PX 4096   // canvas route: source pixels of a row held in LDS at a time (three planes: 12 KiB)
+#define U8C_THREADS 256
+// OH, OW < 2^30: a bounds table is indexed with the int 2 * index + 1 and the table kernel counts OW + OH rows in an int; every
+// other expression over OH, OW, ksize and the offsets is 64-bit or a double
+#define CLIP_MAX_OUT 0x3fffffff
+
+struct ClipImg {
   int g[8];            // H, W, OH, OW, top, left, ksize_h, ksize_v
+  int rows_cap;        // rows of the intermediate: an upper bound of the row window, from the geometry alone
+  int tile;            // canvas route: output columns a workgroup resamples from one LDS fill (<= U8C_THREADS)
   long long off[6];    // workspace byte offsets: bounds_h (OW x 2 int32), kk_h (OW x ksize_h), bounds_v (OH x 2), kk_v (OH x ksize_v),
-                       // the u8 copy (3 x H x W) and the horizontal-pass output (3 x H x S)
+                       // the planar u8 copy (3 x H x W; fp32 route only, empty on the canvas route) and the horizontal-pass
+                       // output (3 x rows_cap x S)
 };
 
-struct ClipRaggedChunk {
-  ClipRaggedImg img[RAGGED_CHUNK];
+struct ClipChunk {
+  ClipImg img[RAGGED_CHUNK];
 };
 
-// image b's slice of the workspace, at byte offset *off (advanced past it): its four tables, its u8 copy, its horizontal-pass output,
-// each 16-byte aligned
-static int clip_ragged_image(const int32_t *q, int S, long long *off, ClipRaggedImg *m) {
+// the window of n consecutive outputs of an in_size -> out_size resample spans fewer than (n - 1) * scale + 2 * support + 1 inputs
+// (first index > centre_0 - support - 0.5, end <= centre_{n-1} + support + 0.5; clamping to [0, in_size] only shrinks it)
+static double u8c_span_bound(int in_size, int out_size, int n) {
+  const double scale = (double)in_size / (double)out_size;
+  return (double)(n - 1) * scale + 4.0 * (scale > 1.0 ? scale : 1.0) + 1.0;
+}
+
+// one image's geometry (func: the entry point it is checked for) and its slice of the workspace, at byte offset *off (advanced past
+// it): its four tables, its planar u8 copy if the route has one, its horizontal-pass output, each 16-byte aligned
+static int clip_image(const char *func, const int32_t *q, int S, bool planar, long long *off, ClipImg *m) {
   const int H = q[0], W = q[1], OH = q[2], OW = q[3], top = q[4], left = q[5];
-  SGIC_REQUIRE(H > 0 && W > 0 && OH > 0 && OW > 0 && H <= 65535 && W <= 65535 && OH <= 65535 && OW <= 65535, "image geometry");
-  SGIC_REQUIRE(top >= 0 && left >= 0 && top + S <= OH && left + S <= OW, "crop window");
+  SGIC_REQUIRE_AS(func, H > 0 && W > 0 && OH > 0 && OW > 0 && H <= 65535 && W <= 65535 && OH <= CLIP_MAX_OUT && OW <= CLIP_MAX_OUT,
+                  "image geometry");
+  SGIC_REQUIRE_AS(func, top >= 0 && left >= 0 && S <= OH && S <= OW && top <= OH - S && left <= OW - S, "crop window");
   m->g[0] = H, m->g[1] = W, m->g[2] = OH, m->g[3] = OW, m->g[4] = top, m->g[5] = left;
   m->g[6] = pil_ksize(W, OW), m->g[7] = pil_ksize(H, OH);
-  const long long size[6] = {8LL * OW, 4LL * OW * m->g[6], 8LL * OH, 4LL * OH * m->g[7], 3LL * H * W, 3LL * H * S};
+  m->rows_cap = (int)std::min((double)H, std::floor(u8c_span_bound(H, OH, S)) + 2.0);
+  // the largest tile whose window is sure to fit one LDS fill; a window that does not fit (one output with more than U8C_TILE_PX
+  // taps) is resampled in several fills
+  const double per = (double)W / (double)OW, room = (double)U8C_TILE_PX - u8c_span_bound(W, OW, 1);
+  m->tile = room > 0.0 ? (int)std::min((double)std::min(S, U8C_THREADS), std::floor(room / per) + 1.0) : 1;
+  const long long size[6] = {8LL * OW, 4LL * OW * m->g[6], 8LL * OH, 4LL * OH * m->g[7], planar ? 3LL * H * W : 0LL, 3LL * m->rows_cap * S};
   for (int k = 0; k < 6; k++) {
     m->off[k] = *off;
     *off += (size[k] + 15) & ~15LL;
@@ -820,21 +764,40 @@ static int clip_ragged_image(const int32_t *q, int S, long long *off, ClipRagged
   return 0;
 }
 
-template <class Chunk>   // ClipRaggedChunk, or ClipU8Chunk of the u8-canvas path below: g[] and off[0..3] mean the same in both
-__global__ void clip_ragged_coeffs_kernel(Chunk ch, uint8_t *__restrict__ work) {
-  const auto &m = ch.img[blockIdx.y];
+__global__ void clip_ragged_coeffs_kernel(ClipChunk ch, uint8_t *__restrict__ work) {
+  const ClipImg &m = ch.img[blockIdx.y];
   const int H = m.g[0], W = m.g[1], OH = m.g[2], OW = m.g[3];
   int *bh = reinterpret_cast<int *>(work + m.off[0]), *kh = reinterpret_cast<int *>(work + m.off[1]);
   int *bv = reinterpret_cast<int *>(work + m.off[2]), *kv = reinterpret_cast<int *>(work + m.off[3]);
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < OW + OH; t += gridDim.x * blockDim.x) {
-    if (t < OW) pil_coeff_row(W, OW, m.g[6], t, bh, kh);
-    else pil_coeff_row(H, OH, m.g[7], t - OW, bv, kv);
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < OW + OH; t += (long)gridDim.x * blockDim.x) {
+    if (t < OW) pil_coeff_row(W, OW, m.g[6], (int)t, bh, kh);
+    else pil_coeff_row(H, OH, m.g[7], (int)t - OW, bv, kv);
   }
 }
 
-__global__ void clip_ragged_to_u8_kernel(const float *__restrict__ x, long img_stride, long ch_stride, int ldx, ClipRaggedChunk ch,
+// the tail of Pillow's 8bpc passes: the accumulator starts at half an output unit (22 fractional bits) and ends as a clamped byte
+__device__ __forceinline__ int pil_acc_to_u8(int ss) {
+  ss >>= 22;
+  return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+}
+
+// one output sample of one channel: cnt taps p[0], p[stride], ... against the 22-bit coefficients k
+__device__ __forceinline__ int pil_resample_u8(const uint8_t *__restrict__ p, long stride, const int *__restrict__ k, int cnt) {
+  int ss = 1 << 21;
+  for (int t = 0; t < cnt; t++) ss += (int)p[t * stride] * k[t];
+  return pil_acc_to_u8(ss);
+}
+
+// the source rows the vertical pass reads for output rows top .. top + S - 1 (bv: its bounds table): first row *r0 -> their number
+__device__ __forceinline__ int clip_row_window(const ClipImg &m, const int *__restrict__ bv, int S, int *r0) {
+  const int top = m.g[4];
+  *r0 = bv[2 * top];
+  return min(bv[2 * (top + S - 1)] + bv[2 * (top + S - 1) + 1] - *r0, m.rows_cap);
+}
+
+__global__ void clip_ragged_to_u8_kernel(const float *__restrict__ x, long img_stride, long ch_stride, int ldx, ClipChunk ch,
                                          uint8_t *__restrict__ work) {
-  const ClipRaggedImg &m = ch.img[blockIdx.y];
+  const ClipImg &m = ch.img[blockIdx.y];
   const int H = m.g[0], W = m.g[1];
   const float *src = x + (long)blockIdx.y * img_stride;
   uint8_t *out = work + m.off[4];
@@ -851,151 +814,25 @@ __global__ void clip_ragged_to_u8_kernel(const float *__restrict__ x, long img_s
   }
 }
 
-__global__ void clip_ragged_resize_h_kernel(ClipRaggedChunk ch, int S, uint8_t *__restrict__ work) {
-  const ClipRaggedImg &m = ch.img[blockIdx.y];
-  const int H = m.g[0], W = m.g[1], left = m.g[5], ksize = m.g[6];
+__global__ void clip_ragged_resize_h_kernel(ClipChunk ch, int S, uint8_t *__restrict__ work) {
+  const ClipImg &m = ch.img[blockIdx.y];
+  const int H = m.g[0], W = m.g[1], left = m.g[5], ksize = m.g[6], rows_cap = m.rows_cap;
   const int *bounds = reinterpret_cast<const int *>(work + m.off[0]), *kk = reinterpret_cast<const int *>(work + m.off[1]);
+  int r0;
+  const int rows = clip_row_window(m, reinterpret_cast<const int *>(work + m.off[2]), S, &r0);
   const uint8_t *in = work + m.off[4];
   uint8_t *out = work + m.off[5];
-  const long total = 3L * H * S;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % S) + left;
-    const long row = i / S;  // c*H + y
-    const int xmin = bounds[2 * ox], cnt = bounds[2 * ox + 1];
-    int ss = 1 << 21;
-    const uint8_t *p = in + row * W + xmin;
-    const int *k = kk + (long)ox * ksize;
-    for (int x = 0; x < cnt; x++) ss += (int)p[x] * k[x];
-    ss >>= 22;
-    out[i] = (uint8_t)(ss < 0 ? 0 : (ss > 255 ? 255 : ss));
-  }
-}
-
-__global__ void clip_ragged_resize_v_norm_kernel(ClipRaggedChunk ch, int S, const uint8_t *__restrict__ work, float m0, float m1, float m2,
-                                                 float s0, float s1, float s2, float *__restrict__ out) {
-  const ClipRaggedImg &m = ch.img[blockIdx.y];
-  const int H = m.g[0], top = m.g[4], ksize = m.g[7];
-  const int *bounds = reinterpret_cast<const int *>(work + m.off[2]), *kk = reinterpret_cast<const int *>(work + m.off[3]);
-  const uint8_t *in = work + m.off[5];
-  float *dst = out + (long)blockIdx.y * 3 * S * S;
-  const long total = 3L * S * S;
+  const long total = 3L * rows_cap * S;   // i: the intermediate's own index, (c * rows_cap + r) * S + xx; rows past the window stay unwritten
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int xx = (int)(i % S);
-    const long t = i / S;
-    const int yy = (int)(t % S);
-    const int c = (int)(t / S);
-    const int oy = yy + top;
-    const int ymin = bounds[2 * oy], cnt = bounds[2 * oy + 1];
-    const int *k = kk + (long)oy * ksize;
-    const uint8_t *p = in + ((long)c * H + ymin) * S + xx;
-    int ss = 1 << 21;
-    for (int y = 0; y < cnt; y++) ss += (int)p[(long)y * S] * k[y];
-    ss >>= 22;
-    const int u = ss < 0 ? 0 : (ss > 255 ? 255 : ss);
-    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    dst[i] = ((float)u / 255.0f - mean) / sd;
+    const int t = (int)(i / S);           // < 3 * rows_cap <= 3 * 65535
+    const int c = (t >= rows_cap) + (t >= 2 * rows_cap);
+    const int r = t - c * rows_cap;
+    if (r >= rows) continue;
+    const int ox = xx + left;
+    const int xmin = bounds[2 * ox], cnt = bounds[2 * ox + 1];
+    out[i] = (uint8_t)pil_resample_u8(in + ((long)c * H + r0 + r) * W + xmin, 1, kk + (long)ox * ksize, cnt);
   }
-}
-
-extern "C" int sgic_clip_preprocess_ragged_workspace(int B, const int32_t *h_geo, int S, size_t *bytes) {
-  SGIC_REQUIRE(B > 0 && h_geo && S > 0 && bytes, "args");
-  long long off = 0;
-  ClipRaggedImg m;
-  for (int b = 0; b < B; b++) {
-    const int rc = clip_ragged_image(h_geo + 6 * b, S, &off, &m);
-    if (rc) return rc;
-  }
-  *bytes = (size_t)off;
-  return 0;
-}
-
-extern "C" int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_stride, int ldx, int B, const int32_t *h_geo, int S,
-                                           const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
-                                           sgic_stream_t stream) {
-  SGIC_REQUIRE(d_x && h_geo && d_work && d_out && mean3 && std3 && B > 0 && S > 0, "args");
-  SGIC_REQUIRE((((uintptr_t)d_work) & 15) == 0, "workspace alignment");
-  hipStream_t st = to_stream(stream);
-  const auto gx = [](long n) { return (unsigned)std::min((n + 255) / 256, 1024L); };
-  long long off = 0;
-  for (int c0 = 0; c0 < B; c0 += RAGGED_CHUNK) {
-    const int n = std::min(RAGGED_CHUNK, B - c0);
-    ClipRaggedChunk ch{};
-    long mx_tab = 0, mx_u8 = 0, mx_th = 0;
-    for (int j = 0; j < n; j++) {
-      ClipRaggedImg &m = ch.img[j];
-      const int rc = clip_ragged_image(h_geo + 6 * (c0 + j), S, &off, &m);
-      if (rc) return rc;
-      SGIC_REQUIRE((size_t)off <= work_bytes, "workspace too small (sgic_clip_preprocess_ragged_workspace)");
-      SGIC_REQUIRE(m.g[1] <= ldx, "image wider than the row stride");
-      mx_tab = std::max(mx_tab, (long)m.g[2] + m.g[3]);
-      mx_u8 = std::max(mx_u8, 3L * m.g[0] * m.g[1]);
-      mx_th = std::max(mx_th, 3L * m.g[0] * S);
-    }
-    clip_ragged_coeffs_kernel<<<dim3(cdiv((size_t)mx_tab, 64), n), 64, 0, st>>>(ch, d_work);
-    int rc = sgic::check_launch("clip_ragged_coeffs_kernel");
-    if (rc) return rc;
-    clip_ragged_to_u8_kernel<<<dim3(gx(mx_u8), n), 256, 0, st>>>(d_x + (long)c0 * img_stride, img_stride, ch_stride, ldx, ch, d_work);
-    rc = sgic::check_launch("clip_ragged_to_u8_kernel");
-    if (rc) return rc;
-    clip_ragged_resize_h_kernel<<<dim3(gx(mx_th), n), 256, 0, st>>>(ch, S, d_work);
-    rc = sgic::check_launch("clip_ragged_resize_h_kernel");
-    if (rc) return rc;
-    clip_ragged_resize_v_norm_kernel<<<dim3(gx(3L * S * S), n), 256, 0, st>>>(ch, S, d_work, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
-                                                                            std3[2], d_out + (long)c0 * 3 * S * S);
-    rc = sgic::check_launch("clip_ragged_resize_v_norm_kernel");
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// CLIP preprocessing straight from the u8 canvas of the ingest (B, Hc, Wc, 3 interleaved RGB; image b is the top-left H_b x W_b
-// region, the rest of the canvas holds stale bytes and is never read): the decoded bytes are resampled AS THEY ARE -- what
-// `preprocess(Image.open(path))` does in the reference's build-images.  No fp32 image, no planar u8 copy; tables and pixel
-// arithmetic are those of the ragged path above.  The horizontal pass covers the S columns the crop keeps and only the source rows
-// the vertical pass reads, bounds_v[top].xmin up to bounds_v[top + S - 1].xmin + count (both bounds are non-decreasing in the output
-// index): the intermediate is 3 x rows x S u8.  A workgroup takes one source row: it loads the segment of the row its output
-// columns read with 16-byte loads, de-interleaves it into three planes in LDS, and every lane resamples one output column of the
-// three channels from there.
-// ------------------------------------------------------------------------------------------------
-#define U8C_TILE_PX 4096   // source pixels of a row held in LDS at a time (three planes: 12 KiB)
-#define U8C_THREADS 256
-
-struct ClipU8Img {
-  int g[8];            // H, W, OH, OW, top, left, ksize_h, ksize_v
-  int rows_cap;        // rows of the intermediate: an upper bound of the row window, from the geometry alone
-  int tile;            // output columns a workgroup resamples from one LDS fill (<= U8C_THREADS)
-  long long off[5];    // workspace byte offsets: bounds_h, kk_h, bounds_v, kk_v, the horizontal-pass output (3 x rows_cap x S)
-};
-
-struct ClipU8Chunk {
-  ClipU8Img img[RAGGED_CHUNK];
-};
-
-// the window of n consecutive outputs of an in_size -> out_size resample spans fewer than (n - 1) * scale + 2 * support + 1 inputs
-// (first index > centre_0 - support - 0.5, end <= centre_{n-1} + support + 0.5; clamping to [0, in_size] only shrinks it)
-static double u8c_span_bound(int in_size, int out_size, int n) {
-  const double scale = (double)in_size / (double)out_size;
-  return (double)(n - 1) * scale + 4.0 * (scale > 1.0 ? scale : 1.0) + 1.0;
-}
-
-static int clip_u8canvas_image(const int32_t *q, int S, long long *off, ClipU8Img *m) {
-  const int H = q[0], W = q[1], OH = q[2], OW = q[3], top = q[4], left = q[5];
-  SGIC_REQUIRE(H > 0 && W > 0 && OH > 0 && OW > 0 && H <= 65535 && W <= 65535 && OH <= 65535 && OW <= 65535, "image geometry");
-  SGIC_REQUIRE(top >= 0 && left >= 0 && top + S <= OH && left + S <= OW, "crop window");
-  m->g[0] = H, m->g[1] = W, m->g[2] = OH, m->g[3] = OW, m->g[4] = top, m->g[5] = left;
-  m->g[6] = pil_ksize(W, OW), m->g[7] = pil_ksize(H, OH);
-  m->rows_cap = (int)std::min((double)H, std::floor(u8c_span_bound(H, OH, S)) + 2.0);
-  // the largest tile whose window is sure to fit one LDS fill; a window that does not fit (one output with more than U8C_TILE_PX
-  // taps) is resampled in several fills
-  const double per = (double)W / (double)OW, room = (double)U8C_TILE_PX - u8c_span_bound(W, OW, 1);
-  m->tile = room > 0.0 ? (int)std::min((double)std::min(S, U8C_THREADS), std::floor(room / per) + 1.0) : 1;
-  const long long size[5] = {8LL * OW, 4LL * OW * m->g[6], 8LL * OH, 4LL * OH * m->g[7], 3LL * m->rows_cap * S};
-  for (int k = 0; k < 5; k++) {
-    m->off[k] = *off;
-    *off += (size[k] + 15) & ~15LL;
-  }
-  return 0;
 }
 
 // nbytes of interleaved RGB starting at a pixel boundary -> px[c][i]: 16-byte loads over the aligned middle, single bytes for the
@@ -1021,16 +858,20 @@ __device__ __forceinline__ void u8c_stage_row(const uint8_t *__restrict__ p, int
   }
 }
 
+// the horizontal pass straight from the u8 canvas of the ingest (B, Hc, Wc, 3 interleaved RGB; image b is the top-left H_b x W_b
+// region, the rest of the canvas holds stale bytes and is never read): the decoded bytes are resampled AS THEY ARE -- what
+// `preprocess(Image.open(path))` does in the reference's build-images.  A workgroup takes one source row: it loads the segment of
+// the row its output columns read with 16-byte loads, de-interleaves it into three planes in LDS, and every lane resamples one
+// output column of the three channels from there.
 __global__ __launch_bounds__(U8C_THREADS) void clip_u8canvas_resize_h_kernel(const uint8_t *__restrict__ canvas, long img_stride, int Wc,
-                                                                             ClipU8Chunk ch, int S, uint8_t *__restrict__ work) {
+                                                                             ClipChunk ch, int S, uint8_t *__restrict__ work) {
   __shared__ __attribute__((aligned(16))) uint8_t px[3][U8C_TILE_PX];
-  const ClipU8Img &m = ch.img[blockIdx.y];
-  const int W = m.g[1], top = m.g[4], left = m.g[5], ksize = m.g[6], tile = m.tile, rows_cap = m.rows_cap;
+  const ClipImg &m = ch.img[blockIdx.y];
+  const int W = m.g[1], left = m.g[5], ksize = m.g[6], tile = m.tile, rows_cap = m.rows_cap;
   const int *bh = reinterpret_cast<const int *>(work + m.off[0]), *kh = reinterpret_cast<const int *>(work + m.off[1]);
-  const int *bv = reinterpret_cast<const int *>(work + m.off[2]);
-  const int r0 = bv[2 * top];
-  const int rows = min(bv[2 * (top + S - 1)] + bv[2 * (top + S - 1) + 1] - r0, rows_cap);
-  uint8_t *out = work + m.off[4];
+  int r0;
+  const int rows = clip_row_window(m, reinterpret_cast<const int *>(work + m.off[2]), S, &r0);
+  uint8_t *out = work + m.off[5];
   const uint8_t *img = canvas + (long)blockIdx.y * img_stride;
   const int tid = threadIdx.x;
   for (int r = blockIdx.x; r < rows; r += gridDim.x) {
@@ -1043,7 +884,7 @@ __global__ __launch_bounds__(U8C_THREADS) void clip_u8canvas_resize_h_kernel(con
       const int ox = left + t0 + (active ? tid : 0);
       const int xmin = bh[2 * ox], xend = xmin + bh[2 * ox + 1];
       const int *k = kh + (long)ox * ksize;
-      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;   // pil_resample_u8's accumulator, three channels per tap
       for (int c0 = w0; c0 < w1; c0 += U8C_TILE_PX) {
         const int n = min(U8C_TILE_PX, w1 - c0);
         __syncthreads();   // the previous fill has been read
@@ -1060,22 +901,22 @@ __global__ __launch_bounds__(U8C_THREADS) void clip_u8canvas_resize_h_kernel(con
         }
       }
       if (active) {
-        a0 >>= 22, a1 >>= 22, a2 >>= 22;
         uint8_t *o = out + (long)r * S + t0 + tid;
-        o[0] = (uint8_t)(a0 < 0 ? 0 : (a0 > 255 ? 255 : a0));
-        o[(long)rows_cap * S] = (uint8_t)(a1 < 0 ? 0 : (a1 > 255 ? 255 : a1));
-        o[2L * rows_cap * S] = (uint8_t)(a2 < 0 ? 0 : (a2 > 255 ? 255 : a2));
+        o[0] = (uint8_t)pil_acc_to_u8(a0);
+        o[(long)rows_cap * S] = (uint8_t)pil_acc_to_u8(a1);
+        o[2L * rows_cap * S] = (uint8_t)pil_acc_to_u8(a2);
       }
     }
   }
 }
 
-__global__ void clip_u8canvas_resize_v_norm_kernel(ClipU8Chunk ch, int S, const uint8_t *__restrict__ work, float m0, float m1, float m2,
-                                                   float s0, float s1, float s2, float *__restrict__ out) {
-  const ClipU8Img &m = ch.img[blockIdx.y];
+// vertical pass over the row window the horizontal stage left (3 x rows_cap x S, its row 0 the source row r0) + normalise
+__global__ void clip_resize_v_norm_kernel(ClipChunk ch, int S, const uint8_t *__restrict__ work, float m0, float m1, float m2, float s0,
+                                          float s1, float s2, float *__restrict__ out) {
+  const ClipImg &m = ch.img[blockIdx.y];
   const int top = m.g[4], ksize = m.g[7], rows_cap = m.rows_cap;
   const int *bounds = reinterpret_cast<const int *>(work + m.off[2]), *kk = reinterpret_cast<const int *>(work + m.off[3]);
-  const uint8_t *in = work + m.off[4];
+  const uint8_t *in = work + m.off[5];
   const int r0 = bounds[2 * top];
   float *dst = out + (long)blockIdx.y * 3 * S * S;
   const long total = 3L * S * S;
@@ -1086,61 +927,108 @@ __global__ void clip_u8canvas_resize_v_norm_kernel(ClipU8Chunk ch, int S, const 
     const int c = (int)(t / S);
     const int oy = yy + top;
     const int ymin = bounds[2 * oy] - r0, cnt = min(bounds[2 * oy + 1], rows_cap - ymin);
-    const int *k = kk + (long)oy * ksize;
-    const uint8_t *p = in + ((long)c * rows_cap + ymin) * S + xx;
-    int ss = 1 << 21;
-    for (int y = 0; y < cnt; y++) ss += (int)p[(long)y * S] * k[y];
-    ss >>= 22;
-    const int u = ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+    const int u = pil_resample_u8(in + ((long)c * rows_cap + ymin) * S + xx, S, kk + (long)oy * ksize, cnt);
     const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
     dst[i] = ((float)u / 255.0f - mean) / sd;
   }
 }
 
-extern "C" int sgic_clip_preprocess_u8canvas_workspace(int B, const int32_t *h_geo, int S, size_t *bytes) {
-  SGIC_REQUIRE(B > 0 && h_geo && S > 0 && bytes, "args");
+static int clip_workspace(const char *func, int B, const int32_t *h_geo, int S, bool planar, size_t *bytes) {
+  SGIC_REQUIRE_AS(func, B > 0 && h_geo && S > 0 && bytes, "args");
   long long off = 0;
-  ClipU8Img m;
+  ClipImg m;
   for (int b = 0; b < B; b++) {
-    const int rc = clip_u8canvas_image(h_geo + 6 * b, S, &off, &m);
+    const int rc = clip_image(func, h_geo + 6 * b, S, planar, &off, &m);
     if (rc) return rc;
   }
   *bytes = (size_t)off;
   return 0;
 }
 
-extern "C" int sgic_clip_preprocess_u8canvas(const uint8_t *d_canvas, int Hc, int Wc, int B, const int32_t *h_geo, int S,
-                                             const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
-                                             sgic_stream_t stream) {
-  SGIC_REQUIRE(d_canvas && h_geo && d_work && d_out && mean3 && std3 && B > 0 && S > 0 && Hc > 0 && Wc > 0, "args");
-  SGIC_REQUIRE((((uintptr_t)d_work) & 15) == 0, "workspace alignment");
-  hipStream_t st = to_stream(stream);
-  const long img_stride = 3L * Hc * Wc;
+static unsigned clip_grid(long n) { return (unsigned)std::min((n + 255) / 256, 1024L); }
+
+// both routes, RAGGED_CHUNK images per launch.  The route brings fits(image) -- the image lies inside its source -- and
+// horizontal(chunk, first image, images, most pixels of an image, most rows_cap), which leaves the row window in the workspace
+template <class Fits, class Horizontal>
+static int clip_preprocess(const char *func, const char *too_small, bool planar, int B, const int32_t *h_geo, int S, const float *mean3,
+                           const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out, hipStream_t st, Fits fits,
+                           Horizontal horizontal) {
+  SGIC_REQUIRE_AS(func, (((uintptr_t)d_work) & 15) == 0, "workspace alignment");
   long long off = 0;
   for (int c0 = 0; c0 < B; c0 += RAGGED_CHUNK) {
     const int n = std::min(RAGGED_CHUNK, B - c0);
-    ClipU8Chunk ch{};
-    long mx_tab = 0, mx_rows = 0;
+    ClipChunk ch{};
+    long mx_tab = 0, mx_px = 0, mx_rows = 0;
     for (int j = 0; j < n; j++) {
-      ClipU8Img &m = ch.img[j];
-      const int rc = clip_u8canvas_image(h_geo + 6 * (c0 + j), S, &off, &m);
+      ClipImg &m = ch.img[j];
+      int rc = clip_image(func, h_geo + 6 * (c0 + j), S, planar, &off, &m);
       if (rc) return rc;
-      SGIC_REQUIRE((size_t)off <= work_bytes, "workspace too small (sgic_clip_preprocess_u8canvas_workspace)");
-      SGIC_REQUIRE(m.g[0] <= Hc && m.g[1] <= Wc, "extent outside the canvas");
+      SGIC_REQUIRE_AS(func, (size_t)off <= work_bytes, too_small);
+      rc = fits(m);
+      if (rc) return rc;
       mx_tab = std::max(mx_tab, (long)m.g[2] + m.g[3]);
+      mx_px = std::max(mx_px, (long)m.g[0] * m.g[1]);
       mx_rows = std::max(mx_rows, (long)m.rows_cap);
     }
     clip_ragged_coeffs_kernel<<<dim3(cdiv((size_t)mx_tab, 64), n), 64, 0, st>>>(ch, d_work);
     int rc = sgic::check_launch("clip_ragged_coeffs_kernel");
     if (rc) return rc;
-    clip_u8canvas_resize_h_kernel<<<dim3((unsigned)std::min(mx_rows, 2048L), n), U8C_THREADS, 0, st>>>(d_canvas + (long)c0 * img_stride,
-                                                                                                     img_stride, Wc, ch, S, d_work);
-    rc = sgic::check_launch("clip_u8canvas_resize_h_kernel");
+    rc = horizontal(ch, c0, n, mx_px, mx_rows);
     if (rc) return rc;
-    clip_u8canvas_resize_v_norm_kernel<<<dim3((unsigned)std::min((3L * S * S + 255) / 256, 1024L), n), 256, 0, st>>>(
-        ch, S, d_work, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], d_out + (long)c0 * 3 * S * S);
-    rc = sgic::check_launch("clip_u8canvas_resize_v_norm_kernel");
+    clip_resize_v_norm_kernel<<<dim3(clip_grid(3L * S * S), n), 256, 0, st>>>(ch, S, d_work, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
+                                                                            std3[2], d_out + (long)c0 * 3 * S * S);
+    rc = sgic::check_launch("clip_resize_v_norm_kernel");
     if (rc) return rc;
   }
   return 0;
+}
+
+extern "C" int sgic_clip_preprocess_ragged_workspace(int B, const int32_t *h_geo, int S, size_t *bytes) {
+  return clip_workspace(__func__, B, h_geo, S, true, bytes);
+}
+
+extern "C" int sgic_clip_preprocess_ragged(const float *d_x, long img_stride, long ch_stride, int ldx, int B, const int32_t *h_geo, int S,
+                                           const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
+                                           sgic_stream_t stream) {
+  SGIC_REQUIRE(d_x && h_geo && d_work && d_out && mean3 && std3 && B > 0 && S > 0, "args");
+  const char *func = __func__;
+  hipStream_t st = to_stream(stream);
+  return clip_preprocess(
+      func, "workspace too small (sgic_clip_preprocess_ragged_workspace)", true, B, h_geo, S, mean3, std3, d_work, work_bytes, d_out, st,
+      [=](const ClipImg &m) -> int {
+        SGIC_REQUIRE_AS(func, m.g[1] <= ldx, "image wider than the row stride");
+        return 0;
+      },
+      [=](const ClipChunk &ch, int c0, int n, long mx_px, long mx_rows) -> int {
+        clip_ragged_to_u8_kernel<<<dim3(clip_grid(3 * mx_px), n), 256, 0, st>>>(d_x + (long)c0 * img_stride, img_stride, ch_stride, ldx, ch,
+                                                                               d_work);
+        const int rc = sgic::check_launch("clip_ragged_to_u8_kernel");
+        if (rc) return rc;
+        clip_ragged_resize_h_kernel<<<dim3(clip_grid(3 * mx_rows * S), n), 256, 0, st>>>(ch, S, d_work);
+        return sgic::check_launch("clip_ragged_resize_h_kernel");
+      });
+}
+
+extern "C" int sgic_clip_preprocess_u8canvas_workspace(int B, const int32_t *h_geo, int S, size_t *bytes) {
+  return clip_workspace(__func__, B, h_geo, S, false, bytes);
+}
+
+extern "C" int sgic_clip_preprocess_u8canvas(const uint8_t *d_canvas, int Hc, int Wc, int B, const int32_t *h_geo, int S,
+                                             const float *mean3, const float *std3, uint8_t *d_work, size_t work_bytes, float *d_out,
+                                             sgic_stream_t stream) {
+  SGIC_REQUIRE(d_canvas && h_geo && d_work && d_out && mean3 && std3 && B > 0 && S > 0 && Hc > 0 && Wc > 0, "args");
+  const char *func = __func__;
+  hipStream_t st = to_stream(stream);
+  const long img_stride = 3L * Hc * Wc;
+  return clip_preprocess(
+      func, "workspace too small (sgic_clip_preprocess_u8canvas_workspace)", false, B, h_geo, S, mean3, std3, d_work, work_bytes, d_out, st,
+      [=](const ClipImg &m) -> int {
+        SGIC_REQUIRE_AS(func, m.g[0] <= Hc && m.g[1] <= Wc, "extent outside the canvas");
+        return 0;
+      },
+      [=](const ClipChunk &ch, int c0, int n, long, long mx_rows) -> int {
+        clip_u8canvas_resize_h_kernel<<<dim3((unsigned)std::min(mx_rows, 2048L), n), U8C_THREADS, 0, st>>>(d_canvas + (long)c0 * img_stride,
+                                                                                                         img_stride, Wc, ch, S, d_work);
+        return sgic::check_launch("clip_u8canvas_resize_h_kernel");
+      });
 }

@@ -998,20 +998,37 @@ def u8canvas_to_f32chw_pad(x_u8, hw, OH, OW):
     return out
 
 
+def _clip_preprocess(entry, src, geo, S, mean, std, device):
+    """the call both CLIP preprocessing routes make: `entry`(*src, B, geo, S, mean, std, workspace, its size, out), the workspace
+    sized by `entry`_workspace"""
+    B, S = len(geo), int(S)
+    geo = np.ascontiguousarray(geo, dtype=np.int32).reshape(B, 6)
+    mean, std = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (mean, std))
+    nbytes = ctypes.c_size_t(0)
+    call(entry + "_workspace", B, geo, S, ctypes.byref(nbytes))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    out = torch.empty(B, 3, S, S, dtype=torch.float32, device=device)
+    call(entry, *src, B, geo, S, mean, std, _p(work), ctypes.c_size_t(nbytes.value), _p(out))
+    return out
+
+
+def clip_preprocess_ragged(x, geo, S, mean, std):
+    """(B,3,Hp,Wp) fp32 in [-1,1] on the device (any batch / channel / row strides, unit column stride), image b its top-left
+    region with geo[b] = (H, W, OH, OW, top, left) (clip.resize_geometry) -> (B,3,S,S) fp32: trunc((x*0.5+0.5)*255) as ToPILImage
+    does, then Pillow's bicubic resize, centre crop, / 255, (v - mean) / std, bit for bit.  mean, std: float32 numpy arrays of three"""
+    assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32 and x.stride(3) == 1 and x.is_cuda and len(geo) == x.shape[0]
+    src = (_p(x), ctypes.c_long(x.stride(0)), ctypes.c_long(x.stride(1)), int(x.stride(2)))
+    return _clip_preprocess("sgic_clip_preprocess_ragged", src, geo, S, mean, std, x.device)
+
+
 def clip_preprocess_u8canvas(x_u8, geo, S, mean, std):
     """(B,Hc,Wc,3) u8 canvas on the device, image b at its top left with geo[b] = (H, W, OH, OW, top, left) (clip.resize_geometry) ->
     (B,3,S,S) fp32: Pillow's bicubic resize of the bytes as they are, centre crop, / 255, (v - mean) / std, bit for bit.  mean, std:
     float32 numpy arrays of three"""
     assert x_u8.dim() == 4 and x_u8.shape[3] == 3 and x_u8.dtype == torch.uint8 and x_u8.is_contiguous() and x_u8.is_cuda
-    B, Hc, Wc, _ = x_u8.shape
-    geo = np.ascontiguousarray(geo, dtype=np.int32).reshape(B, 6)
-    mean, std = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (mean, std))
-    nbytes = ctypes.c_size_t(0)
-    call("sgic_clip_preprocess_u8canvas_workspace", B, geo, int(S), ctypes.byref(nbytes))
-    work = torch.empty(nbytes.value, dtype=torch.uint8, device=x_u8.device)
-    out = torch.empty(B, 3, int(S), int(S), dtype=torch.float32, device=x_u8.device)
-    call("sgic_clip_preprocess_u8canvas", _p(x_u8), Hc, Wc, B, geo, int(S), mean, std, _p(work), ctypes.c_size_t(nbytes.value), _p(out))
-    return out
+    assert len(geo) == x_u8.shape[0]
+    src = (_p(x_u8), int(x_u8.shape[1]), int(x_u8.shape[2]))
+    return _clip_preprocess("sgic_clip_preprocess_u8canvas", src, geo, S, mean, std, x_u8.device)
 
 
 def clip_resize_coeffs(in_size, out_size, device):

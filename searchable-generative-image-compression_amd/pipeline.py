@@ -8,7 +8,6 @@ copies and turns them into host byte strings (slice the end-aligned rANS streams
 Calling `submit(batch i+1)` before `finish(batch i)` hides the host-side byte work under the GPU; `bench.py` times
 exactly this, `compress.py` writes the .c2df files from it.
 """
-import numpy as np
 import torch
 
 
@@ -42,15 +41,8 @@ class CompressPipeline:
         clip_hw = (h, w): the top-left h x w region is the real image the CLIP tower must see (compress.py:266).
         hw: (B, 2) per-image extents instead, for a batch of images of different sizes that pad to one geometry."""
         B, _, H, W = x.shape
-        if hw is not None:
-            hw = np.asarray(hw).reshape(B, 2)
-            if (hw == hw[0]).all():           # one size after all: the uniform kernels
-                clip_hw, hw = (int(hw[0, 0]), int(hw[0, 1])), None
         r = self.codec.encode_device(x, side_stream=self.side)
-        if hw is not None:
-            unit, q = self.clipc.batch_to_codes(x, hw=hw)
-        else:
-            unit, q = self.clipc.batch_to_codes(x, *(clip_hw or (None, None)))
+        unit, q = self.clipc.batch_to_codes(x, *(clip_hw or (None, None)), hw=hw)
         if self.on_unit is not None:
             self.on_unit(unit)
         torch.cuda.current_stream().wait_stream(self.side)

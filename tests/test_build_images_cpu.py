@@ -103,9 +103,10 @@ def _bounds(in_size, out_size):
 
 
 def test_row_window_fits_the_intermediate_the_host_sizes():
-    """the u8-canvas kernels keep 3 x rows_cap x S bytes between the passes, rows_cap bounded on the host from the geometry alone,
-    while the window itself, bounds_v[top].xmin .. bounds_v[top+S-1].xmin + count, exists only on the device.  Over a sweep of
-    geometries the window must fit: the workspace (host-only call, no device) minus the four tables is that buffer."""
+    """the CLIP preprocessing kernels (both routes) keep 3 x rows_cap x S bytes between the passes, rows_cap bounded on the host from
+    the geometry alone, while the window itself, bounds_v[top].xmin .. bounds_v[top+S-1].xmin + count, exists only on the device.
+    Over a sweep of geometries the window must fit: the workspace (host-only call, no device) minus the four tables (and, on the
+    fp32 route, the planar u8 copy) is that buffer."""
     import ctypes
     import sgic_amd  # noqa: F401
     from sgic_amd._lib import call
@@ -124,13 +125,15 @@ def test_row_window_fits_the_intermediate_the_host_sizes():
     for S in (7, 224, 336):
         for H, W in cases:
             OH, OW, top, left = resize_geometry(H, W, S)
-            if max(OH, OW) > 65535:      # refused by the entry point (limits of the ragged path)
+            if max(OH, OW) >= 1 << 30:      # refused by the entry points (2 * index + 1 into a bounds table is an int)
                 continue
             geo = np.array([[H, W, OH, OW, top, left]], dtype=np.int32)
-            nbytes = ctypes.c_size_t(0)
+            nbytes, nbytes_f32 = ctypes.c_size_t(0), ctypes.c_size_t(0)
             call("sgic_clip_preprocess_u8canvas_workspace", 1, geo, S, ctypes.byref(nbytes))
+            call("sgic_clip_preprocess_ragged_workspace", 1, geo, S, ctypes.byref(nbytes_f32))
             tables = a16(8 * OW) + a16(4 * OW * ksize(W, OW)) + a16(8 * OH) + a16(4 * OH * ksize(H, OH))
             rows_cap = (nbytes.value - tables) // (3 * S)          # 3 S >= 21 > the 15 bytes of alignment slack: exact
+            assert (nbytes_f32.value - tables - a16(3 * H * W)) // (3 * S) == rows_cap      # the fp32 route: its planar u8 copy too
             xmin, cnt = _bounds(H, OH)
             rows = int(xmin[top + S - 1] + cnt[top + S - 1] - xmin[top])
             assert 1 <= rows <= rows_cap <= H, (S, H, W, rows, rows_cap)

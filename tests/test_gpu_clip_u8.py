@@ -1,9 +1,15 @@
 """GPU: CLIP preprocessing straight from the u8 canvas of the ingest (ClipHIP.preprocess_u8, sgic_clip_preprocess_u8canvas).  Against
 Pillow on the bytes as they are, bit for bit; against the existing fp32 route on inputs that truncate back to the same bytes; and
 the paths only large geometries take (a window of more than one LDS fill, several tiles of output columns per row)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from clip_pillow_ref import pillow_from_u8 as _pillow  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -26,17 +32,6 @@ def _canvas(shape, ext, rng, outside):
     for j, (h, w) in enumerate(ext):
         c[j, :h, :w] = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
     return c
-
-
-def _pillow(u8_hw3, S, mean, std):
-    """Image.fromarray(u8) -> PIL bicubic resize (shortest side S) -> centre crop -> / 255 -> Normalize: no float round trip"""
-    from PIL import Image
-    H, W, _ = u8_hw3.shape
-    oh, ow = (S, int(S * W / H)) if H <= W else (int(S * H / W), S)
-    pil = Image.fromarray(np.ascontiguousarray(u8_hw3), "RGB").resize((ow, oh), Image.BICUBIC)
-    top, left = int(round((oh - S) / 2.0)), int(round((ow - S) / 2.0))
-    arr = np.asarray(pil)[top:top + S, left:left + S].astype(np.float32) / np.float32(255)
-    return ((arr - np.float32(mean)) / np.float32(std)).transpose(2, 0, 1).astype(np.float32)
 
 
 @pytest.mark.parametrize("shape,ext", [((7, 64, 96, 3), SMALL_EXT), ((3, 517, 640, 3), LARGE_EXT)], ids=["64x96", "517x640"])
@@ -84,6 +79,24 @@ def test_windows_larger_than_one_lds_fill_and_several_tiles_per_row():
         geo = np.array([(h, w) + resize_geometry(h, w, S)], dtype=np.int32)
         got = ops.clip_preprocess_u8canvas(d, geo, S, mean, std).cpu().numpy()
         assert np.array_equal(got[0], _pillow(canvas[0, :h, :w], S, mean, std)), (S, h, w)
+
+
+def test_an_output_side_above_65535_on_both_routes():
+    """a 1 x 30000 image at S = 3 resizes to 3 x 90000: an output side the entry points used to refuse.  Both routes against Pillow,
+    the fp32 one fed values that truncate back to the canvas bytes"""
+    import sgic_amd  # noqa: F401
+    from sgic_amd import ops
+    from sgic_amd.clip import resize_geometry
+    h, w, S = 1, 30000, 3
+    geo = np.array([(h, w) + resize_geometry(h, w, S)], dtype=np.int32)
+    assert tuple(geo[0, 2:4]) == (3, 90000)
+    canvas = np.random.default_rng(54).integers(0, 256, (1, h, w, 3), dtype=np.uint8)
+    mean, std = np.float32([0.48, 0.45, 0.40]), np.float32([0.26, 0.27, 0.28])
+    ref = _pillow(canvas[0], S, mean, std)
+    d = torch.from_numpy(canvas).cuda()
+    assert np.array_equal(ops.clip_preprocess_u8canvas(d, geo, S, mean, std)[0].cpu().numpy(), ref)
+    x = ((d.float() + 0.5) / 255.0 * 2.0 - 1.0).permute(0, 3, 1, 2).contiguous()
+    assert np.array_equal(ops.clip_preprocess_ragged(x, geo, S, mean, std)[0].cpu().numpy(), ref)
 
 
 def test_extents_outside_the_canvas_are_refused(clip):

@@ -6,6 +6,7 @@ Floating point: tolerance 2e-5 * max|ref| (measured 1e-6 ... 3e-6 with both GEMM
 integer outputs (VQ indices, symbols, indexes): mismatch RATE bounds, and the rANS bytes are bit-exact
 for whatever (symbols, indexes) the GPU produced."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +14,9 @@ import torch
 
 from oracle import orc
 from oracle import torch_ref as TR
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from clip_pillow_ref import pillow_from_f32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -146,7 +150,6 @@ def test_batch_invariance(small, enc):
 
 
 def test_clip_preprocess_bit_exact_vs_pillow():
-    from PIL import Image
     import sgic_amd  # noqa
     from sgic_amd import weights as W
     from sgic_amd.clip import ClipHIP
@@ -159,17 +162,18 @@ def test_clip_preprocess_bit_exact_vs_pillow():
         x = synth_images(2, H, W_, 31 + H + W_)
         got = clip.preprocess(x.cuda()).cpu().numpy()
         for b in range(2):
-            u8 = (x[b].clamp(-1, 1).mul(0.5).add(0.5)).mul(255).byte().permute(1, 2, 0).numpy()   # ToPILImage
-            pil = Image.fromarray(u8, "RGB")
-            if H <= W_:
-                oh, ow = 224, int(224 * W_ / H)
-            else:
-                oh, ow = int(224 * H / W_), 224
-            pil = pil.resize((ow, oh), Image.BICUBIC)
-            top, left = int(round((oh - 224) / 2.0)), int(round((ow - 224) / 2.0))
-            arr = np.asarray(pil)[top:top + 224, left:left + 224].astype(np.float32) / np.float32(255)
-            ref = ((arr - mean) / std).transpose(2, 0, 1)
-            assert np.array_equal(got[b], ref.astype(np.float32)), (H, W_, b)
+            assert np.array_equal(got[b], pillow_from_f32(x[b], 224, mean, std)), (H, W_, b)
+    # what compress.py hands over: the batch padded to multiples of 256, H x W the real image.  The padding is not read
+    H, W_ = 300, 437
+    img = synth_images(2, H, W_, 31 + H + W_)
+    outs = []
+    for fill in (-1.0, 0.25):
+        x = torch.full((2, 3, 512, 512), fill)
+        x[:, :, :H, :W_] = img
+        outs.append(clip.preprocess(x.cuda(), H, W_).cpu().numpy())
+    assert np.array_equal(outs[0], outs[1])
+    for b in range(2):
+        assert np.array_equal(outs[0][b], pillow_from_f32(img[b], 224, mean, std)), b
 
 
 def test_clip_tower_vs_torch_ref():

@@ -13,6 +13,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_cases  # noqa: E402
 import jpeg_scans  # noqa: E402
+from clip_pillow_ref import pillow_from_f32, pillow_from_u8  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -54,18 +55,6 @@ def test_device_built_resize_tables_match_pil_coeffs():
         assert dks == ks and np.array_equal(db.cpu().numpy(), b) and np.array_equal(dk.cpu().numpy(), k), (n_in, n_out)
 
 
-def _pillow_clip(x_chw, S, mean, std):
-    """ToPILImage -> PIL bicubic resize (shortest side S) -> centre crop -> ToTensor -> Normalize, as test_gpu_encoder does"""
-    from PIL import Image
-    _, H, W = x_chw.shape
-    u8 = (x_chw.clamp(-1, 1).mul(0.5).add(0.5)).mul(255).byte().permute(1, 2, 0).numpy()
-    oh, ow = (S, int(S * W / H)) if H <= W else (int(S * H / W), S)
-    pil = Image.fromarray(u8, "RGB").resize((ow, oh), Image.BICUBIC)
-    top, left = int(round((oh - S) / 2.0)), int(round((ow - S) / 2.0))
-    arr = np.asarray(pil)[top:top + S, left:left + S].astype(np.float32) / np.float32(255)
-    return ((arr - mean) / std).transpose(2, 0, 1).astype(np.float32)
-
-
 def test_ragged_clip_preprocess_bit_exact_vs_pillow():
     import sgic_amd  # noqa: F401
     from sgic_amd import weights as W
@@ -79,14 +68,44 @@ def test_ragged_clip_preprocess_bit_exact_vs_pillow():
     x = synth_images(len(ext), 1024, 1024, 77)
     got = clip.preprocess(x.cuda(), hw=ext).cpu().numpy()
     for j, (h, w) in enumerate(ext):
-        assert np.array_equal(got[j], _pillow_clip(x[j, :, :h, :w], S, mean, std)), (h, w)
-    # 34 images (two launches): equal to the uniform path on each image alone
+        assert np.array_equal(got[j], pillow_from_f32(x[j, :, :h, :w], S, mean, std)), (h, w)
+    # 34 images (two launches): each equal to Pillow, and to the call on that image alone (an image's bits do not depend on the batch)
     rng = np.random.default_rng(43)
     ext = [tuple(int(v) for v in rng.integers(8, 65, 2)) for _ in range(34)]
-    x = synth_images(len(ext), 64, 64, 78).cuda()
-    got = clip.preprocess(x, hw=ext)
+    x = synth_images(len(ext), 64, 64, 78)
+    got = clip.preprocess(x.cuda(), hw=ext)
     for j, (h, w) in enumerate(ext):
-        assert torch.equal(got[j], clip.preprocess(x[j:j + 1, :, :h, :w].contiguous())[0]), (h, w)
+        assert np.array_equal(got[j].cpu().numpy(), pillow_from_f32(x[j, :, :h, :w], S, mean, std)), (h, w)
+        assert torch.equal(got[j], clip.preprocess(x[j:j + 1, :, :h, :w].contiguous().cuda())[0]), (h, w)
+
+
+def test_fp32_route_reads_only_the_row_window():
+    """S = 3, a 64 x 8 image (OH = 24): the vertical pass reads the source rows bounds_v[top].first .. bounds_v[top + 2].first + count
+    of clip.pil_coeffs(64, 24) and no other.  Rows outside that window change no output bit, one row inside it does"""
+    import sgic_amd  # noqa: F401
+    from sgic_amd import ops
+    from sgic_amd.clip import pil_coeffs, resize_geometry
+    H, Wd, S = 64, 8, 3
+    OH, OW, top, left = resize_geometry(H, Wd, S)
+    assert (OH, OW) == (24, 3) and top in (10, 11)
+    bv, _, _ = pil_coeffs(H, OH)
+    r0, r1 = int(bv[top, 0]), int(bv[top + S - 1].sum())
+    assert 0 < r0 < r1 < H
+    geo = np.array([[H, Wd, OH, OW, top, left]], dtype=np.int32)
+    mean, std = np.float32([0.48, 0.45, 0.40]), np.float32([0.26, 0.27, 0.28])
+    u = np.random.default_rng(46).integers(0, 256, (H, Wd, 3), dtype=np.uint8)
+    to_x = lambda a: ((torch.from_numpy(a).float() + 0.5) / 255.0 * 2.0 - 1.0).permute(2, 0, 1)[None].contiguous().cuda()
+    run = lambda a: ops.clip_preprocess_ragged(to_x(a), geo, S, mean, std)
+    base = run(u)
+    assert np.array_equal(base[0].cpu().numpy(), pillow_from_u8(u, S, mean, std))
+    outside = u.copy()
+    outside[:r0] = 255 - outside[:r0]
+    outside[r1:] = 255 - outside[r1:]
+    assert torch.equal(run(outside), base)
+    inside = u.copy()
+    mid = (r0 + r1) // 2
+    inside[mid] = 255 - inside[mid]
+    assert not torch.equal(run(inside), base)
 
 
 def test_mixed_size_baseline_jpeg_batch_decodes_into_the_canvas():

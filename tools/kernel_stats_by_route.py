@@ -4,9 +4,10 @@ usage: python tools/kernel_stats_by_route.py KERNEL_STATS_CSV"""
 import csv
 import sys
 
-NEW = ("clip_u8canvas_resize_h_kernel", "clip_u8canvas_resize_v_norm_kernel", "ClipU8Chunk")
-OLD = ("u8canvas_to_f32chw_pad_kernel", "clip_ragged_to_u8_kernel", "clip_ragged_resize_h_kernel", "clip_ragged_resize_v_norm_kernel",
-       "ClipRaggedChunk")
+# the table and vertical kernels serve both routes: their mean time per call (over both routes' calls) counts once for each
+SHARED = ("clip_ragged_coeffs_kernel", "clip_resize_v_norm_kernel")
+NEW = ("clip_u8canvas_resize_h_kernel",) + SHARED
+OLD = ("u8canvas_to_f32chw_pad_kernel", "clip_ragged_to_u8_kernel", "clip_ragged_resize_h_kernel") + SHARED
 rows = list(csv.DictReader(open(sys.argv[1])))
 calls = {}
 for name, keys in (("preprocess_u8", NEW), ("via_fp32_image", OLD)):
