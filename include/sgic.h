@@ -689,6 +689,23 @@ int sgic_jpeg_encode_work_bytes(int B, int H, int W, int subsampling, size_t *by
 int sgic_jpeg_encode_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt, uint8_t *d_work,
                            size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, sgic_stream_t stream);
 
+/* The same with optimised Huffman tables: the bytes that `save(format="JPEG", quality, subsampling, optimize=True)` writes after its
+ * SOS header.  Per image the symbols of the scan are counted (dummy blocks included) and libjpeg's jpeg_gen_optimal_table makes the
+ * four tables from the counts, all on the device.  d_huff (B, 4, 272) u8, 4-byte aligned: BITS (16 bytes) and HUFFVAL (256 bytes,
+ * zeros past the table's symbols) of image b's tables in the header's order DC0, AC0, DC1, AC1; d_nval (B, 4) int32: the number of
+ * HUFFVAL entries of each, so a DHT segment is 2 + 2 + 1 + 16 + d_nval bytes.  The host writes the header from them.  A fitted code
+ * may be 16 bits long for any symbol, so a block can take 16 + 11 + 63 * 26 = 1665 bits: cap is at least sgic_jpeg_encode_opt_cap's
+ * (424 per coded block + 2), the workspace sgic_jpeg_encode_opt_work_bytes', and an image has at most 2579559 coded blocks.  Every
+ * other argument, the refusals (also for a null or misaligned d_huff or d_nval) and the overflow contract are those of
+ * sgic_jpeg_encode_batch.  Where a code would be longer than 32 bits before the length limiter (libjpeg ends with an error there; it
+ * takes counts in Fibonacci proportions that sum past 9.2 million in one table), d_err[b] = 2, d_len[b] = 0 and that table's d_nval
+ * entry is -1. */
+int sgic_jpeg_encode_opt_cap(int H, int W, int subsampling, size_t *cap);
+int sgic_jpeg_encode_opt_work_bytes(int B, int H, int W, int subsampling, size_t *bytes);
+int sgic_jpeg_encode_opt_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt, uint8_t *d_work,
+                               size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff,
+                               int32_t *d_nval, sgic_stream_t stream);
+
 /* CLIP text tower front end: out[b*L+l,:] = table[ids[b,l],:] + pos[l,:] (open_clip CLIP.encode_text, reached from
  * search.py:93-97; ids outside [0,vocab) are clamped).  D multiple of 4. */
 int sgic_embed_tokens(const int32_t *d_ids, const float *d_table, const float *d_pos, float *d_out, int B, int L, int D,

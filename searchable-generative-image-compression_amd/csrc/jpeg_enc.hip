@@ -9,6 +9,10 @@
 //          integer atomicOr (order-free, so two runs give the same bytes), words in between are plain stores
 //   count  one workgroup per 4 KiB of the stream: the 0xFF bytes (the 1-bit padding of the last byte included)
 //   emit   the same split: bytes move to their slot, a 0x00 follows every 0xFF, then FF D9, the length and the error word
+// sgic_jpeg_encode_opt_batch writes the file of save(..., optimize=True) instead: the same passes, but bits and pack read the image's
+// own tables from the workspace, and two passes in front of them make those tables:
+//   hist   one thread per block: the symbols its codes would use, counted in LDS, then added to the image's four histograms
+//   tables one wavefront per (image, table): libjpeg's jpeg_gen_optimal_table -> code words, BITS and HUFFVAL
 #include "common.h"
 
 namespace {
@@ -16,9 +20,12 @@ namespace {
 constexpr int NT = 256;
 constexpr int MAX_GRID_Y = 32768;
 constexpr int WORDS_PER_BLOCK = 52;        // a block codes to at most 20 + 63 * 26 = 1658 bits <= 208 bytes
+constexpr int WORDS_PER_BLOCK_OPT = 53;    // fitted tables: any code may have 16 bits, so 16 + 11 + 63 * (16 + 10) = 1665 bits
 constexpr int CHUNK_WORDS = NT * 4;        // words of the bit stream that a workgroup of count / emit takes at a time
 constexpr int MAX_CHUNK_GRID = 1024;
 constexpr unsigned MAX_BLOCKS = 2581110;   // 1664 bits each stay below 2^32: bit offsets within an image are 32-bit
+constexpr unsigned MAX_BLOCKS_OPT = 2579559;   // the same with 1665 bits each
+static_assert((unsigned long long)MAX_BLOCKS_OPT * 1665 < (1ull << 32) && 1665 <= WORDS_PER_BLOCK_OPT * 32, "32-bit bit offsets");
 
 constexpr int ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -86,12 +93,13 @@ struct EPlan {
   int nbchunk;       // CHUNK_WORDS pieces of an image's worst-case bit stream
   size_t words;      // u32 words of one image's bit stream (a multiple of 4, one spare word for the last flush)
   size_t off_qt, off_local, off_csum, off_bits, off_ffsum, off_tot;   // bytes from d_work; the coefficients lie at 0
+  size_t off_hist, off_tabs;   // optimised tables only: TAB_WORDS counters (directly in front of the bit stream) and code words per image
   size_t bytes, cap;
 };
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-bool make_plan(int B, int H, int W, int sub, EPlan *p) {
+bool make_plan(int B, int H, int W, int sub, bool opt, EPlan *p) {
   if (B < 1 || H < 1 || W < 1 || H > 16384 || W > 16384 || sub < 0 || sub > 2) return false;
   p->B = B; p->H = H; p->W = W;
   p->hs = sub == 0 ? 1 : 2;
@@ -103,20 +111,23 @@ bool make_plan(int B, int H, int W, int sub, EPlan *p) {
   p->ny = p->hs * p->vs;
   p->bpm = p->ny + 2;
   const size_t nblk = (size_t)p->mx * p->my * p->bpm;
-  if (nblk > MAX_BLOCKS) return false;
+  if (nblk > (opt ? MAX_BLOCKS_OPT : MAX_BLOCKS)) return false;
   p->nblk = (int)nblk;
   p->nchunk = (int)((nblk + NT - 1) / NT);
-  p->words = (nblk * WORDS_PER_BLOCK + 1 + 3) & ~(size_t)3;
+  const size_t wpb = opt ? WORDS_PER_BLOCK_OPT : WORDS_PER_BLOCK;
+  p->words = (nblk * wpb + 1 + 3) & ~(size_t)3;
   p->nbchunk = (int)((p->words + CHUNK_WORDS - 1) / CHUNK_WORDS);
   size_t o = align16((size_t)B * nblk * 64 * sizeof(int16_t));
   p->off_qt = o;     o += align16((size_t)B * 128 * sizeof(uint16_t));
   p->off_local = o;  o += align16((size_t)B * nblk * sizeof(uint32_t));
   p->off_csum = o;   o += align16((size_t)B * p->nchunk * sizeof(uint32_t));
+  p->off_tabs = o;   o += opt ? (size_t)B * TAB_WORDS * sizeof(uint32_t) : 0;
+  p->off_hist = o;   o += opt ? (size_t)B * TAB_WORDS * sizeof(uint32_t) : 0;
   p->off_bits = o;   o += (size_t)B * p->words * sizeof(uint32_t);
   p->off_ffsum = o;  o += align16((size_t)B * p->nbchunk * sizeof(uint32_t));
   p->off_tot = o;    o += align16((size_t)B * 2 * sizeof(uint32_t));
   p->bytes = o;
-  p->cap = nblk * (2 * WORDS_PER_BLOCK * 4) + 2;
+  p->cap = nblk * (2 * wpb * 4) + 2;
   return true;
 }
 
@@ -257,13 +268,23 @@ __device__ __forceinline__ int dc_before(const EPlan &p, const int16_t *__restri
   return coef[(size_t)(mcu * p.bpm + k) * 64];
 }
 
+// A sink takes the symbols of a block from code_block: sym(i, extra, nb) is the symbol at word i of the table layout (TAB_DC / TAB_AC)
+// followed by nb extra bits.
 struct CountSink {
+  const uint32_t *tab;
   unsigned bits;
-  __device__ __forceinline__ void put(unsigned, int len) { bits += (unsigned)len; }
+  __device__ __forceinline__ void sym(int i, unsigned, int nb) { bits += (tab[i] & 0xff) + (unsigned)nb; }
+};
+
+// counts symbols instead of bits: hist is a workgroup's histogram in LDS, in the table layout
+struct HistSink {
+  unsigned *hist;
+  __device__ __forceinline__ void sym(int i, unsigned, int) { atomicAdd(&hist[i], 1u); }
 };
 
 // MSB first: bit i of the stream is bit 31 - i % 32 of word i / 32
 struct PackSink {
+  const uint32_t *tab;
   uint32_t *words;
   unsigned wi;
   unsigned long long acc;
@@ -285,18 +306,20 @@ struct PackSink {
       acc &= (1ull << n) - 1;
     }
   }
+  __device__ __forceinline__ void sym(int i, unsigned extra, int nb) {
+    const uint32_t e = tab[i];
+    put(((e >> 8) << nb) | extra, (int)(e & 0xff) + nb);
+  }
 };
 
-// the codes of one block: c holds its 64 coefficients in zigzag order (8 x uint4 of i16 pairs), tab the tables in LDS
+// the symbols of one block: c holds its 64 coefficients in zigzag order (8 x uint4 of i16 pairs)
 template <typename Sink>
-__device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int pred, int chroma, const uint32_t *tab) {
-  const uint32_t *dc = tab + TAB_DC + 12 * chroma, *ac = tab + TAB_AC + 256 * chroma;
+__device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int pred, int chroma) {
+  const int dc = TAB_DC + 12 * chroma, ac = TAB_AC + 256 * chroma;
   const int diff = (int)(short)(c[0].x & 0xffff) - pred;
   {
     const int nb = min(32 - __clz(abs(diff)), 11);
-    const uint32_t e = dc[nb];
-    const unsigned extra = (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1);
-    sink.put(((e >> 8) << nb) | extra, (int)(e & 0xff) + nb);
+    sink.sym(dc + nb, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1), nb);
   }
   int run = 0;
 #pragma unroll
@@ -306,20 +329,19 @@ __device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int 
     if (v == 0) {
       ++run;
     } else {
-      const uint32_t zrl = ac[0xF0];
-      for (; run > 15; run -= 16) sink.put(zrl >> 8, (int)(zrl & 0xff));
+      for (; run > 15; run -= 16) sink.sym(ac + 0xF0, 0, 0);
       const int nb = min(32 - __clz(abs(v)), 15);
-      const uint32_t e = ac[(run << 4) | nb];
-      const unsigned extra = (unsigned)(v < 0 ? v - 1 : v) & ((1u << nb) - 1);
-      sink.put(((e >> 8) << nb) | extra, (int)(e & 0xff) + nb);
+      sink.sym(ac + ((run << 4) | nb), (unsigned)(v < 0 ? v - 1 : v) & ((1u << nb) - 1), nb);
       run = 0;
     }
   }
-  if (run) sink.put(ac[0] >> 8, (int)(ac[0] & 0xff));
+  if (run) sink.sym(ac, 0, 0);
 }
 
-__device__ __forceinline__ void stage_tabs(uint32_t *tab) {
-  for (int i = threadIdx.x; i < TAB_WORDS; i += NT) tab[i] = kTabs.w[i];
+// the tables go to LDS: the Annex K ones, or (OPT) those that the tables pass has written for an image
+template <bool OPT>
+__device__ __forceinline__ void stage_tabs(uint32_t *tab, const uint32_t *__restrict__ src) {
+  for (int i = threadIdx.x; i < TAB_WORDS; i += NT) tab[i] = OPT ? src[i] : kTabs.w[i];
   __syncthreads();
 }
 
@@ -349,24 +371,39 @@ __device__ __forceinline__ unsigned wg_exclusive_scan(unsigned v, unsigned *red,
 // The codes of a dummy block: a zero DC difference in the luma table (00) and EOB (1010).
 constexpr unsigned DUMMY_CODE = 0x0A, DUMMY_BITS = 6;
 
-__global__ __launch_bounds__(NT) void jpeg_enc_bits_kernel(const int16_t *__restrict__ coef, uint32_t *__restrict__ local,
-                                                           uint32_t *__restrict__ csum, EPlan p) {
+// With fitted tables a dummy block takes the image's own codes for those two symbols, DC first.
+__device__ __forceinline__ void dummy_code(const uint32_t *tab, unsigned &code, unsigned &len) {
+  const uint32_t d = tab[TAB_DC], e = tab[TAB_AC];
+  code = ((d >> 8) << (e & 0xff)) | (e >> 8);
+  len = (d & 0xff) + (e & 0xff);
+}
+
+// OPT: the tables are the image's own (tabs, TAB_WORDS per image), staged for every image of the loop
+template <bool OPT>
+__global__ __launch_bounds__(NT) void jpeg_enc_bits_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
+                                                           uint32_t *__restrict__ local, uint32_t *__restrict__ csum, EPlan p) {
   __shared__ uint32_t tab[TAB_WORDS];
   __shared__ unsigned red[NT / 64];
-  stage_tabs(tab);
+  if (!OPT) stage_tabs<false>(tab, nullptr);
   const int t = blockIdx.x * NT + threadIdx.x;
   int comp = 0, bx, by;
   const bool real = t < p.nblk && block_of(p, t, comp, bx, by);
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    unsigned bits = t < p.nblk ? DUMMY_BITS : 0;
+    unsigned dummy_bits = DUMMY_BITS;
+    if (OPT) {
+      stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);     // the scan below ends with a barrier, so nobody still reads tab
+      unsigned code;
+      dummy_code(tab, code, dummy_bits);
+    }
+    unsigned bits = t < p.nblk ? dummy_bits : 0;
     if (real) {
       const int16_t *ci = coef + (size_t)img * p.nblk * 64;
       const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
       uint4 c[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) c[j] = src[j];
-      CountSink sink{0};
-      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0, tab);
+      CountSink sink{tab, 0};
+      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
       bits = sink.bits;
     }
     unsigned total;
@@ -401,29 +438,210 @@ __global__ __launch_bounds__(NT) void jpeg_enc_scan_kernel(uint32_t *__restrict_
   }
 }
 
-__global__ __launch_bounds__(NT) void jpeg_enc_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ local,
-                                                           const uint32_t *__restrict__ csum, uint32_t *__restrict__ bits, EPlan p) {
+template <bool OPT>
+__global__ __launch_bounds__(NT) void jpeg_enc_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
+                                                           const uint32_t *__restrict__ local, const uint32_t *__restrict__ csum,
+                                                           uint32_t *__restrict__ bits, EPlan p) {
   __shared__ uint32_t tab[TAB_WORDS];
-  stage_tabs(tab);
+  if (!OPT) stage_tabs<false>(tab, nullptr);
   const int t = blockIdx.x * NT + threadIdx.x;
-  if (t >= p.nblk) return;
-  int comp, bx, by;
-  const bool real = block_of(p, t, comp, bx, by);
+  if (!OPT && t >= p.nblk) return;      // with OPT every thread stays for the barriers of the image loop
+  int comp = 0, bx, by;
+  const bool coded = t < p.nblk;
+  const bool real = coded && block_of(p, t, comp, bx, by);
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    if (OPT) {
+      __syncthreads();                    // the image before this one has been coded from tab
+      stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);
+    }
+    if (!coded) continue;
     const unsigned pos = csum[(size_t)img * p.nchunk + blockIdx.x] + local[(size_t)img * p.nblk + t];
     // the bits of the word in front of this block count as zeros of the accumulator, so that whole words leave it
-    PackSink sink{bits + (size_t)img * p.words, pos >> 5, 0ull, (int)(pos & 31), true};
+    PackSink sink{tab, bits + (size_t)img * p.words, pos >> 5, 0ull, (int)(pos & 31), true};
     if (real) {
       const int16_t *ci = coef + (size_t)img * p.nblk * 64;
       const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
       uint4 c[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) c[j] = src[j];
-      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0, tab);
+      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
+    } else if (OPT) {
+      unsigned code, len;
+      dummy_code(tab, code, len);
+      sink.put(code, (int)len);
     } else {
       sink.put(DUMMY_CODE, DUMMY_BITS);
     }
     if (sink.n) atomicOr(&sink.words[sink.wi], (uint32_t)(sink.acc << (32 - sink.n)));
+  }
+}
+
+// One thread per coded block counts the symbols that its codes use (dummy blocks: a zero DC difference and EOB in the luma tables) in
+// the workgroup's histogram, which then joins the image's: hist (B, TAB_WORDS), zeroed by the call.  Integer atomics in LDS and in
+// memory are order-free, so two runs give the same counts.
+__global__ __launch_bounds__(NT) void jpeg_enc_hist_kernel(const int16_t *__restrict__ coef, uint32_t *__restrict__ hist, EPlan p) {
+  __shared__ unsigned h[TAB_WORDS];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  int comp = 0, bx, by;
+  const bool coded = t < p.nblk;
+  const bool real = coded && block_of(p, t, comp, bx, by);
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    for (int i = threadIdx.x; i < TAB_WORDS; i += NT) h[i] = 0;
+    __syncthreads();
+    HistSink sink{h};
+    if (real) {
+      const int16_t *ci = coef + (size_t)img * p.nblk * 64;
+      const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
+      uint4 c[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) c[j] = src[j];
+      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
+    } else if (coded) {
+      sink.sym(TAB_DC, 0, 0);
+      sink.sym(TAB_AC, 0, 0);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < TAB_WORDS; i += NT)
+      if (h[i]) atomicAdd(&hist[(size_t)img * TAB_WORDS + i], h[i]);
+    __syncthreads();
+  }
+}
+
+// key of a symbol for the two smallest counts: the lower count wins, on equal counts the larger symbol; no count: the largest key
+__device__ __forceinline__ unsigned long long merge_key(unsigned count, int sym) {
+  return count ? ((unsigned long long)count << 9) | (unsigned)(256 - sym) : ~0ull;
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int d) {
+  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, d, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), d, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ unsigned long long min_u64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+// the two smallest keys of the wave from every lane's two smallest (k1 <= k2), in every lane: one butterfly for c1 and c2 together
+__device__ __forceinline__ void wave_min2(unsigned long long &k1, unsigned long long &k2) {
+#pragma unroll
+  for (int d = 32; d; d >>= 1) {
+    const unsigned long long o1 = shfl_xor_u64(k1, d), o2 = shfl_xor_u64(k2, d);
+    const unsigned long long hi = k1 < o1 ? o1 : k1;
+    k1 = min_u64(k1, o1);
+    k2 = min_u64(hi, min_u64(k2, o2));
+  }
+}
+
+constexpr int HUFF_BYTES = 272;     // BITS (16) and HUFFVAL (256, zeros after the table's symbols)
+constexpr int MAX_CLEN = 32;        // libjpeg's bound, where it ends with an error: a longer code needs counts in Fibonacci proportions
+                                    // that sum past 9.2 million in one table.  Here the image's error word becomes 2.
+
+// One wavefront per (image, table), the four tables of an image in one workgroup in the header's order DC0, AC0, DC1, AC1:
+// jpeg_gen_optimal_table.  Lane l holds symbols l, l + 64, ..., l + 256 (the pseudo-symbol 256 with count 1 keeps the all-ones code
+// free).  Every merge takes c1 and c2 from one wave reduction of the two smallest keys; a tree id per symbol makes it "size += 1, tree = c1" for the symbols
+// of both trees.  The sizes go to LDS, where lane 0 counts them, limits the lengths to 16 and orders HUFFVAL; all lanes write out.
+// tabs (B, TAB_WORDS): code << 8 | length per symbol, 0 for a symbol without code; huff (B, 4, HUFF_BYTES); nval (B, 4).
+__global__ __launch_bounds__(NT) void jpeg_enc_tables_kernel(const uint32_t *__restrict__ hist, uint32_t *__restrict__ tabs,
+                                                             uint8_t *__restrict__ huff, int32_t *__restrict__ nval, int B) {
+  __shared__ uint8_t s_size[4][260];
+  __shared__ uint8_t s_val[4][256];
+  __shared__ uint32_t s_word[4][256];
+  __shared__ int s_bits[4][MAX_CLEN + 2];
+  __shared__ int s_start[4][MAX_CLEN + 2];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nsym = (w & 1) ? 256 : 12;
+  const int off = (w & 1) ? TAB_AC + 256 * (w >> 1) : TAB_DC + 12 * (w >> 1);
+  for (int img = blockIdx.x; img < B; img += gridDim.x) {
+    const uint32_t *hi = hist + (size_t)img * TAB_WORDS + off;
+    unsigned count[5];
+    int size[5], tree[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const int s = lane + 64 * j;
+      count[j] = s < nsym ? hi[s] : s == 256 ? 1u : 0u;
+      size[j] = 0;
+      tree[j] = s;
+    }
+    for (;;) {
+      unsigned long long k1 = ~0ull, k2 = ~0ull;      // keys of different symbols differ, so "c2 over the remaining symbols" is the second smallest
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        const unsigned long long k = merge_key(count[j], lane + 64 * j);
+        k2 = min_u64(k2, k < k1 ? k1 : k);
+        k1 = min_u64(k1, k);
+      }
+      wave_min2(k1, k2);
+      if (k2 == ~0ull) break;      // one tree is left
+      const int c1 = 256 - (int)(k1 & 511), c2 = 256 - (int)(k2 & 511);
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        const int s = lane + 64 * j;
+        if (s == c1) count[j] += (unsigned)(k2 >> 9);
+        if (s == c2) count[j] = 0;
+        if (tree[j] == c1 || tree[j] == c2) {
+          ++size[j];
+          tree[j] = c1;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+      if (lane + 64 * j <= 256) s_size[w][lane + 64 * j] = (uint8_t)size[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s_word[w][lane + 64 * j] = 0;
+      s_val[w][lane + 64 * j] = 0;
+    }
+    __syncthreads();
+    if (lane == 0) {
+      int *bits = s_bits[w], *start = s_start[w];
+      for (int i = 0; i <= MAX_CLEN + 1; ++i) bits[i] = 0;
+      for (int s = 0; s <= 256; ++s) ++bits[min((int)s_size[w][s], MAX_CLEN + 1)];
+      // HUFFVAL: by unlimited size, then by symbol; the pseudo-symbol has no place in it
+      int n = 0;
+      for (int i = 1; i <= MAX_CLEN; ++i) {
+        start[i] = n;
+        n += bits[i] - (s_size[w][256] == i ? 1 : 0);
+      }
+      for (int s = 0; s < 256; ++s) {
+        const int i = s_size[w][s];
+        if (i >= 1 && i <= MAX_CLEN) s_val[w][start[i]++] = (uint8_t)s;
+      }
+      // a code longer than MAX_CLEN bits before limiting: libjpeg ends with an error, here the count becomes -1, which the emit
+      // pass turns into the image's error word; the limiter and the codes are left out (their counts would no longer add up)
+      const bool too_long = bits[MAX_CLEN + 1] > 0;
+      if (!too_long) {
+        for (int i = MAX_CLEN; i > 16; --i) {
+          while (bits[i] > 0) {
+            int j = i - 2;
+            while (bits[j] == 0) --j;
+            bits[i] -= 2;
+            bits[i - 1] += 1;
+            bits[j + 1] += 2;
+            bits[j] -= 1;
+          }
+        }
+        int i = 16;
+        while (bits[i] == 0) --i;
+        --bits[i];
+        unsigned code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; ++len) {
+          for (int m = 0; m < bits[len]; ++m) s_word[w][s_val[w][k++]] = (code++ << 8) | (unsigned)len;
+          code <<= 1;
+        }
+      }
+      nval[(size_t)img * 4 + w] = too_long ? -1 : n;
+    }
+    __syncthreads();
+    uint32_t *to = tabs + (size_t)img * TAB_WORDS + off;
+    uint8_t *hb = huff + ((size_t)img * 4 + w) * HUFF_BYTES;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int s = lane + 64 * j;
+      if (s < nsym) to[s] = s_word[w][s];
+      hb[16 + s] = s_val[w][s];
+    }
+    if (lane < 16) hb[lane] = (uint8_t)s_bits[w][lane + 1];
+    __syncthreads();      // the next image's sizes overwrite what the lanes have just read
   }
 }
 
@@ -470,7 +688,8 @@ __global__ __launch_bounds__(NT) void jpeg_enc_count_kernel(const uint32_t *__re
 
 __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
                                                            const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
-                                                           int32_t *__restrict__ lens, int32_t *__restrict__ err, EPlan p) {
+                                                           int32_t *__restrict__ lens, int32_t *__restrict__ err,
+                                                           const int32_t *__restrict__ nval, EPlan p) {
   __shared__ unsigned red[NT / 64];
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
     const unsigned tbits = tot[(size_t)img * 2];
@@ -512,15 +731,69 @@ __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__res
         slot[len - 2] = 0xff;
         slot[len - 1] = 0xd9;
       }
-      lens[img] = fits ? (int32_t)len : 0;
-      err[img] = fits ? 0 : 1;
+      // nval (fitted tables only): a table whose count is negative had a code that libjpeg refuses, so there is no file
+      const bool coded = !nval || (nval[(size_t)img * 4] | nval[(size_t)img * 4 + 1] | nval[(size_t)img * 4 + 2] | nval[(size_t)img * 4 + 3]) >= 0;
+      lens[img] = fits && coded ? (int32_t)len : 0;
+      err[img] = !coded ? 2 : fits ? 0 : 1;
     }
   }
 }
 
-}  // namespace
-
 #define JPEG_ENC_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2581110 coded blocks per image"
+#define JPEG_ENC_OPT_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2579559 coded blocks per image"
+
+bool make_plan(int B, int H, int W, int sub, EPlan *p) { return make_plan(B, H, W, sub, false, p); }
+bool make_opt_plan(int B, int H, int W, int sub, EPlan *p) { return make_plan(B, H, W, sub, true, p); }
+
+// The checks that both entry points share, then the launches; p is the entry point's plan, opt says whether it is make_opt_plan's.
+// d_huff and d_nval are those of sgic_jpeg_encode_opt_batch (checked there), null for the Annex K tables.
+int encode_batch(const char *name, bool opt, const EPlan &p, const uint8_t *d_rgb, int B, const uint16_t *h_qt, uint8_t *d_work,
+                 size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff, int32_t *d_nval,
+                 sgic_stream_t stream) {
+  SGIC_REQUIRE_AS(name, d_rgb && h_qt && d_work && d_out && d_len && d_err, "null pointer");
+  SGIC_REQUIRE_AS(name, ((uintptr_t)d_work & 15) == 0, "the workspace must be 16-byte aligned");
+  SGIC_REQUIRE_AS(name, ((uintptr_t)h_qt & 1) == 0 && ((uintptr_t)d_len & 3) == 0 && ((uintptr_t)d_err & 3) == 0, "misaligned pointer");
+  SGIC_REQUIRE_AS(name, work_bytes >= p.bytes,
+                  opt ? "the workspace is smaller than sgic_jpeg_encode_opt_work_bytes says"
+                      : "the workspace is smaller than sgic_jpeg_encode_work_bytes says");
+  SGIC_REQUIRE_AS(name, cap >= p.cap && cap <= 0x7fffffff,
+                  opt ? "the slots are smaller than sgic_jpeg_encode_opt_cap says" : "the slots are smaller than sgic_jpeg_encode_cap says");
+  for (size_t i = 0; i < (size_t)B * 128; ++i) SGIC_REQUIRE_AS(name, h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
+  hipStream_t st = to_stream(stream);
+  int16_t *coef = reinterpret_cast<int16_t *>(d_work);
+  uint16_t *qt = reinterpret_cast<uint16_t *>(d_work + p.off_qt);
+  uint32_t *local = reinterpret_cast<uint32_t *>(d_work + p.off_local);
+  uint32_t *csum = reinterpret_cast<uint32_t *>(d_work + p.off_csum);
+  uint32_t *tabs = reinterpret_cast<uint32_t *>(d_work + p.off_tabs);
+  uint32_t *hist = reinterpret_cast<uint32_t *>(d_work + p.off_hist);
+  uint32_t *bits = reinterpret_cast<uint32_t *>(d_work + p.off_bits);
+  uint32_t *ffsum = reinterpret_cast<uint32_t *>(d_work + p.off_ffsum);
+  uint32_t *tot = reinterpret_cast<uint32_t *>(d_work + p.off_tot);
+  SGIC_HIP(hipMemcpyAsync(qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+  // the histograms lie directly in front of the bit stream (make_plan), so one memset zeroes both
+  SGIC_HIP(hipMemsetAsync(opt ? hist : bits, 0, p.off_ffsum - (opt ? p.off_hist : p.off_bits), st));
+  const unsigned gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+  const dim3 gblocks(p.nchunk, gy), gbytes(p.nbchunk < MAX_CHUNK_GRID ? p.nbchunk : MAX_CHUNK_GRID, gy);
+  jpeg_enc_coef_kernel<<<gblocks, NT, 0, st>>>(d_rgb, qt, coef, p);
+  if (opt) {
+    jpeg_enc_hist_kernel<<<gblocks, NT, 0, st>>>(coef, hist, p);
+    jpeg_enc_tables_kernel<<<gy, NT, 0, st>>>(hist, tabs, d_huff, d_nval, B);
+    jpeg_enc_bits_kernel<true><<<gblocks, NT, 0, st>>>(coef, tabs, local, csum, p);
+  } else {
+    jpeg_enc_bits_kernel<false><<<gblocks, NT, 0, st>>>(coef, nullptr, local, csum, p);
+  }
+  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(csum, p.nchunk, p.nchunk, tot, 0, 0, B);
+  if (opt)
+    jpeg_enc_pack_kernel<true><<<gblocks, NT, 0, st>>>(coef, tabs, local, csum, bits, p);
+  else
+    jpeg_enc_pack_kernel<false><<<gblocks, NT, 0, st>>>(coef, nullptr, local, csum, bits, p);
+  jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, p);
+  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(ffsum, p.nbchunk, 0, tot, 1, 1, B);
+  jpeg_enc_emit_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, d_out, cap, d_len, d_err, opt ? d_nval : nullptr, p);
+  return sgic::check_launch(name);
+}
+
+}  // namespace
 
 extern "C" int sgic_jpeg_encode_cap(int H, int W, int subsampling, size_t *cap) {
   SGIC_REQUIRE(cap != nullptr, "null output");
@@ -543,30 +816,31 @@ extern "C" int sgic_jpeg_encode_batch(const uint8_t *d_rgb, int B, int H, int W,
                                       sgic_stream_t stream) {
   EPlan p;
   SGIC_REQUIRE(make_plan(B, H, W, subsampling, &p), JPEG_ENC_LIMITS);
-  SGIC_REQUIRE(d_rgb && h_qt && d_work && d_out && d_len && d_err, "null pointer");
-  SGIC_REQUIRE(((uintptr_t)d_work & 15) == 0, "the workspace must be 16-byte aligned");
-  SGIC_REQUIRE(((uintptr_t)h_qt & 1) == 0 && ((uintptr_t)d_len & 3) == 0 && ((uintptr_t)d_err & 3) == 0, "misaligned pointer");
-  SGIC_REQUIRE(work_bytes >= p.bytes, "the workspace is smaller than sgic_jpeg_encode_work_bytes says");
-  SGIC_REQUIRE(cap >= p.cap && cap <= 0x7fffffff, "the slots are smaller than sgic_jpeg_encode_cap says");
-  for (size_t i = 0; i < (size_t)B * 128; ++i) SGIC_REQUIRE(h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
-  hipStream_t st = to_stream(stream);
-  int16_t *coef = reinterpret_cast<int16_t *>(d_work);
-  uint16_t *qt = reinterpret_cast<uint16_t *>(d_work + p.off_qt);
-  uint32_t *local = reinterpret_cast<uint32_t *>(d_work + p.off_local);
-  uint32_t *csum = reinterpret_cast<uint32_t *>(d_work + p.off_csum);
-  uint32_t *bits = reinterpret_cast<uint32_t *>(d_work + p.off_bits);
-  uint32_t *ffsum = reinterpret_cast<uint32_t *>(d_work + p.off_ffsum);
-  uint32_t *tot = reinterpret_cast<uint32_t *>(d_work + p.off_tot);
-  SGIC_HIP(hipMemcpyAsync(qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-  SGIC_HIP(hipMemsetAsync(bits, 0, (size_t)B * p.words * sizeof(uint32_t), st));
-  const unsigned gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
-  const dim3 gblocks(p.nchunk, gy), gbytes(p.nbchunk < MAX_CHUNK_GRID ? p.nbchunk : MAX_CHUNK_GRID, gy);
-  jpeg_enc_coef_kernel<<<gblocks, NT, 0, st>>>(d_rgb, qt, coef, p);
-  jpeg_enc_bits_kernel<<<gblocks, NT, 0, st>>>(coef, local, csum, p);
-  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(csum, p.nchunk, p.nchunk, tot, 0, 0, B);
-  jpeg_enc_pack_kernel<<<gblocks, NT, 0, st>>>(coef, local, csum, bits, p);
-  jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, p);
-  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(ffsum, p.nbchunk, 0, tot, 1, 1, B);
-  jpeg_enc_emit_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, d_out, cap, d_len, d_err, p);
-  return sgic::check_launch("sgic_jpeg_encode_batch");
+  return encode_batch(__func__, false, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, nullptr, nullptr, stream);
+}
+
+extern "C" int sgic_jpeg_encode_opt_cap(int H, int W, int subsampling, size_t *cap) {
+  SGIC_REQUIRE(cap != nullptr, "null output");
+  EPlan p;
+  SGIC_REQUIRE(make_opt_plan(1, H, W, subsampling, &p), JPEG_ENC_OPT_LIMITS);
+  *cap = p.cap;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_jpeg_encode_opt_work_bytes(int B, int H, int W, int subsampling, size_t *bytes) {
+  SGIC_REQUIRE(bytes != nullptr, "null output");
+  EPlan p;
+  SGIC_REQUIRE(make_opt_plan(B, H, W, subsampling, &p), JPEG_ENC_OPT_LIMITS);
+  *bytes = p.bytes;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_jpeg_encode_opt_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt,
+                                          uint8_t *d_work, size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err,
+                                          uint8_t *d_huff, int32_t *d_nval, sgic_stream_t stream) {
+  EPlan p;
+  SGIC_REQUIRE(make_opt_plan(B, H, W, subsampling, &p), JPEG_ENC_OPT_LIMITS);
+  SGIC_REQUIRE(d_huff && d_nval, "null pointer");
+  SGIC_REQUIRE(((uintptr_t)d_huff & 3) == 0 && ((uintptr_t)d_nval & 3) == 0, "misaligned pointer");
+  return encode_batch(__func__, true, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
 }

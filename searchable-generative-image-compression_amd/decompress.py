@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Counterpart of the reference driver src/decompress.py (same flags; writes save_dir/results/<stem>.png),
 running the MI355X decode path.  Files with identical shapes are decoded as one batch.  --format jpg writes baseline JPEG files
-encoded on the GPU instead (jpeg_enc: the bytes Pillow's save(quality, subsampling) would write for the same pixels)."""
+encoded on the GPU instead (jpeg_enc: the bytes Pillow's save(quality, subsampling) would write for the same pixels; with --optimize
+those of save(quality, subsampling, optimize=True): Huffman tables fitted to every image)."""
 import argparse
 import os
 import sys
@@ -40,9 +41,12 @@ def main(argv=None):
     ap.add_argument("--format", choices=("png", "jpg"), default="png", help="results as PNG (host zlib) or as JPEG encoded on the GPU")
     ap.add_argument("--quality", type=int, default=90, help="JPEG quality, 1..100 (--format jpg)")
     ap.add_argument("--subsampling", type=int, choices=(0, 1, 2), default=2, help="JPEG chroma layout: 0 4:4:4, 1 4:2:2, 2 4:2:0")
+    ap.add_argument("--optimize", action="store_true", help="JPEG with Huffman tables fitted to every image, as Pillow's optimize=True (--format jpg)")
     args = ap.parse_args(argv)
     if not 1 <= args.quality <= 100:
         ap.error("--quality must be in 1..100")
+    if args.optimize and args.format != "jpg":
+        ap.error("--optimize fits the Huffman tables of a JPEG file: give --format jpg")
 
     from . import weights as W
     from .codec import Codec
@@ -93,7 +97,7 @@ def main(argv=None):
                     pending.append(pool.submit(lambda arr, p: Image.fromarray(arr).save(p), a, path))
                 for members in crops.values():       # one encode per distinct cropped size; only the coded bytes cross the bus
                     from . import jpeg_enc
-                    files = jpeg_enc.encode_batch(torch.stack([m[1] for m in members]), args.quality, args.subsampling)
+                    files = jpeg_enc.encode_batch(torch.stack([m[1] for m in members]), args.quality, args.subsampling, optimize=args.optimize)
                     for (path, _), data in zip(members, files):
                         pending.append(pool.submit(_write_bytes, path, data))
         for f in pending:

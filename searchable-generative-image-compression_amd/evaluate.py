@@ -11,6 +11,8 @@
                                                                 quality whose file is not larger than the container is kept, decoded
                                                                 on the GPU (jpeg.JpegBatch) and measured like the reconstruction
   evaluate.py ... --anchor_quality Q                            the anchor at a fixed quality (needs no --bitstreams)
+  evaluate.py ... --anchor_optimize                             the anchor with Huffman tables fitted to every image (Pillow's
+                                                                optimize=True): the ladder, the pick and the kept file
   evaluate.py ... --lpips_ckpt P [P ...]                        adds "lpips" to every record, to its anchor and to the summary: LPIPS
                                                                 with the VGG16 trunk (lpips.LpipsVGG) on the same u8 tensors; P: one
                                                                 or more state dict files that together hold the trunk and the lin
@@ -230,22 +232,23 @@ class ClipSets:
         return {prefix + k: s[k] for k in ("recall@1", "recall@5", "recall@10", "mrr", "median_rank")}
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None):
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None, optimize=False):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
     on the GPU and measured against the original.  Encode, decode and measurement stay on the device; sizes and numbers come back.
     pair_metrics: [(key, model)] in record order (lpips.LpipsVGG, lpips_alex.LpipsAlex, dists.DistsVGG): every record also carries
     `key`, the model's measure of the decoded anchor against the original.  decoded_out: a list that receives the decoded anchors
-    (B, H, W, 3) u8 on the device (the FID of the anchor set)."""
+    (B, H, W, 3) u8 on the device (the FID of the anchor set).  optimize: sizes and files with Huffman tables fitted to every image
+    (jpeg_enc's optimize); the records then carry "optimize": true after "subsampling"."""
     from . import jpeg, jpeg_enc, quality
     B, H, W, _ = a_u8.shape
     if fixed_quality is None:
-        sizes = jpeg_enc.ladder_sizes(a_u8, subsampling)
+        sizes = jpeg_enc.ladder_sizes(a_u8, subsampling, optimize=optimize)
         picks = [jpeg_enc.pick_quality(dict(zip(jpeg_enc.LADDER, (int(v) for v in sizes[j]))), budgets[j]) for j in range(B)]
     else:
         picks = [(int(fixed_quality), None)] * B
-    files = jpeg_enc.encode_batch(a_u8, [q for q, _ in picks], subsampling)
+    files = jpeg_enc.encode_batch(a_u8, [q for q, _ in picks], subsampling, optimize=optimize)
     decoded = jpeg.JpegBatch(files).decode(a_u8.device)
     if decoded_out is not None:
         decoded_out.append(decoded)
@@ -255,7 +258,10 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
     for j, ((q, over), data) in enumerate(zip(picks, files)):
         if over is None:      # a fixed quality: over the rate if the container is known and smaller
             over = budgets[j] is not None and len(data) > budgets[j]
-        rec = {"codec": "jpeg", "quality": q, "subsampling": int(subsampling), "bytes": len(data), "bpp": 8 * len(data) / (H * W)}
+        rec = {"codec": "jpeg", "quality": q, "subsampling": int(subsampling)}
+        if optimize:
+            rec["optimize"] = True
+        rec.update({"bytes": len(data), "bpp": 8 * len(data) / (H * W)})
         for k in FIELDS:
             rec[k] = None if m[k] is None else _json_number(m[k][j])
         for k, v in pm:
@@ -280,6 +286,8 @@ def main(argv=None):
                          "not larger than the container (needs --bitstreams for the sizes)")
     ap.add_argument("--anchor_subsampling", type=int, choices=(0, 1, 2), default=2, help="the anchor's chroma layout (Pillow's values)")
     ap.add_argument("--anchor_quality", type=int, default=None, help="fix the anchor's quality instead of searching (implies --anchor jpeg)")
+    ap.add_argument("--anchor_optimize", action="store_true",
+                    help="the anchor with Huffman tables fitted to every image, as Pillow's optimize=True (with --anchor jpeg or --anchor_quality)")
     ap.add_argument("--lpips_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) with the VGG16 trunk and the lin layers of LPIPS: adds \"lpips\" to every record")
     ap.add_argument("--lpips_alex_ckpt", type=str, nargs="+", default=None,
@@ -304,6 +312,8 @@ def main(argv=None):
     if args.anchor and args.anchor_quality is None and not args.bitstreams:
         ap.error("--anchor jpeg matches the rate of the containers: give --bitstreams, or fix the quality with --anchor_quality")
     anchor = args.anchor or ("jpeg" if args.anchor_quality is not None else None)
+    if args.anchor_optimize and not anchor:
+        ap.error("--anchor_optimize changes the anchor: give --anchor jpeg or --anchor_quality")
     if args.batch_size < 1:
         ap.error("--batch_size must be at least 1")
     if args.fid_patch < 0:
@@ -367,7 +377,7 @@ def main(argv=None):
             pm = [(k, model.measure(a, b)) for k, model in pair_metrics]
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
             decoded = [] if fid_sets is not None or clip_sets is not None or niqe_model is not None else None
-            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded) if anchor else None
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded, args.anchor_optimize) if anchor else None
             if clip_sets is not None:
                 from .search import embedded_clip_codes
                 ua, qa = clip_sets.embed(a)

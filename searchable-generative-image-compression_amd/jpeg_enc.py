@@ -44,8 +44,17 @@ def _segment(marker, payload):
     return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
 
 
-def header(H, W, tables, subsampling):
-    """everything in front of the entropy-coded segment: SOI, APP0 (JFIF 1.01, no units, 1 x 1), two DQT, SOF0, four DHT, SOS"""
+def header(H, W, tables, subsampling, huffman=None):
+    """everything in front of the entropy-coded segment: SOI, APP0 (JFIF 1.01, no units, 1 x 1), two DQT, SOF0, four DHT, SOS.
+    huffman: four (BITS, HUFFVAL) pairs in the order DC0, AC0, DC1, AC1 (an image's optimised tables); None: the Annex K tables"""
+    return _header_front(H, W, tables, subsampling) + _header_back(huffman)
+
+
+_SOS = _segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+
+
+def _header_front(H, W, tables, subsampling):
+    """SOI .. SOF0: what an image's Huffman tables do not touch"""
     H, W = int(H), int(W)
     if not (1 <= H <= 65535 and 1 <= W <= 65535):
         raise ValueError(f"a JPEG frame is 1..65535 on a side, got {H}x{W}")
@@ -56,9 +65,17 @@ def header(H, W, tables, subsampling):
     for i in range(2):
         out.append(_segment(0xDB, bytes((i,)) + bytes(int(tables[i][z]) for z in ZIGZAG)))
     out.append(_segment(0xC0, bytes((8,)) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes((3, 1, h << 4 | v, 0, 2, 0x11, 1, 3, 0x11, 1))))
-    for tc_th, bits, vals in HUFFMAN:
-        out.append(_segment(0xC4, bytes((tc_th,)) + bits + vals))
-    out.append(_segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0))))
+    return b"".join(out)
+
+
+def _header_back(huffman=None):
+    """the four DHT segments and SOS"""
+    if huffman is None:
+        huffman = [(bits, vals) for _, bits, vals in HUFFMAN]
+    elif len(huffman) != 4 or any(len(bits) != 16 or sum(bits) != len(vals) or len(vals) > 256 for bits, vals in huffman):
+        raise ValueError("huffman is four (BITS of 16 counts, HUFFVAL of their sum) pairs")
+    out = [_segment(0xC4, bytes((tc_th,)) + bytes(bits) + bytes(vals)) for (tc_th, _, _), (bits, vals) in zip(HUFFMAN, huffman)]
+    out.append(_SOS)
     return b"".join(out)
 
 
@@ -71,20 +88,34 @@ def pick_quality(sizes_by_quality, budget):
     return (max(fits), False) if fits else (min(sizes_by_quality), True)
 
 
-def encode_scans(rgb_u8, tables, subsampling):
+def _raise_for(err):
+    """the encoder's error words, not all zero: 1 a slot was too small, 2 (optimised tables) a code past 32 bits before limiting"""
+    if (np.asarray(err) == 2).any():
+        raise RuntimeError("JPEG encoder: a Huffman code longer than 32 bits before the length limiter; libjpeg refuses such an image too")
+    raise RuntimeError(f"JPEG encoder: slot overflow, error words {np.asarray(err).ravel().tolist()}")
+
+
+def encode_scans(rgb_u8, tables, subsampling, optimize=False):
     """(B, H, W, 3) u8 on the device, tables (B, 2, 64) -> list of B bytes objects: entropy-coded segment and EOI.  One read-back of
-    the lengths and one of the bytes (the longest segment's length per image, not the slots)."""
+    the lengths and one of the bytes (the longest segment's length per image, not the slots).  optimize: -> (that list, a list of
+    every image's four (BITS, HUFFVAL) pairs); the tables and their counts come back in one more read each."""
     from . import ops
-    buf, lens, err = ops.jpeg_encode(rgb_u8, tables, subsampling)
+    buf, lens, err, *tabs = ops.jpeg_encode(rgb_u8, tables, subsampling, optimize)
     lens_h, err_h = lens.cpu().numpy(), err.cpu().numpy()
     if err_h.any():
-        raise RuntimeError(f"JPEG encoder: slot overflow, error words {err_h.tolist()}")
+        _raise_for(err_h)
     host = buf[:, :int(lens_h.max())].cpu().numpy()
-    return [host[b, :int(n)].tobytes() for b, n in enumerate(lens_h)]
+    scans = [host[b, :int(n)].tobytes() for b, n in enumerate(lens_h)]
+    if not optimize:
+        return scans
+    raw, nval = tabs[0].cpu().numpy().tobytes(), tabs[1].cpu().numpy().ravel().tolist()      # 272 bytes and one count per table
+    pairs = [(raw[o:o + 16], raw[o + 16:o + 16 + n]) for o, n in zip(range(0, len(raw), 272), nval)]
+    return scans, [pairs[4 * b:4 * b + 4] for b in range(len(scans))]
 
 
-def encode_batch(rgb_u8, quality, subsampling=2):
-    """(B, H, W, 3) u8 RGB on the device -> list of B whole JPEG files (bytes).  quality: an int, or one int per image."""
+def encode_batch(rgb_u8, quality, subsampling=2, optimize=False):
+    """(B, H, W, 3) u8 RGB on the device -> list of B whole JPEG files (bytes).  quality: an int, or one int per image.  optimize:
+    the files of Pillow's save(optimize=True), every image with Huffman tables fitted to it."""
     assert rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3, "images are (B, H, W, 3)"
     B, H, W, _ = rgb_u8.shape
     qs = [int(quality)] * B if np.ndim(quality) == 0 else [int(q) for q in quality]
@@ -93,14 +124,21 @@ def encode_batch(rgb_u8, quality, subsampling=2):
     if int(subsampling) not in SAMPLING:
         raise ValueError(f"subsampling must be 0, 1 or 2, got {subsampling}")
     by_q = {q: quant_tables(q) for q in set(qs)}
+    tables = np.stack([by_q[q] for q in qs])
+    if optimize:
+        scans, huffman = encode_scans(rgb_u8.contiguous(), tables, int(subsampling), True)
+        fronts = {q: _header_front(H, W, t, subsampling) for q, t in by_q.items()}
+        return [fronts[q] + _header_back(hf) + s for q, s, hf in zip(qs, scans, huffman)]
     heads = {q: header(H, W, t, subsampling) for q, t in by_q.items()}
-    scans = encode_scans(rgb_u8.contiguous(), np.stack([by_q[q] for q in qs]), int(subsampling))
+    scans = encode_scans(rgb_u8.contiguous(), tables, int(subsampling))
     return [heads[q] + s for q, s in zip(qs, scans)]
 
 
-def ladder_sizes(rgb_u8, subsampling=2, qualities=LADDER, max_slot_bytes=1 << 30):
+def ladder_sizes(rgb_u8, subsampling=2, qualities=LADDER, max_slot_bytes=1 << 30, optimize=False):
     """file size of every image at every quality -> (B, len(qualities)) int64 numpy array.  The images are encoded at several
-    qualities per call (per-image tables), as many as keep the output slots below max_slot_bytes; only the lengths are read back."""
+    qualities per call (per-image tables), as many as keep the output slots below max_slot_bytes; only the lengths are read back.
+    optimize: sizes with fitted Huffman tables; the header's length is then per (image, quality), from the four HUFFVAL counts,
+    which are read back with the lengths."""
     import ctypes
 
     import torch
@@ -109,7 +147,7 @@ def ladder_sizes(rgb_u8, subsampling=2, qualities=LADDER, max_slot_bytes=1 << 30
     from ._lib import call
     B, H, W, _ = rgb_u8.shape
     cap = ctypes.c_size_t(0)
-    call("sgic_jpeg_encode_cap", H, W, int(subsampling), ctypes.byref(cap))
+    call("sgic_jpeg_encode_opt_cap" if optimize else "sgic_jpeg_encode_cap", H, W, int(subsampling), ctypes.byref(cap))
     per_call = max(1, min(len(qualities), max_slot_bytes // (cap.value * B)))
     x = rgb_u8.contiguous()
     sizes = np.zeros((B, len(qualities)), dtype=np.int64)
@@ -118,12 +156,18 @@ def ladder_sizes(rgb_u8, subsampling=2, qualities=LADDER, max_slot_bytes=1 << 30
         qs = qualities[s:s + per_call]
         tabs = np.stack([quant_tables(q) for q in qs])                         # (n, 2, 64)
         rep = x.unsqueeze(0).expand(len(qs), B, H, W, 3).reshape(len(qs) * B, H, W, 3).contiguous()
-        _, lens, err = ops.jpeg_encode(rep, np.repeat(tabs, B, axis=0), int(subsampling))
-        pending.append((s, qs, torch.stack([lens, err])))
+        _, lens, err, *huff = ops.jpeg_encode(rep, np.repeat(tabs, B, axis=0), int(subsampling), optimize)
+        rows = [lens, err]
+        if optimize:        # the file's four HUFFVAL counts
+            rows.append(huff[1].sum(dim=1, dtype=torch.int32))
+        pending.append((s, qs, torch.stack(rows)))
     for s, qs, le in pending:
-        le = le.cpu().numpy().reshape(2, len(qs), B)
+        le = le.cpu().numpy().reshape(-1, len(qs), B)
         if le[1].any():
-            raise RuntimeError("JPEG encoder: slot overflow")
+            _raise_for(le[1])
         for j, q in enumerate(qs):
-            sizes[:, s + j] = le[0, j] + len(header(H, W, quant_tables(q), subsampling))
+            if optimize:    # the header of a file: the front, four DHT segments of 2 + 2 + 1 + 16 bytes and their HUFFVAL, SOS
+                sizes[:, s + j] = le[0, j] + len(_header_front(H, W, quant_tables(q), subsampling)) + 4 * 21 + le[2, j] + len(_SOS)
+            else:
+                sizes[:, s + j] = le[0, j] + len(header(H, W, quant_tables(q), subsampling))
     return sizes

@@ -14,8 +14,16 @@ under a time limit; the first point that fails ends the run.
   anchor   evaluate.py on the four images of tests/test_gpu_evaluate.py (SMALL architecture) with and without --anchor jpeg, host
            clock around each call, alternating.  No pass mark; the corpus is small, so this is mostly fixed cost.
 
-    python tools/bench_jpeg_enc.py [--quick] [--out profiles/jpeg_enc.txt]"""
+  --optimize   the same enc and ladder points for the optimised Huffman tables (encode_batch / ladder_sizes with optimize=True against
+               Pillow's save(optimize=True) on the pool; same requirement), each with the baseline-table encoder as a third side in the
+               same process (for information: the cost of the histogram and table passes), and in place of anchor:
+  size     evaluate.py --anchor jpeg with and without --anchor_optimize on that corpus and on tests/golden/ref_apple.jpg compressed
+           once (SMALL architecture): per image the container's bytes, the picked quality, over_rate, the anchor's bytes, PSNR and
+           MS-SSIM in dB.  No timing, no pass mark.
+
+    python tools/bench_jpeg_enc.py [--quick] [--optimize] [--out profiles/jpeg_enc.txt]"""
 import argparse
+import contextlib
 import io
 import json
 import os
@@ -32,51 +40,126 @@ THREADS = 16
 REQUIRED = "not slower than the Pillow pool beyond its own spread: min(gpu) <= min(pillow) + spread"
 
 
-def pillow_save(arr, quality, subsampling=2):
+def pillow_save(arr, quality, subsampling=2, optimize=False):
     from PIL import Image
     buf = io.BytesIO()
-    Image.fromarray(arr).save(buf, format="JPEG", quality=quality, subsampling=subsampling)
+    if optimize:
+        Image.fromarray(arr).save(buf, format="JPEG", quality=quality, subsampling=subsampling, optimize=True)
+    else:
+        Image.fromarray(arr).save(buf, format="JPEG", quality=quality, subsampling=subsampling)
     return buf.getvalue()
 
 
-def point_enc(size, B, quality, iters):
+@contextlib.contextmanager
+def pillow_block(size):
+    """Pillow sizes the buffer of an optimised save from the image and fails on a larger file: room for any file of a size x size
+    image while an --optimize point runs (set once, around the pool; the threads only read it; size 0 leaves it alone), the old value
+    afterwards"""
+    from PIL import ImageFile
+    keep = ImageFile.MAXBLOCK
+    ImageFile.MAXBLOCK = max(keep, 16 * size * size)
+    try:
+        yield
+    finally:
+        ImageFile.MAXBLOCK = keep
+
+
+def _with_baseline(rec, tb, tn):
+    """the third side of an --optimize point: the baseline-table encoder in the same process, for information"""
+    rec.update({"gpu_baseline_tables_ms": tb, "optimize_over_baseline": min(tn) / min(tb)})
+    return rec
+
+
+def point_enc(size, B, quality, iters, optimize=0):
     from concurrent.futures import ThreadPoolExecutor
     from sgic_amd import jpeg_enc
     x = pairs(B, size, size, 3)[1]
-    with ThreadPoolExecutor(max_workers=THREADS) as pool:
-        new = lambda: jpeg_enc.encode_batch(x, quality, 2)                                           # noqa: E731
-        old = lambda: list(pool.map(lambda a: pillow_save(a, quality), x.cpu().numpy()))             # noqa: E731
+    with pillow_block(size if optimize else 0), ThreadPoolExecutor(max_workers=THREADS) as pool:
+        new = lambda: jpeg_enc.encode_batch(x, quality, 2, optimize=bool(optimize))                              # noqa: E731
+        old = lambda: list(pool.map(lambda a: pillow_save(a, quality, 2, bool(optimize)), x.cpu().numpy()))      # noqa: E731
+        base = lambda: jpeg_enc.encode_batch(x, quality, 2)                                                      # noqa: E731
         got, want = new(), old()
         equal = got == want
         new()
         old()
-        tn, to = alternate((new, old), iters)
+        if optimize:
+            base()
+            tn, to, tb = alternate((new, old, base), iters)
+        else:
+            tn, to = alternate((new, old), iters)
     spread = max(to) - min(to)
-    return {"what": "jpeg_enc.encode_batch vs Pillow save on 16 threads, 4:2:0, device pixels -> files in host memory", "B": B, "H": size,
-            "W": size, "quality": quality, "iters": iters, "file_bytes_mean": sum(len(f) for f in got) / B, "gpu_ms": tn, "pillow_ms": to,
-            "pillow_spread_ms": spread, "ratio": min(to) / min(tn), "files_equal": bool(equal), "required": REQUIRED,
-            "met": bool(equal and min(tn) <= min(to) + spread)}
+    what = "jpeg_enc.encode_batch(optimize=True) vs Pillow save(optimize=True)" if optimize else "jpeg_enc.encode_batch vs Pillow save"
+    rec = {"what": what + " on 16 threads, 4:2:0, device pixels -> files in host memory", "B": B, "H": size,
+           "W": size, "quality": quality, "iters": iters, "file_bytes_mean": sum(len(f) for f in got) / B, "gpu_ms": tn, "pillow_ms": to,
+           "pillow_spread_ms": spread, "ratio": min(to) / min(tn), "files_equal": bool(equal), "required": REQUIRED,
+           "met": bool(equal and min(tn) <= min(to) + spread)}
+    return _with_baseline(rec, tb, tn) if optimize else rec
 
 
-def point_ladder(size, B, iters):
+def point_ladder(size, B, iters, optimize=0):
     from concurrent.futures import ThreadPoolExecutor
     import numpy as np
     from sgic_amd import jpeg_enc
     x = pairs(B, size, size, 3)[1]
     jobs = [(b, q) for b in range(B) for q in jpeg_enc.LADDER]
-    with ThreadPoolExecutor(max_workers=THREADS) as pool:
-        new = lambda: jpeg_enc.ladder_sizes(x, 2)                                                    # noqa: E731
+    with pillow_block(size if optimize else 0), ThreadPoolExecutor(max_workers=THREADS) as pool:
+        new = lambda: jpeg_enc.ladder_sizes(x, 2, optimize=bool(optimize))                           # noqa: E731
+        base = lambda: jpeg_enc.ladder_sizes(x, 2)                                                   # noqa: E731
 
         def old():
             arrs = x.cpu().numpy()
-            return np.array(list(pool.map(lambda j: len(pillow_save(arrs[j[0]], j[1])), jobs)), dtype=np.int64).reshape(B, -1)
+            return np.array(list(pool.map(lambda j: len(pillow_save(arrs[j[0]], j[1], 2, bool(optimize))), jobs)),
+                            dtype=np.int64).reshape(B, -1)
 
         equal = bool((new() == old()).all())
-        tn, to = alternate((new, old), iters)
+        if optimize:
+            base()
+            tn, to, tb = alternate((new, old, base), iters)
+        else:
+            tn, to = alternate((new, old), iters)
     spread = max(to) - min(to)
-    return {"what": "jpeg_enc.ladder_sizes (qualities 1..95) vs Pillow save of every image at every quality on 16 threads", "B": B,
-            "H": size, "W": size, "rungs": len(jpeg_enc.LADDER), "iters": iters, "gpu_ms": tn, "pillow_ms": to, "pillow_spread_ms": spread,
-            "ratio": min(to) / min(tn), "sizes_equal": equal, "required": REQUIRED, "met": bool(equal and min(tn) <= min(to) + spread)}
+    what = "jpeg_enc.ladder_sizes(optimize=True) (qualities 1..95) vs Pillow save(optimize=True)" if optimize else \
+        "jpeg_enc.ladder_sizes (qualities 1..95) vs Pillow save"
+    rec = {"what": what + " of every image at every quality on 16 threads", "B": B,
+           "H": size, "W": size, "rungs": len(jpeg_enc.LADDER), "iters": iters, "gpu_ms": tn, "pillow_ms": to, "pillow_spread_ms": spread,
+           "ratio": min(to) / min(tn), "sizes_equal": equal, "required": REQUIRED, "met": bool(equal and min(tn) <= min(to) + spread)}
+    return _with_baseline(rec, tb, tn) if optimize else rec
+
+
+def point_size():
+    """the size effect of --anchor_optimize: the picks and the numbers of the anchor with and without it, per image"""
+    import tempfile
+    import numpy as np
+    from PIL import Image
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import quality_ref
+    from sgic_amd import compress, evaluate
+    rows = []
+    with tempfile.TemporaryDirectory() as root:
+        src, out = os.path.join(root, "imgs"), os.path.join(root, "out")
+        os.makedirs(src)
+        for i, (h, w) in enumerate([(256, 256)] * 3 + [(200, 300)]):
+            Image.fromarray(quality_ref.texture(np.random.default_rng(40 + i), h, w)).save(os.path.join(src, f"im{i}.png"))
+        Image.open(os.path.join(ROOT, "tests", "golden", "ref_apple.jpg")).convert("RGB").save(os.path.join(src, "ref_apple.png"))
+        with contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()):
+            assert compress.main(["--dataset_dir", src, "--save_dir", out, "--small", "--batch_size", "4"]) == 0
+        base = ["--originals", src, "--bitstreams", os.path.join(out, "bitstreams"), "--small", "--anchor", "jpeg"]
+        reports = []
+        for extra in ([], ["--anchor_optimize"]):
+            rep = os.path.join(root, f"r{len(extra)}.jsonl")
+            with contextlib.redirect_stderr(io.StringIO()):
+                assert evaluate.main(base + extra + ["--out", rep]) == 0
+            with open(rep, encoding="utf-8") as fh:
+                reports.append([json.loads(ln) for ln in fh.read().splitlines()])
+        for plain, opt in zip(reports[0][:-1], reports[1][:-1]):
+            pick = lambda a: {k: a[k] for k in ("quality", "over_rate", "bytes", "psnr", "ms_ssim_db")}      # noqa: E731
+            rows.append({"name": plain["name"], "height": plain["height"], "width": plain["width"], "container_bytes": plain["bytes"],
+                         "anchor": pick(plain["anchor"]), "anchor_optimize": pick(opt["anchor"])})
+        keys = ("anchor_bpp", "anchor_psnr", "anchor_ms_ssim_db", "anchor_over_rate")
+        summary = {"anchor": {k: reports[0][-1][k] for k in keys}, "anchor_optimize": {k: reports[1][-1][k] for k in keys}}
+    return {"what": "evaluate.py --anchor jpeg without and with --anchor_optimize, SMALL architecture, synthetic weights: the four "
+                    "textures of tests/test_gpu_evaluate_anchor.py and tests/golden/ref_apple.jpg, compressed once", "images": rows,
+            "summary": summary, "required": "none"}
 
 
 def point_anchor(iters):
@@ -123,7 +206,7 @@ def run_point(spec):
     if not torch.cuda.is_available():
         raise SystemExit("bench_jpeg_enc needs the GPU: there is nothing to time without one")
     kind, args = spec.split(":")[0], [int(a) for a in spec.split(":")[1:]]
-    rec = {"enc": point_enc, "ladder": point_ladder, "anchor": point_anchor}[kind](*args)
+    rec = {"enc": point_enc, "ladder": point_ladder, "anchor": point_anchor, "size": point_size}[kind](*args)
     rec["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(rec), flush=True)
     return 0
@@ -132,15 +215,21 @@ def run_point(spec):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small sizes only (a rehearsal of the protocol, not a measurement)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_enc.txt"))
+    ap.add_argument("--optimize", action="store_true", help="the points of the optimised Huffman tables (default --out: profiles/jpeg_enc_opt.txt)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--point", default=None, help="run one point in this process (what the parent starts, under its time limit)")
     ap.add_argument("--limit", type=int, default=240, help="seconds each point may take")
     args = ap.parse_args(argv)
     if args.point:
         return run_point(args.point)
     points = ["enc:192:2:75:3"] if args.quick else ["enc:256:32:75:50", "enc:256:32:95:50", "enc:512:16:75:30", "ladder:256:32:3", "anchor:3"]
-    lines = ["# tools/bench_jpeg_enc.py; ms per call, two repeats each, the GPU encoder and the Pillow pool alternating in one process per "
-             "point"]
+    if args.optimize:       # the trailing 1 is the points' optimize argument
+        points = [p + ":1" for p in points if not p.startswith("anchor")] + ([] if args.quick else ["size"])
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_enc_opt.txt" if args.optimize else "jpeg_enc.txt")
+    ok = False
+    lines = ["# tools/bench_jpeg_enc.py" + (" --optimize" if args.optimize else "") + "; ms per call, two repeats each, the GPU encoder and "
+             "the Pillow pool" + (" and the baseline-table encoder" if args.optimize else "") + " alternating in one process per point"]
     for p in points:
         try:
             done = subprocess.run([sys.executable, os.path.abspath(__file__), "--point", p], capture_output=True, text=True,
@@ -153,10 +242,16 @@ def main(argv=None):
             break
         lines.append(done.stdout.strip().splitlines()[-1])
         print(lines[-1], flush=True)
+    else:
+        ok = True          # every point gave its line
+    if args.optimize:      # said plainly: which of the timed points met the requirement
+        timed = [(p, json.loads(ln)) for p, ln in zip(points, lines[1:]) if not ln.startswith("#") and "met" in json.loads(ln)]
+        lines.append("# requirement (" + REQUIRED + "): met at " + (", ".join(p for p, r in timed if r["met"]) or "no point") +
+                     "; missed at " + (", ".join(p for p, r in timed if not r["met"]) or "no point"))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w", encoding="utf-8") as fh:
         fh.write("\n".join(lines) + "\n")
-    return 0 if len(lines) == len(points) + 1 else 1
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
