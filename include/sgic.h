@@ -706,6 +706,22 @@ int sgic_jpeg_encode_opt_batch(const uint8_t *d_rgb, int B, int H, int W, int su
                                size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff,
                                int32_t *d_nval, sgic_stream_t stream);
 
+/* Image.resize for u8 RGB on the device: d_in (B, H, W, 3) -> d_out (B, OH, OW, 3), both contiguous, one geometry per call: the bytes
+ * of Pillow's `Image.fromarray(x).resize((OW, OH), filter)` (default box, reducing_gap=None; ImagingResample for 8-bit images).
+ * filter: 2 = bicubic, 1 = Lanczos (this ABI's codes; Pillow numbers Image.BICUBIC 3).  Per axis the tables are precompute_coeffs' (22-bit fixed point after
+ * normalisation); the horizontal pass runs first and writes u8 (accumulator from 1 << 21, >> 22, clamped), the vertical pass runs the
+ * same over that intermediate.  The tables are made on the host inside the call (Lanczos needs the host libm's sin to give Pillow's
+ * bits) and uploaded on the stream.  d_work: a device workspace, 16-byte aligned, of at least sgic_resize_u8_work_bytes (host-only,
+ * takes no stream; 0 for a geometry the call refuses).  SGIC_EINVAL before any launch, the output untouched, for: B < 1; H, W, OH or
+ * OW outside [1, 16384]; a filter other than 1 or 2; a null pointer; a workspace that is misaligned or too small.
+ * sgic_resize_u8_coeffs (host-only, takes no stream): the tables of one axis as the call makes them, into HOST arrays h_bounds
+ * (out_size x 2: first input index, count) and h_kk (out_size x ksize, zero past the count); ksize =
+ * ceil(support * max(in_size / out_size, 1)) * 2 + 1 with support 2 (bicubic) or 3 (Lanczos), checked. */
+size_t sgic_resize_u8_work_bytes(int B, int H, int W, int OH, int OW, int filter);
+int sgic_resize_u8_coeffs(int in_size, int out_size, int filter, int ksize, int32_t *h_bounds, int32_t *h_kk);
+int sgic_resize_u8_batch(const uint8_t *d_in, int B, int H, int W, uint8_t *d_out, int OH, int OW, int filter, uint8_t *d_work,
+                         size_t work_bytes, sgic_stream_t stream);
+
 /* CLIP text tower front end: out[b*L+l,:] = table[ids[b,l],:] + pos[l,:] (open_clip CLIP.encode_text, reached from
  * search.py:93-97; ids outside [0,vocab) are clamped).  D multiple of 4. */
 int sgic_embed_tokens(const int32_t *d_ids, const float *d_table, const float *d_pos, float *d_out, int B, int L, int D,

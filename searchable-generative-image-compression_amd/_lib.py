@@ -39,6 +39,11 @@ lib.sgic_lpips_head.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, 
 # sgic_dists_moments (csrc/dists.hip): (d_feat, B, H, W, C, d_work, work_bytes, d_sums, stream)
 lib.sgic_dists_moments_work_bytes.argtypes = [c_int, c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_dists_moments.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+# sgic_resize_u8_batch (csrc/resize.hip): (d_in, B, H, W, d_out, OH, OW, filter, d_work, work_bytes, stream)
+lib.sgic_resize_u8_work_bytes.restype = c_size_t
+lib.sgic_resize_u8_work_bytes.argtypes = [c_int] * 6
+lib.sgic_resize_u8_coeffs.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.sgic_resize_u8_batch.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
 
 
 class LaunchOpts(C.Structure):
@@ -95,7 +100,7 @@ _NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profil
               "sgic_clip_preprocess_ragged_workspace", "sgic_clip_preprocess_u8canvas_workspace", "sgic_search_codes_u8_work_bytes",
               "sgic_search_codes_f32q_work_bytes", "sgic_search_rank_work_bytes", "sgic_assign_codes_f32c_work_bytes", "sgic_quality_u8_work_bytes", "sgic_jpeg_encode_cap",
               "sgic_jpeg_encode_work_bytes", "sgic_jpeg_encode_opt_cap", "sgic_jpeg_encode_opt_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes",
-              "sgic_niqe_u8_work_bytes"}
+              "sgic_niqe_u8_work_bytes", "sgic_resize_u8_coeffs"}
 
 
 def call(name, *args):

@@ -12,10 +12,11 @@ LIB = os.path.join(HERE, "libsgic.so")
 # restatement that has no fma either.  lpips.hip, dists.hip: their input layers are compared with single fp32 operations for
 # equality; the DISTS head needs x == y to give exactly 0.  lpips_alex.hip: the same input layer, compared the same way.  fid.hip: its
 # producers and pools are compared for equality, its resize and Gram with restatements that have no fma.  niqe.hip: the sign of its
-# MSCN samples (a sum of ten products) has to be the CPU restatement's, which has no fma.
+# MSCN samples (a sum of ten products) has to be the CPU restatement's, which has no fma.  resize.hip: the double arithmetic of Pillow's
+# coefficient tables (pil_resample.h, shared with misc.hip) must stay single operations.
 FLAGS = {"entropy.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "quality.hip": ["-ffp-contract=off"],
          "lpips.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "lpips_alex.hip": ["-ffp-contract=off"], "fid.hip": ["-ffp-contract=off"],
-         "niqe.hip": ["-ffp-contract=off"]}
+         "niqe.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src_list, out):

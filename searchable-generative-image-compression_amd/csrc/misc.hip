@@ -4,6 +4,7 @@
 // tile <-> stack rearranges (models/codec_sq_fixbpp.py:123-125, models/cross_blocks.py:78-79,96-97)
 // the identity, so no gather/scatter pass is ever needed.
 #include "common.h"
+#include "pil_resample.h"
 #include <limits.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -662,62 +663,20 @@ extern "C" int sgic_u8canvas_to_f32chw_pad(const uint8_t *d_in, const int32_t *h
 //               the output index): the intermediate is 3 x rows x S u8.  The one stage that depends on where the pixels come from:
 //               an fp32 image in [-1, 1] (truncated to a planar u8 copy first, as ToPILImage does) or the u8 canvas of the ingest
 //   vertical:   u8 -> (v / 255 - mean) / std fp32 (3, S, S)
+// The coefficient rule, the 8-bit accumulator and the LDS staging of an interleaved row are pil_resample.h's, shared with resize.hip.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double pil_bicubic(double x) {
-  const double a = -0.5;
-  x = fabs(x);
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
-  if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * a;
-  return 0.0;
-}
-
-// Pillow's (bounds, 22-bit ints) for output index xx of an in_size -> out_size bicubic resample; the kk row is zero past its
-// count, as in pil_coeffs
-__device__ void pil_coeff_row(int in_size, int out_size, int ksize, int xx, int *__restrict__ bounds, int *__restrict__ kk) {
-  const double scale = __ddiv_rn((double)in_size, (double)out_size);
-  const double fscale = scale > 1.0 ? scale : 1.0;
-  const double support = 2.0 * fscale;
-  const double ss = __ddiv_rn(1.0, fscale);
-  const double center = ((double)xx + 0.5) * scale;
-  int xmin = (int)(center - support + 0.5);
-  xmin = max(xmin, 0);
-  int xmax = (int)(center + support + 0.5);
-  xmax = min(min(xmax, in_size) - xmin, ksize);
-  double ww = 0.0;
-  for (int x = 0; x < xmax; x++) ww += pil_bicubic(((double)(x + xmin) - center + 0.5) * ss);
-  int *k = kk + (long)xx * ksize;
-  for (int x = 0; x < ksize; x++) {
-    int q = 0;
-    if (x < xmax) {
-      double v = pil_bicubic(((double)(x + xmin) - center + 0.5) * ss);
-      if (ww != 0.0) v = __ddiv_rn(v, ww);
-      q = v < 0.0 ? (int)(-0.5 + v * 4194304.0) : (int)(0.5 + v * 4194304.0);
-    }
-    k[x] = q;
-  }
-  bounds[2 * xx] = xmin;
-  bounds[2 * xx + 1] = xmax;
-}
-
 __global__ void pil_coeffs_kernel(int in_size, int out_size, int ksize, int *__restrict__ bounds, int *__restrict__ kk) {
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (xx < out_size) pil_coeff_row(in_size, out_size, ksize, xx, bounds, kk);
-}
-
-static int pil_ksize(int in_size, int out_size) {   // clip.py pil_coeffs: int(ceil(2 * max(in / out, 1))) * 2 + 1
-  const double scale = (double)in_size / (double)out_size;
-  return (int)std::ceil(2.0 * (scale > 1.0 ? scale : 1.0)) * 2 + 1;
+  if (xx < out_size) pil_coeff_row<PilBicubic>(in_size, out_size, ksize, xx, bounds, kk);
 }
 
 extern "C" int sgic_clip_resize_coeffs(int in_size, int out_size, int ksize, int32_t *d_bounds, int32_t *d_kk, sgic_stream_t stream) {
   SGIC_REQUIRE(d_bounds && d_kk && in_size > 0 && out_size > 0, "args");
-  SGIC_REQUIRE(ksize == pil_ksize(in_size, out_size), "ksize");
+  SGIC_REQUIRE(ksize == pil_ksize<PilBicubic>(in_size, out_size), "ksize");
   pil_coeffs_kernel<<<cdiv(out_size, 64), 64, 0, to_stream(stream)>>>(in_size, out_size, ksize, d_bounds, d_kk);
   return sgic::check_launch("pil_coeffs_kernel");
 }
 
-#define U8C_TILE_PX 4096   // canvas route: source pixels of a row held in LDS at a time (three planes: 12 KiB)
-#define U8C_THREADS 256
 // OH, OW < 2^30: a bounds table is indexed with the int 2 * index + 1 and the table kernel counts OW + OH rows in an int; every
 // other expression over OH, OW, ksize and the offsets is 64-bit or a double
 #define CLIP_MAX_OUT 0x3fffffff
@@ -735,13 +694,6 @@ struct ClipChunk {
   ClipImg img[RAGGED_CHUNK];
 };
 
-// the window of n consecutive outputs of an in_size -> out_size resample spans fewer than (n - 1) * scale + 2 * support + 1 inputs
-// (first index > centre_0 - support - 0.5, end <= centre_{n-1} + support + 0.5; clamping to [0, in_size] only shrinks it)
-static double u8c_span_bound(int in_size, int out_size, int n) {
-  const double scale = (double)in_size / (double)out_size;
-  return (double)(n - 1) * scale + 4.0 * (scale > 1.0 ? scale : 1.0) + 1.0;
-}
-
 // one image's geometry (func: the entry point it is checked for) and its slice of the workspace, at byte offset *off (advanced past
 // it): its four tables, its planar u8 copy if the route has one, its horizontal-pass output, each 16-byte aligned
 static int clip_image(const char *func, const int32_t *q, int S, bool planar, long long *off, ClipImg *m) {
@@ -750,12 +702,11 @@ static int clip_image(const char *func, const int32_t *q, int S, bool planar, lo
                   "image geometry");
   SGIC_REQUIRE_AS(func, top >= 0 && left >= 0 && S <= OH && S <= OW && top <= OH - S && left <= OW - S, "crop window");
   m->g[0] = H, m->g[1] = W, m->g[2] = OH, m->g[3] = OW, m->g[4] = top, m->g[5] = left;
-  m->g[6] = pil_ksize(W, OW), m->g[7] = pil_ksize(H, OH);
+  m->g[6] = pil_ksize<PilBicubic>(W, OW), m->g[7] = pil_ksize<PilBicubic>(H, OH);
   m->rows_cap = (int)std::min((double)H, std::floor(u8c_span_bound(H, OH, S)) + 2.0);
   // the largest tile whose window is sure to fit one LDS fill; a window that does not fit (one output with more than U8C_TILE_PX
   // taps) is resampled in several fills
-  const double per = (double)W / (double)OW, room = (double)U8C_TILE_PX - u8c_span_bound(W, OW, 1);
-  m->tile = room > 0.0 ? (int)std::min((double)std::min(S, U8C_THREADS), std::floor(room / per) + 1.0) : 1;
+  m->tile = u8c_tile(W, OW, std::min(S, U8C_THREADS));
   const long long size[6] = {8LL * OW, 4LL * OW * m->g[6], 8LL * OH, 4LL * OH * m->g[7], planar ? 3LL * H * W : 0LL, 3LL * m->rows_cap * S};
   for (int k = 0; k < 6; k++) {
     m->off[k] = *off;
@@ -770,22 +721,9 @@ __global__ void clip_ragged_coeffs_kernel(ClipChunk ch, uint8_t *__restrict__ wo
   int *bh = reinterpret_cast<int *>(work + m.off[0]), *kh = reinterpret_cast<int *>(work + m.off[1]);
   int *bv = reinterpret_cast<int *>(work + m.off[2]), *kv = reinterpret_cast<int *>(work + m.off[3]);
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < OW + OH; t += (long)gridDim.x * blockDim.x) {
-    if (t < OW) pil_coeff_row(W, OW, m.g[6], (int)t, bh, kh);
-    else pil_coeff_row(H, OH, m.g[7], (int)t - OW, bv, kv);
+    if (t < OW) pil_coeff_row<PilBicubic>(W, OW, m.g[6], (int)t, bh, kh);
+    else pil_coeff_row<PilBicubic>(H, OH, m.g[7], (int)t - OW, bv, kv);
   }
-}
-
-// the tail of Pillow's 8bpc passes: the accumulator starts at half an output unit (22 fractional bits) and ends as a clamped byte
-__device__ __forceinline__ int pil_acc_to_u8(int ss) {
-  ss >>= 22;
-  return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
-}
-
-// one output sample of one channel: cnt taps p[0], p[stride], ... against the 22-bit coefficients k
-__device__ __forceinline__ int pil_resample_u8(const uint8_t *__restrict__ p, long stride, const int *__restrict__ k, int cnt) {
-  int ss = 1 << 21;
-  for (int t = 0; t < cnt; t++) ss += (int)p[t * stride] * k[t];
-  return pil_acc_to_u8(ss);
 }
 
 // the source rows the vertical pass reads for output rows top .. top + S - 1 (bv: its bounds table): first row *r0 -> their number
@@ -835,29 +773,6 @@ __global__ void clip_ragged_resize_h_kernel(ClipChunk ch, int S, uint8_t *__rest
   }
 }
 
-// nbytes of interleaved RGB starting at a pixel boundary -> px[c][i]: 16-byte loads over the aligned middle, single bytes for the
-// up to 15 bytes on either side, so that no byte outside [p, p + nbytes) is touched
-__device__ __forceinline__ void u8c_stage_row(const uint8_t *__restrict__ p, int nbytes, uint8_t (*px)[U8C_TILE_PX]) {
-  const int head = min(nbytes, (int)((16u - (unsigned)((uintptr_t)p & 15)) & 15u));
-  const int nvec = (nbytes - head) >> 4;
-  const int tail0 = head + (nvec << 4);
-  for (int i = threadIdx.x; i < head + nbytes - tail0; i += U8C_THREADS) {
-    const int o = i < head ? i : tail0 + (i - head);
-    px[o % 3][o / 3] = p[o];
-  }
-  for (int v = threadIdx.x; v < nvec; v += U8C_THREADS) {
-    const int o = head + (v << 4);
-    const uint4 q = *reinterpret_cast<const uint4 *>(p + o);
-    const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-    int pix = o / 3, c = o - 3 * pix;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      px[c][pix] = (uint8_t)(w4[j >> 2] >> (8 * (j & 3)));
-      if (++c == 3) c = 0, pix++;
-    }
-  }
-}
-
 // the horizontal pass straight from the u8 canvas of the ingest (B, Hc, Wc, 3 interleaved RGB; image b is the top-left H_b x W_b
 // region, the rest of the canvas holds stale bytes and is never read): the decoded bytes are resampled AS THEY ARE -- what
 // `preprocess(Image.open(path))` does in the reference's build-images.  A workgroup takes one source row: it loads the segment of
@@ -888,7 +803,7 @@ __global__ __launch_bounds__(U8C_THREADS) void clip_u8canvas_resize_h_kernel(con
       for (int c0 = w0; c0 < w1; c0 += U8C_TILE_PX) {
         const int n = min(U8C_TILE_PX, w1 - c0);
         __syncthreads();   // the previous fill has been read
-        u8c_stage_row(row + 3L * c0, 3 * n, px);
+        u8c_stage_row(row + 3L * c0, 3 * n, px, U8C_THREADS);
         __syncthreads();
         if (active) {
           const int lo = max(xmin, c0), hi = min(xend, c0 + n);

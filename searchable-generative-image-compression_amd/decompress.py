@@ -2,7 +2,8 @@
 """Counterpart of the reference driver src/decompress.py (same flags; writes save_dir/results/<stem>.png),
 running the MI355X decode path.  Files with identical shapes are decoded as one batch.  --format jpg writes baseline JPEG files
 encoded on the GPU instead (jpeg_enc: the bytes Pillow's save(quality, subsampling) would write for the same pixels; with --optimize
-those of save(quality, subsampling, optimize=True): Huffman tables fitted to every image)."""
+those of save(quality, subsampling, optimize=True): Huffman tables fitted to every image).  --max_side N reduces results whose longer
+side exceeds N on the device before they are written (ops.resize_u8, Lanczos: the pixels of Pillow's Image.resize)."""
 import argparse
 import os
 import sys
@@ -42,7 +43,11 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=90, help="JPEG quality, 1..100 (--format jpg)")
     ap.add_argument("--subsampling", type=int, choices=(0, 1, 2), default=2, help="JPEG chroma layout: 0 4:4:4, 1 4:2:2, 2 4:2:0")
     ap.add_argument("--optimize", action="store_true", help="JPEG with Huffman tables fitted to every image, as Pillow's optimize=True (--format jpg)")
+    ap.add_argument("--max_side", type=int, default=None, metavar="N",
+                    help="reduce results whose longer side exceeds N (1..16384) to that side, Lanczos, before they are written")
     args = ap.parse_args(argv)
+    if args.max_side is not None and not 1 <= args.max_side <= 16384:
+        ap.error("--max_side must be in 1..16384")
     if not 1 <= args.quality <= 100:
         ap.error("--quality must be in 1..100")
     if args.optimize and args.format != "jpg":
@@ -81,23 +86,31 @@ def main(argv=None):
             for s in range(0, len(idxs), args.batch_size):
                 chunk = idxs[s:s + args.batch_size]
                 x_hat = model.decode_batch([items[i][1] for i in chunk])
-                crops = {}      # --format jpg: the u8 images of this batch by cropped size, still on the device
+                crops = {}      # --format jpg, --max_side: the u8 images of this batch by cropped size, still on the device
                 for j, i in enumerate(chunk):
                     fp, _, header = items[i]
                     pl, pr, pt, pb = header.get("padding", [0, 0, 0, 0])
                     H, Wd = x_hat.shape[2] - pt - pb, x_hat.shape[3] - pl - pr   # negative-pad crop (decompress.py:110-112)
                     x01 = x_hat[j, :, pt:pt + H, pl:pl + Wd].clamp(-1, 1) * 0.5 + 0.5
                     stem = os.path.splitext(os.path.basename(fp))[0]
-                    if args.format == "jpg":
+                    if args.format == "jpg" or args.max_side is not None:
                         from .evaluate import to_u8_hwc_device
-                        crops.setdefault((H, Wd), []).append((os.path.join(out_dir, stem + ".jpg"), to_u8_hwc_device(x01)))
+                        crops.setdefault((H, Wd), []).append((os.path.join(out_dir, f"{stem}.{args.format}"), to_u8_hwc_device(x01)))
                         continue
                     a = to_u8_hwc(x01)
                     path = os.path.join(out_dir, stem + ".png")
                     pending.append(pool.submit(lambda arr, p: Image.fromarray(arr).save(p), a, path))
-                for members in crops.values():       # one encode per distinct cropped size; only the coded bytes cross the bus
-                    from . import jpeg_enc
-                    files = jpeg_enc.encode_batch(torch.stack([m[1] for m in members]), args.quality, args.subsampling, optimize=args.optimize)
+                for (H, Wd), members in crops.items():       # one resize and one encode per distinct cropped size
+                    from . import jpeg_enc, ops
+                    from .resize import max_side_size
+                    images = torch.stack([m[1] for m in members])
+                    if args.max_side is not None and max(H, Wd) > args.max_side:
+                        images = ops.resize_u8(images, *max_side_size(H, Wd, args.max_side), "lanczos")
+                    if args.format == "png":
+                        for (path, _), arr in zip(members, images.cpu().numpy()):
+                            pending.append(pool.submit(lambda arr, p: Image.fromarray(arr).save(p), arr, path))
+                        continue
+                    files = jpeg_enc.encode_batch(images, args.quality, args.subsampling, optimize=args.optimize)   # only the coded bytes cross the bus
                     for (path, _), data in zip(members, files):
                         pending.append(pool.submit(_write_bytes, path, data))
         for f in pending:

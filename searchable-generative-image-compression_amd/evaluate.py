@@ -13,6 +13,13 @@
   evaluate.py ... --anchor_quality Q                            the anchor at a fixed quality (needs no --bitstreams)
   evaluate.py ... --anchor_optimize                             the anchor with Huffman tables fitted to every image (Pillow's
                                                                 optimize=True): the ladder, the pick and the kept file
+  evaluate.py ... --anchor_scales R [R ...]                     the anchor at reduced resolution, what a JPEG user does at low rates:
+                                                                for every R the original is reduced to ceil(H / R) x ceil(W / R)
+                                                                (Lanczos, ops.resize_u8), coded as above, decoded and enlarged back
+                                                                (bicubic); every image keeps the R with the highest PSNR among those
+                                                                with a quality that fits its container.  The anchor then carries
+                                                                "scale", "coded_height", "coded_width", the summary
+                                                                "anchor_scale_counts".  With --anchor_quality: exactly one R
   evaluate.py ... --lpips_ckpt P [P ...]                        adds "lpips" to every record, to its anchor and to the summary: LPIPS
                                                                 with the VGG16 trunk (lpips.LpipsVGG) on the same u8 tensors; P: one
                                                                 or more state dict files that together hold the trunk and the lin
@@ -128,6 +135,9 @@ def summarise(records, fid_sets=None, clip_sets=None):
         if clip_sets is not None:
             out["anchor_clip_sim"] = mean([a["clip_sim"] for a in anchors])
             out.update(clip_sets.summary("anchor", [r for r in records if "anchor" in r], "anchor_clip_"))
+        if any("scale" in a for a in anchors):      # --anchor_scales: how many images kept which scale, the last anchor key
+            out["anchor_scale_counts"] = {str(r): sum(1 for a in anchors if a.get("scale") == r)
+                                          for r in sorted({a["scale"] for a in anchors if "scale" in a})}
     if fid_sets is not None:
         out.update(fid_sets.summary())
     if any("niqe" in r for r in records):      # --niqe_params: after every other key
@@ -232,7 +242,29 @@ class ClipSets:
         return {prefix + k: s[k] for k in ("recall@1", "recall@5", "recall@10", "mrr", "median_rank")}
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None, optimize=False):
+def _anchor_files(src_u8, budgets, subsampling, fixed_quality, optimize):
+    """the anchor's pick and files for a batch as it is coded: src_u8 (B, h, w, 3) -> ([(quality, over_rate or None)], [bytes])"""
+    from . import jpeg_enc
+    B = src_u8.shape[0]
+    if fixed_quality is None:
+        sizes = jpeg_enc.ladder_sizes(src_u8, subsampling, optimize=optimize)
+        picks = [jpeg_enc.pick_quality(dict(zip(jpeg_enc.LADDER, (int(v) for v in sizes[j]))), budgets[j]) for j in range(B)]
+    else:
+        picks = [(int(fixed_quality), None)] * B
+    return picks, jpeg_enc.encode_batch(src_u8, [q for q, _ in picks], subsampling, optimize=optimize)
+
+
+def choose_scale(candidates):
+    """the rule of --anchor_scales for one image: candidates [(scale, over_rate, bytes, psnr)] in ascending scale -> the index of the
+    one kept.  Among the scales where a quality fits the budget the highest PSNR (an infinite one wins), the smaller scale on a tie;
+    if none fits, the smallest file, the smaller scale on a tie"""
+    fits = [i for i, c in enumerate(candidates) if not c[1]]
+    if fits:
+        return max(fits, key=lambda i: (candidates[i][3], -i))
+    return min(range(len(candidates)), key=lambda i: (candidates[i][2], i))
+
+
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None, optimize=False, scales=None):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
@@ -240,16 +272,34 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
     pair_metrics: [(key, model)] in record order (lpips.LpipsVGG, lpips_alex.LpipsAlex, dists.DistsVGG): every record also carries
     `key`, the model's measure of the decoded anchor against the original.  decoded_out: a list that receives the decoded anchors
     (B, H, W, 3) u8 on the device (the FID of the anchor set).  optimize: sizes and files with Huffman tables fitted to every image
-    (jpeg_enc's optimize); the records then carry "optimize": true after "subsampling"."""
-    from . import jpeg, jpeg_enc, quality
+    (jpeg_enc's optimize); the records then carry "optimize": true after "subsampling".
+    scales: the anchor at reduced resolution.  For every r of the list (ascending) the batch is reduced to resize.reduced_size(H, W, r)
+    with Lanczos (ops.resize_u8; r = 1: the image as it is), picked and encoded as above against the same budgets, decoded, enlarged
+    to (H, W) with bicubic and measured; every image keeps the scale choose_scale names.  The records then carry "scale",
+    "coded_height" and "coded_width" after "subsampling" ("optimize"); "bytes" is the reduced file and "bpp" counts the original's
+    pixels."""
+    from . import jpeg, ops, quality
+    from .resize import reduced_size
     B, H, W, _ = a_u8.shape
-    if fixed_quality is None:
-        sizes = jpeg_enc.ladder_sizes(a_u8, subsampling, optimize=optimize)
-        picks = [jpeg_enc.pick_quality(dict(zip(jpeg_enc.LADDER, (int(v) for v in sizes[j]))), budgets[j]) for j in range(B)]
+    if scales is None:
+        picks, files = _anchor_files(a_u8, budgets, subsampling, fixed_quality, optimize)
+        decoded = jpeg.JpegBatch(files).decode(a_u8.device)
+        coded = None
     else:
-        picks = [(int(fixed_quality), None)] * B
-    files = jpeg_enc.encode_batch(a_u8, [q for q, _ in picks], subsampling, optimize=optimize)
-    decoded = jpeg.JpegBatch(files).decode(a_u8.device)
+        per = []      # one entry per scale, ascending: what every image of the batch would get at it
+        for r in sorted(int(r) for r in scales):
+            h, w = reduced_size(H, W, r)
+            src = a_u8 if r == 1 else ops.resize_u8(a_u8, h, w, "lanczos")
+            pk, fl = _anchor_files(src, budgets, subsampling, fixed_quality, optimize)
+            dec = jpeg.JpegBatch(fl).decode(a_u8.device)
+            if r != 1:
+                dec = ops.resize_u8(dec.contiguous(), H, W, "bicubic")
+            per.append({"scale": r, "coded": (h, w), "picks": pk, "files": fl, "decoded": dec, "psnr": quality.measure(a_u8, dec)["psnr"]})
+        kept = [per[choose_scale([(s["scale"], bool(s["picks"][j][1]), len(s["files"][j]), float(s["psnr"][j])) for s in per])]
+                for j in range(B)]      # a fixed quality has no over_rate yet (None): its one scale is kept
+        picks, files = [s["picks"][j] for j, s in enumerate(kept)], [s["files"][j] for j, s in enumerate(kept)]
+        decoded = torch.stack([s["decoded"][j] for j, s in enumerate(kept)])
+        coded = [(s["scale"], s["coded"]) for s in kept]
     if decoded_out is not None:
         decoded_out.append(decoded)
     m = quality.measure(a_u8, decoded)
@@ -261,6 +311,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
         rec = {"codec": "jpeg", "quality": q, "subsampling": int(subsampling)}
         if optimize:
             rec["optimize"] = True
+        if coded is not None:
+            rec.update({"scale": coded[j][0], "coded_height": coded[j][1][0], "coded_width": coded[j][1][1]})
         rec.update({"bytes": len(data), "bpp": 8 * len(data) / (H * W)})
         for k in FIELDS:
             rec[k] = None if m[k] is None else _json_number(m[k][j])
@@ -288,6 +340,10 @@ def main(argv=None):
     ap.add_argument("--anchor_quality", type=int, default=None, help="fix the anchor's quality instead of searching (implies --anchor jpeg)")
     ap.add_argument("--anchor_optimize", action="store_true",
                     help="the anchor with Huffman tables fitted to every image, as Pillow's optimize=True (with --anchor jpeg or --anchor_quality)")
+    ap.add_argument("--anchor_scales", type=int, nargs="+", default=None, metavar="R",
+                    help="the anchor at reduced resolution: for every R (distinct integers in 1..16) the original is reduced to "
+                         "ceil(H / R) x ceil(W / R) with Lanczos, coded, decoded and enlarged with bicubic; every image keeps the R "
+                         "with the highest PSNR among those that fit its container (with --anchor_quality: exactly one R)")
     ap.add_argument("--lpips_ckpt", type=str, nargs="+", default=None,
                     help="state dict file(s) with the VGG16 trunk and the lin layers of LPIPS: adds \"lpips\" to every record")
     ap.add_argument("--lpips_alex_ckpt", type=str, nargs="+", default=None,
@@ -314,6 +370,14 @@ def main(argv=None):
     anchor = args.anchor or ("jpeg" if args.anchor_quality is not None else None)
     if args.anchor_optimize and not anchor:
         ap.error("--anchor_optimize changes the anchor: give --anchor jpeg or --anchor_quality")
+    if args.anchor_scales is not None:
+        if not anchor:
+            ap.error("--anchor_scales changes the anchor: give --anchor jpeg or --anchor_quality")
+        if any(not 1 <= r <= 16 for r in args.anchor_scales) or len(set(args.anchor_scales)) != len(args.anchor_scales):
+            ap.error("--anchor_scales takes distinct integers in 1..16")
+        if args.anchor_quality is not None and len(args.anchor_scales) != 1:
+            ap.error("--anchor_quality fixes the quality: give exactly one scale with --anchor_scales")
+        args.anchor_scales = sorted(args.anchor_scales)
     if args.batch_size < 1:
         ap.error("--batch_size must be at least 1")
     if args.fid_patch < 0:
@@ -377,7 +441,8 @@ def main(argv=None):
             pm = [(k, model.measure(a, b)) for k, model in pair_metrics]
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
             decoded = [] if fid_sets is not None or clip_sets is not None or niqe_model is not None else None
-            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded, args.anchor_optimize) if anchor else None
+            anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded, args.anchor_optimize,
+                                   args.anchor_scales) if anchor else None
             if clip_sets is not None:
                 from .search import embedded_clip_codes
                 ua, qa = clip_sets.embed(a)

@@ -1041,6 +1041,33 @@ def clip_resize_coeffs(in_size, out_size, device):
     return bounds, kk, ksize
 
 
+RESIZE_FILTERS = {"lanczos": 1, "bicubic": 2}      # the C ABI's filter codes (Pillow's Image.BICUBIC is 3: the names, not the numbers, are shared with Pillow)
+
+
+def resize_u8(x_u8, OH, OW, filter="lanczos"):
+    """(B,H,W,3) u8 on the device -> (B,OH,OW,3) u8: the bytes of Pillow's Image.fromarray(x[b]).resize((OW, OH), filter) for
+    filter "lanczos" or "bicubic" (csrc/resize.hip).  Allocates the output and the workspace; does not synchronise"""
+    assert x_u8.dim() == 4 and x_u8.shape[3] == 3 and x_u8.dtype == torch.uint8 and x_u8.is_contiguous() and x_u8.is_cuda
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, not {filter!r}")
+    B, H, W, _ = x_u8.shape
+    OH, OW, f = int(OH), int(OW), RESIZE_FILTERS[filter]
+    nbytes = lib.sgic_resize_u8_work_bytes(B, H, W, OH, OW, f)      # 0: a geometry the call refuses (it says which)
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x_u8.device)
+    out = torch.empty(B, max(OH, 0), max(OW, 0), 3, dtype=torch.uint8, device=x_u8.device)
+    call("sgic_resize_u8_batch", _p(x_u8), B, H, W, _p(out), OH, OW, f, _p(work), ctypes.c_size_t(nbytes))
+    return out
+
+
+def resize_u8_coeffs(in_size, out_size, filter="lanczos"):
+    """the tables resize_u8 uses for one axis, made on the host as the call makes them -> (bounds int32 (out,2), kk int32 (out,ksize))"""
+    f = RESIZE_FILTERS[filter]
+    ksize = int(math.ceil((2.0 if f == 2 else 3.0) * max(in_size / out_size, 1.0))) * 2 + 1
+    bounds, kk = np.empty((out_size, 2), dtype=np.int32), np.empty((out_size, ksize), dtype=np.int32)
+    call("sgic_resize_u8_coeffs", int(in_size), int(out_size), f, ksize, bounds, kk)
+    return bounds, kk
+
+
 def topk_rows(scores, k):
     """scores (nq, n) fp32 on device (consumed) -> (top scores (nq,k), indices (nq,k) int32)"""
     nq, n = scores.shape
