@@ -706,6 +706,28 @@ int sgic_jpeg_encode_opt_batch(const uint8_t *d_rgb, int B, int H, int W, int su
                                size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff,
                                int32_t *d_nval, sgic_stream_t stream);
 
+/* The progressive file: what `save(format="JPEG", quality, subsampling, progressive=True)` writes, scan by scan.  The coefficients are
+ * those of the calls above; they are coded in the ten scans of libjpeg's jpeg_simple_progression -- (Y Cb Cr, 0-0, Al 1), (Y, 1-5, Al 2),
+ * (Cr, 1-63, Al 1), (Cb, 1-63, Al 1), (Y, 6-63, Al 2), (Y, 1-63, Ah 2 Al 1), (Y Cb Cr, 0-0, Ah 1 Al 0), (Cr, 1-63, Ah 1 Al 0), (Cb, the same),
+ * (Y, the same) -- every scan with Huffman tables fitted to its own symbols, all on the device.  Image b's ten entropy-coded
+ * segments (each padded with 1-bits to a byte and stuffed on its own, no markers between them, no EOI) lie back to back from
+ * d_out[b * cap]; d_len (B, 10) int32 holds their lengths.  d_huff (B, 10, 272) u8 and d_nval (B, 10) int32 are BITS, HUFFVAL and
+ * the HUFFVAL counts of the ten tables in file order: DC 0 and DC 1 of the first scan, then the AC table of scans 2, 3, 4, 5, 6, 8, 9,
+ * 10 (the seventh scan sends raw bits).  The host places SOF2, the DHT and SOS segments and EOI (sgic_amd/jpeg_enc.py).  A block takes
+ * at most 27 bits in the first scan, 1 in the seventh, (Se - Ss + 1) * (26 - Al) + 30 in a first AC scan (30: an EOBRUN symbol and its
+ * extra bits) and 63 * 17 + 48 + 30 = 1149 in a refinement scan; the largest, 1605, sets the limit of 2675992 coded blocks per
+ * image, so that a bit offset within a scan of an image fits 32 bits.  sgic_jpeg_encode_prog_cap is the sum over the scans of
+ * twice their largest stream (for 4:2:0 about 880 bytes per coded block).  It must stay below 2^31 as well: a geometry whose slot
+ * would be larger is refused by all three calls, which binds before the block limit at 4:2:2 and 4:2:0 (the largest accepted
+ * width at H = 10240 is 8032 and 10144; at 4:4:4 the block limit binds first).  d_err (B): 1 where the slot was too small, 2 where a
+ * code of some table would pass 32 bits before limiting (that table's d_nval entry is -1); the image's ten lengths are then 0.
+ * Every other argument and the refusals are those of sgic_jpeg_encode_opt_batch. */
+int sgic_jpeg_encode_prog_cap(int H, int W, int subsampling, size_t *cap);
+int sgic_jpeg_encode_prog_work_bytes(int B, int H, int W, int subsampling, size_t *bytes);
+int sgic_jpeg_encode_prog_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt, uint8_t *d_work,
+                                size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff,
+                                int32_t *d_nval, sgic_stream_t stream);
+
 /* Image.resize for u8 RGB on the device: d_in (B, H, W, 3) -> d_out (B, OH, OW, 3), both contiguous, one geometry per call: the bytes
  * of Pillow's `Image.fromarray(x).resize((OW, OH), filter)` (default box, reducing_gap=None; ImagingResample for 8-bit images).
  * filter: 2 = bicubic, 1 = Lanczos (this ABI's codes; Pillow numbers Image.BICUBIC 3).  Per axis the tables are precompute_coeffs' (22-bit fixed point after

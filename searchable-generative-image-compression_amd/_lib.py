@@ -33,6 +33,10 @@ lib.sgic_jpeg_encode_batch.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_v
 lib.sgic_jpeg_encode_opt_cap.argtypes = lib.sgic_jpeg_encode_cap.argtypes
 lib.sgic_jpeg_encode_opt_work_bytes.argtypes = lib.sgic_jpeg_encode_work_bytes.argtypes
 lib.sgic_jpeg_encode_opt_batch.argtypes = lib.sgic_jpeg_encode_batch.argtypes[:-1] + [c_void_p, c_void_p, c_void_p]
+# sgic_jpeg_encode_prog_batch: the optimised call's arguments, the outputs widened to ten scans
+lib.sgic_jpeg_encode_prog_cap.argtypes = lib.sgic_jpeg_encode_cap.argtypes
+lib.sgic_jpeg_encode_prog_work_bytes.argtypes = lib.sgic_jpeg_encode_work_bytes.argtypes
+lib.sgic_jpeg_encode_prog_batch.argtypes = lib.sgic_jpeg_encode_opt_batch.argtypes
 # sgic_lpips_head (csrc/lpips.hip): (d_feat, d_w, B, H, W, C, d_work, work_bytes, d_d, stream)
 lib.sgic_lpips_head_work_bytes.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_lpips_head.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
@@ -99,7 +103,8 @@ def ptr(t):
 _NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profiler_create", "sgic_profiler_begin", "sgic_profiler_end",
               "sgic_clip_preprocess_ragged_workspace", "sgic_clip_preprocess_u8canvas_workspace", "sgic_search_codes_u8_work_bytes",
               "sgic_search_codes_f32q_work_bytes", "sgic_search_rank_work_bytes", "sgic_assign_codes_f32c_work_bytes", "sgic_quality_u8_work_bytes", "sgic_jpeg_encode_cap",
-              "sgic_jpeg_encode_work_bytes", "sgic_jpeg_encode_opt_cap", "sgic_jpeg_encode_opt_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes",
+              "sgic_jpeg_encode_work_bytes", "sgic_jpeg_encode_opt_cap", "sgic_jpeg_encode_opt_work_bytes", "sgic_jpeg_encode_prog_cap",
+              "sgic_jpeg_encode_prog_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes",
               "sgic_niqe_u8_work_bytes", "sgic_resize_u8_coeffs"}
 
 

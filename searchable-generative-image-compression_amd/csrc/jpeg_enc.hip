@@ -13,6 +13,8 @@
 // own tables from the workspace, and two passes in front of them make those tables:
 //   hist   one thread per block: the symbols its codes would use, counted in LDS, then added to the image's four histograms
 //   tables one wavefront per (image, table): libjpeg's jpeg_gen_optimal_table -> code words, BITS and HUFFVAL
+// sgic_jpeg_encode_prog_batch writes the ten scans of save(..., progressive=True) from the same coefficients; its passes are listed
+// where it begins, below the optimised encoder's kernels.
 #include "common.h"
 
 namespace {
@@ -99,7 +101,8 @@ struct EPlan {
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-bool make_plan(int B, int H, int W, int sub, bool opt, EPlan *p) {
+// max_blocks: the caller's own block limit; 0: that of the baseline or the optimised call
+bool make_plan(int B, int H, int W, int sub, bool opt, EPlan *p, unsigned max_blocks = 0) {
   if (B < 1 || H < 1 || W < 1 || H > 16384 || W > 16384 || sub < 0 || sub > 2) return false;
   p->B = B; p->H = H; p->W = W;
   p->hs = sub == 0 ? 1 : 2;
@@ -111,7 +114,7 @@ bool make_plan(int B, int H, int W, int sub, bool opt, EPlan *p) {
   p->ny = p->hs * p->vs;
   p->bpm = p->ny + 2;
   const size_t nblk = (size_t)p->mx * p->my * p->bpm;
-  if (nblk > (opt ? MAX_BLOCKS_OPT : MAX_BLOCKS)) return false;
+  if (nblk > (max_blocks ? max_blocks : opt ? MAX_BLOCKS_OPT : MAX_BLOCKS)) return false;
   p->nblk = (int)nblk;
   p->nchunk = (int)((nblk + NT - 1) / NT);
   const size_t wpb = opt ? WORDS_PER_BLOCK_OPT : WORDS_PER_BLOCK;
@@ -270,16 +273,19 @@ __device__ __forceinline__ int dc_before(const EPlan &p, const int16_t *__restri
 
 // A sink takes the symbols of a block from code_block: sym(i, extra, nb) is the symbol at word i of the table layout (TAB_DC / TAB_AC)
 // followed by nb extra bits.
+// The progressive walks also send bits that no symbol leads: raw(v, n), the low n <= 63 bits of v.
 struct CountSink {
   const uint32_t *tab;
   unsigned bits;
   __device__ __forceinline__ void sym(int i, unsigned, int nb) { bits += (tab[i] & 0xff) + (unsigned)nb; }
+  __device__ __forceinline__ void raw(unsigned long long, int n) { bits += (unsigned)n; }
 };
 
 // counts symbols instead of bits: hist is a workgroup's histogram in LDS, in the table layout
 struct HistSink {
   unsigned *hist;
   __device__ __forceinline__ void sym(int i, unsigned, int) { atomicAdd(&hist[i], 1u); }
+  __device__ __forceinline__ void raw(unsigned long long, int) {}
 };
 
 // MSB first: bit i of the stream is bit 31 - i % 32 of word i / 32
@@ -309,6 +315,14 @@ struct PackSink {
   __device__ __forceinline__ void sym(int i, unsigned extra, int nb) {
     const uint32_t e = tab[i];
     put(((e >> 8) << nb) | extra, (int)(e & 0xff) + nb);
+  }
+  __device__ __forceinline__ void raw(unsigned long long v, int nb) {
+    if (nb > 32) {
+      put((unsigned)(v >> 32), nb - 32);
+      put((unsigned)v, 32);
+    } else if (nb) {
+      put((unsigned)v, nb);
+    }
   }
 };
 
@@ -686,6 +700,40 @@ __global__ __launch_bounds__(NT) void jpeg_enc_count_kernel(const uint32_t *__re
   }
 }
 
+// the workgroup's chunks of one stream (words, tbits bits in nbytes bytes) go to slot, stuffed; ffs: the stream's 0xFF counts in front
+// of every chunk; bytes at cap and beyond are left out
+__device__ __forceinline__ void emit_stuffed(const uint32_t *__restrict__ words, unsigned tbits, unsigned nbytes,
+                                             const uint32_t *__restrict__ ffs, uint8_t *__restrict__ slot, size_t cap, unsigned *red) {
+  for (unsigned c = blockIdx.x; (size_t)c * CHUNK_WORDS * 4 < nbytes; c += gridDim.x) {
+    const unsigned wi = c * CHUNK_WORDS + threadIdx.x * 4;
+    const bool live = (size_t)wi * 4 < nbytes;
+    uint4 w = make_uint4(0, 0, 0, 0);
+    unsigned n = 0;
+    if (live) {
+      w = padded_words(words, wi, tbits);
+      n = count_ff(w.x) + count_ff(w.y) + count_ff(w.z) + count_ff(w.w);
+    }
+    unsigned total;
+    const unsigned before = wg_exclusive_scan(n, red, &total);
+    if (live) {
+      size_t o = (size_t)wi * 4 + ffs[c] + before;
+      const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        if ((size_t)wi * 4 + j < nbytes) {
+          const unsigned byte = (ww[j >> 2] >> (24 - 8 * (j & 3))) & 0xff;
+          if (o < cap) slot[o] = (uint8_t)byte;
+          ++o;
+          if (byte == 0xff) {
+            if (o < cap) slot[o] = 0;
+            ++o;
+          }
+        }
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
                                                            const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
                                                            int32_t *__restrict__ lens, int32_t *__restrict__ err,
@@ -694,36 +742,8 @@ __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__res
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
     const unsigned tbits = tot[(size_t)img * 2];
     const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
-    const uint32_t *words = bits + (size_t)img * p.words;
     uint8_t *slot = out + (size_t)img * cap;
-    for (unsigned c = blockIdx.x; (size_t)c * CHUNK_WORDS * 4 < nbytes; c += gridDim.x) {
-      const unsigned wi = c * CHUNK_WORDS + threadIdx.x * 4;
-      const bool live = (size_t)wi * 4 < nbytes;
-      uint4 w = make_uint4(0, 0, 0, 0);
-      unsigned n = 0;
-      if (live) {
-        w = padded_words(words, wi, tbits);
-        n = count_ff(w.x) + count_ff(w.y) + count_ff(w.z) + count_ff(w.w);
-      }
-      unsigned total;
-      const unsigned before = wg_exclusive_scan(n, red, &total);
-      if (live) {
-        size_t o = (size_t)wi * 4 + ffsum[(size_t)img * p.nbchunk + c] + before;
-        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          if ((size_t)wi * 4 + j < nbytes) {
-            const unsigned byte = (ww[j >> 2] >> (24 - 8 * (j & 3))) & 0xff;
-            if (o < cap) slot[o] = (uint8_t)byte;
-            ++o;
-            if (byte == 0xff) {
-              if (o < cap) slot[o] = 0;
-              ++o;
-            }
-          }
-        }
-      }
-    }
+    emit_stuffed(bits + (size_t)img * p.words, tbits, nbytes, ffsum + (size_t)img * p.nbchunk, slot, cap, red);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       const size_t len = (size_t)nbytes + tot[(size_t)img * 2 + 1] + 2;
       const bool fits = len <= cap;
@@ -737,6 +757,651 @@ __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__res
       err[img] = !coded ? 2 : fits ? 0 : 1;
     }
   }
+}
+
+// ---- progressive: sgic_jpeg_encode_prog_batch -----------------------------------------------------------------
+// The file of save(..., progressive=True): the coefficients of coef, coded in the ten scans of libjpeg's jpeg_simple_progression, every
+// scan with tables fitted to it.  A scan runs the chain of the optimised encoder (hist, tables, bits, scan, pack, count, scan, emit)
+// over its own blocks: the two DC scans over the MCU order of coef, an AC scan over its component's raster without dummy blocks.
+// An AC scan's end-of-band runs span blocks, so three or more passes in front of the chain say which blocks lead an EOBRUN symbol:
+//   flags  one thread per block: does it code a coefficient (nz), does it end in zeros or pending correction bits (tail), how many
+//          correction bits trail it; per workgroup the last and the first nz block and the sum of those bits
+//   link   one workgroup per image: the last nz block in front of every workgroup, the first one behind it, the bits in front of it
+//   runs   one thread per block: the run it lies in (from the nz block in front of it to the one behind it).  First scans: the heads
+//          are every 0x7FFF blocks from the run's start.  Refinement scans: prefix sums of the correction bits, the run starts
+//   next   refinement: the head that follows if this block is one (binary search in the prefix sums: 0x7FFF blocks or 937 bits)
+//   round  refinement: every marked head marks its successor, then next := next o next; ceil(log2(n / 15)) + 1 rounds mark all
+constexpr int K_DC_FIRST = 0, K_DC_REFINE = 1, K_AC_FIRST = 2, K_AC_REFINE = 3;
+constexpr int NSCAN = 10;
+constexpr int EOBRUN_MAX = 0x7FFF;
+constexpr unsigned CORR_BITS = 937;       // libjpeg's MAX_CORR_BITS - DCTSIZE2 + 1: a run is cut once its correction bits pass this
+constexpr int EOBRUN_BITS = 16 + 14;      // the symbol and its extra bits
+// the bits of a block in a scan: a DC difference of at most 11 bits; a refinement bit; in a first scan (10 - Al)-bit values behind
+// 16-bit codes; in a refinement scan a code, a sign and no correction bit per coefficient at the most, three ZRL at the most
+constexpr unsigned dc_first_bits() { return 16 + 11; }
+constexpr unsigned ac_first_bits(int ss, int se, int al) { return (unsigned)(se - ss + 1) * (16 + 10 - al) + EOBRUN_BITS; }
+constexpr unsigned ac_refine_bits(int ss, int se) { return (unsigned)(se - ss + 1) * 17 + 3 * 16 + EOBRUN_BITS; }
+constexpr unsigned MAX_SCAN_BITS = ac_first_bits(1, 63, 1);       // the largest of the ten scans: chroma, 1 .. 63 at Al = 1
+constexpr unsigned MAX_BLOCKS_PROG = 2675992;
+constexpr size_t MAX_SLOT_BYTES = 0x7fffffff;      // the second limit: an image's slot, which d_len and cap count in 31 bits
+static_assert(MAX_SCAN_BITS == 1605 && ac_first_bits(6, 63, 2) < MAX_SCAN_BITS && ac_refine_bits(1, 63) == 1149, "per-block bounds");
+static_assert((unsigned long long)MAX_BLOCKS_PROG * MAX_SCAN_BITS < (1ull << 32) &&
+              (unsigned long long)(MAX_BLOCKS_PROG + 1) * MAX_SCAN_BITS >= (1ull << 32), "32-bit bit offsets within a scan of an image");
+static_assert((CORR_BITS + 1 + 62) / 63 == 15, "a segment that the correction bits cut holds at least 15 blocks");
+
+struct PScan {
+  int kind;
+  int comp;          // AC scans: the component
+  int ss, se, al;
+  int tab;           // AC scans: the table's place in the table layout
+  int slot;          // the scan's first table in d_huff / d_nval; -1: none
+  int ntab, tw[2];   // its tables and the wavefronts of jpeg_enc_tables_kernel that build them (0 DC 0, 1 AC 0, 2 DC 1, 3 AC 1)
+  int n;             // blocks of the scan per image
+  int nchunk;        // workgroups of NT blocks
+  int rounds;
+  unsigned bound;    // bits of a block at the most
+  int nbchunk;
+  size_t words;      // u32 words of one image's bit stream in this scan
+  size_t off_bits;
+};
+
+struct PPlan {
+  EPlan e;
+  PScan scan[NSCAN];
+  size_t off_blk, off_mark, off_cnt, off_re, off_pre, off_next, off_clast, off_cfirst, off_ctb, off_huff4, off_nval4, off_pos;
+};
+
+bool make_prog_plan(int B, int H, int W, int sub, PPlan *pp) {
+  EPlan &p = pp->e;
+  if (!make_plan(B, H, W, sub, true, &p, MAX_BLOCKS_PROG)) return false;
+  // jpeg_simple_progression for three components: (kind, component, Ss, Se, Al, first table)
+  const int script[NSCAN][6] = {{K_DC_FIRST, 0, 0, 0, 1, 0},  {K_AC_FIRST, 0, 1, 5, 2, 2},   {K_AC_FIRST, 2, 1, 63, 1, 3},
+                                {K_AC_FIRST, 1, 1, 63, 1, 4}, {K_AC_FIRST, 0, 6, 63, 2, 5},  {K_AC_REFINE, 0, 1, 63, 1, 6},
+                                {K_DC_REFINE, 0, 0, 0, 0, -1}, {K_AC_REFINE, 2, 1, 63, 0, 7}, {K_AC_REFINE, 1, 1, 63, 0, 8},
+                                {K_AC_REFINE, 0, 1, 63, 0, 9}};
+  const size_t nblk = (size_t)p.nblk;
+  size_t o = p.off_tabs + align16((size_t)B * TAB_WORDS * sizeof(uint32_t));      // coef, qt, local, csum and tabs are the optimised plan's
+  pp->off_blk = o;     o += align16((size_t)B * nblk);
+  pp->off_mark = o;    o += align16((size_t)B * nblk);
+  pp->off_cnt = o;     o += align16((size_t)B * nblk * sizeof(uint16_t));
+  pp->off_re = o;      o += align16((size_t)B * nblk * sizeof(uint32_t));
+  pp->off_pre = o;     o += align16((size_t)B * (nblk + 1) * sizeof(uint32_t));
+  pp->off_next = o;    o += align16((size_t)2 * B * nblk * sizeof(uint32_t));
+  pp->off_clast = o;   o += align16((size_t)B * p.nchunk * sizeof(int32_t));
+  pp->off_cfirst = o;  o += align16((size_t)B * p.nchunk * sizeof(int32_t));
+  pp->off_ctb = o;     o += align16((size_t)B * p.nchunk * sizeof(uint32_t));
+  pp->off_huff4 = o;   o += align16((size_t)B * 4 * HUFF_BYTES);      // what jpeg_enc_tables_kernel writes for the scan at hand
+  pp->off_nval4 = o;   o += align16((size_t)B * 4 * sizeof(int32_t));
+  // zeroed by one memset: the byte positions of the scans in the slots, the histograms of a scan (zeroed again for every later
+  // scan), the bit streams of the ten scans
+  pp->off_pos = o;     o += align16((size_t)(NSCAN + 1) * B * sizeof(unsigned long long));
+  p.off_hist = o;      o += (size_t)B * TAB_WORDS * sizeof(uint32_t);
+  p.cap = 0;
+  p.nbchunk = 0;
+  for (int s = 0; s < NSCAN; ++s) {
+    PScan &sc = pp->scan[s];
+    sc.kind = script[s][0]; sc.comp = script[s][1]; sc.ss = script[s][2]; sc.se = script[s][3]; sc.al = script[s][4];
+    sc.slot = script[s][5];
+    sc.tab = TAB_AC + (sc.comp ? 256 : 0);
+    sc.ntab = sc.kind == K_DC_FIRST ? 2 : sc.kind == K_DC_REFINE ? 0 : 1;
+    sc.tw[0] = sc.kind == K_DC_FIRST ? 0 : sc.comp ? 3 : 1;
+    sc.tw[1] = 2;
+    sc.n = sc.kind < K_AC_FIRST ? p.nblk : sc.comp ? p.mx * p.my : p.wb * p.hb;
+    sc.nchunk = (sc.n + NT - 1) / NT;
+    sc.rounds = 0;
+    if (sc.kind == K_AC_REFINE) {
+      int k = 0;
+      while (((size_t)15 << k) < (size_t)sc.n) ++k;
+      sc.rounds = k + 1;
+    }
+    sc.bound = sc.kind == K_DC_FIRST ? dc_first_bits() : sc.kind == K_DC_REFINE ? 1 : sc.kind == K_AC_FIRST ? ac_first_bits(sc.ss, sc.se, sc.al)
+                                                                                                           : ac_refine_bits(sc.ss, sc.se);
+    sc.words = (((size_t)sc.n * sc.bound + 31) / 32 + 1 + 3) & ~(size_t)3;
+    sc.nbchunk = (int)((sc.words + CHUNK_WORDS - 1) / CHUNK_WORDS);
+    if (sc.nbchunk > p.nbchunk) p.nbchunk = sc.nbchunk;
+    sc.off_bits = o;   o += (size_t)B * sc.words * sizeof(uint32_t);
+    p.cap += sc.words * 8;        // every byte of a stream may be 0xFF and take a stuffed zero
+  }
+  if (p.cap > MAX_SLOT_BYTES) return false;      // lengths and the caller's cap are 31-bit
+  p.off_bits = p.off_hist;        // nothing of the optimised plan's single stream is left
+  p.off_ffsum = o;   o += align16((size_t)B * p.nbchunk * sizeof(uint32_t));
+  p.off_tot = o;     o += align16((size_t)B * 2 * sizeof(uint32_t));
+  p.bytes = o;
+  return true;
+}
+
+struct NullSink {
+  __device__ __forceinline__ void sym(int, unsigned, int) {}
+  __device__ __forceinline__ void raw(unsigned long long, int) {}
+};
+
+// coefficient k (a constant under unrolling) of a block in c
+__device__ __forceinline__ int coef_of(const uint4 (&c)[8], int k) {
+  const unsigned w = (k & 7) < 2 ? c[k >> 3].x : (k & 7) < 4 ? c[k >> 3].y : (k & 7) < 6 ? c[k >> 3].z : c[k >> 3].w;
+  return (int)(short)((k & 1) ? (w >> 16) : (w & 0xffff));
+}
+
+__device__ __forceinline__ void load_block(uint4 (&c)[8], const int16_t *__restrict__ ci, int t) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) c[j] = src[j];
+}
+
+// block i of a scan -> its place in coef
+template <int K>
+__device__ __forceinline__ int scan_block(const EPlan &p, const PScan &s, int i) {
+  if (K < K_AC_FIRST) return i;
+  if (s.comp) return i * p.bpm + p.ny + s.comp - 1;
+  const int by = i / p.wb, bx = i - by * p.wb;
+  return ((by / p.vs) * p.mx + bx / p.hs) * p.bpm + (by % p.vs) * p.hs + bx % p.hs;
+}
+
+// A first AC scan's symbols of one block without its EOBRUN: -> tail (the band ends in zeros); nz: a coefficient was coded
+template <typename Sink>
+__device__ __forceinline__ bool walk_ac_first(Sink &sink, const uint4 (&c)[8], const PScan &s, bool &nz) {
+  int run = 0;
+  nz = false;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    if (k < s.ss || k > s.se) continue;
+    const int v = coef_of(c, k);
+    const int a = abs(v) >> s.al;
+    if (a == 0) {
+      ++run;
+      continue;
+    }
+    nz = true;
+    for (; run > 15; run -= 16) sink.sym(s.tab + 0xF0, 0, 0);
+    const int nb = 32 - __clz(a);
+    sink.sym(s.tab + ((run << 4) | nb), (unsigned)(v < 0 ? ~a : a) & ((1u << nb) - 1), nb);
+    run = 0;
+  }
+  return run > 0;
+}
+
+// A refinement AC scan's symbols of one block without its EOBRUN and without the nbr correction bits br that trail it:
+// -> tail (zeros or correction bits are pending at the band's end); nz: a symbol was coded
+template <typename Sink>
+__device__ __forceinline__ bool walk_ac_refine(Sink &sink, const uint4 (&c)[8], const PScan &s, bool &nz, unsigned long long &br, int &nbr) {
+  // one pass over the coefficients leaves four masks by position: non-zero, becomes non-zero in this scan, negative, correction bit
+  unsigned long long nonzero = 0, one = 0, neg = 0, low = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    if (k < s.ss || k > s.se) continue;
+    const int v = coef_of(c, k);
+    const int a = abs(v) >> s.al;
+    const unsigned long long bit = 1ull << k;
+    if (a) nonzero |= bit;
+    if (a == 1) one |= bit;
+    if (v < 0) neg |= bit;
+    if (a & 1) low |= bit;
+  }
+  const int eob = one ? 63 - __clzll(one) : 0;      // the last coefficient that becomes non-zero in this scan
+  int run = 0;
+  nz = false;
+  br = 0;
+  nbr = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    if (k < s.ss || k > s.se) continue;
+    const unsigned long long bit = 1ull << k;
+    if (!(nonzero & bit)) {
+      ++run;
+      continue;
+    }
+    while (run > 15 && k <= eob) {
+      sink.sym(s.tab + 0xF0, 0, 0);
+      sink.raw(br, nbr);
+      run -= 16;
+      br = 0;
+      nbr = 0;
+      nz = true;
+    }
+    if (!(one & bit)) {
+      br = (br << 1) | ((low >> k) & 1);
+      ++nbr;
+      continue;
+    }
+    sink.sym(s.tab + ((run << 4) | 1), (neg & bit) ? 0u : 1u, 1);
+    sink.raw(br, nbr);
+    run = 0;
+    br = 0;
+    nbr = 0;
+    nz = true;
+  }
+  return run > 0 || nbr > 0;
+}
+
+// Everything block i of a scan sends, in stream order: its own symbols, the EOBRUN symbol if it heads a segment of head blocks, its
+// trailing correction bits.  ci: the image's coefficients.
+template <int K, typename Sink>
+__device__ __forceinline__ void prog_block(Sink &sink, const EPlan &p, const PScan &s, const int16_t *__restrict__ ci, int i, unsigned head) {
+  const int t = scan_block<K>(p, s, i);
+  if (K == K_DC_FIRST || K == K_DC_REFINE) {
+    int comp, bx, by;
+    const bool real = block_of(p, t, comp, bx, by);
+    const int before = dc_before(p, ci, t);
+    if (K == K_DC_FIRST) {
+      // a dummy block repeats the DC before it: difference 0 in the luma table
+      const int diff = real ? ((int)ci[(size_t)t * 64] >> s.al) - (before >> s.al) : 0;
+      const int nb = min(32 - __clz(abs(diff)), 11);
+      sink.sym(TAB_DC + (real && comp ? 12 : 0) + nb, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1), nb);
+    } else {
+      sink.raw((unsigned)(((real ? (int)ci[(size_t)t * 64] : before) >> s.al) & 1), 1);
+    }
+    return;
+  }
+  uint4 c[8];
+  load_block(c, ci, t);
+  bool nz;
+  unsigned long long br = 0;
+  int nbr = 0;
+  if (K == K_AC_FIRST)
+    walk_ac_first(sink, c, s, nz);
+  else
+    walk_ac_refine(sink, c, s, nz, br, nbr);
+  if (head) {
+    const int n = 31 - __clz(head);
+    sink.sym(s.tab + (n << 4), head & ((1u << n) - 1), n);
+  }
+  if (K == K_AC_REFINE) sink.raw(br, nbr);
+}
+
+// blk (B, nblk): nz | tail << 1 | trailing correction bits << 2 of every block of the scan; clast, cfirst, ctb (B, p.nchunk): the
+// workgroup's last nz block (-1: none), its first (s.n: none), the sum of its trailing bits
+template <bool REFINE>
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_flags_kernel(const int16_t *__restrict__ coef, uint8_t *__restrict__ blk,
+                                                                 int32_t *__restrict__ clast, int32_t *__restrict__ cfirst,
+                                                                 uint32_t *__restrict__ ctb, EPlan p, PScan s) {
+  __shared__ unsigned red[NT / 64];
+  __shared__ int s_last, s_first;
+  const int i = blockIdx.x * NT + threadIdx.x;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    if (threadIdx.x == 0) {
+      s_last = -1;
+      s_first = s.n;
+    }
+    __syncthreads();
+    int nbr = 0;
+    if (i < s.n) {
+      uint4 c[8];
+      load_block(c, coef + (size_t)img * p.nblk * 64, scan_block<K_AC_FIRST>(p, s, i));
+      NullSink sink;
+      bool nz, tail;
+      unsigned long long br;
+      if (REFINE)
+        tail = walk_ac_refine(sink, c, s, nz, br, nbr);
+      else
+        tail = walk_ac_first(sink, c, s, nz);
+      blk[(size_t)img * p.nblk + i] = (uint8_t)((nz ? 1 : 0) | (tail ? 2 : 0) | (nbr << 2));
+      if (nz) {
+        atomicMax(&s_last, i);
+        atomicMin(&s_first, i);
+      }
+    }
+    unsigned total;
+    wg_exclusive_scan((unsigned)nbr, red, &total);      // its barriers also end the atomics above
+    if (threadIdx.x == 0) {
+      clast[(size_t)img * p.nchunk + blockIdx.x] = s_last;
+      cfirst[(size_t)img * p.nchunk + blockIdx.x] = s_first;
+      ctb[(size_t)img * p.nchunk + blockIdx.x] = total;
+    }
+    __syncthreads();
+  }
+}
+
+// exclusive maximum scan of one value per thread over the workgroup, none standing for "no value"; *total: the maximum
+__device__ __forceinline__ int wg_exclusive_max(int v, int none, int *red, int *total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc = max(inc, o);
+  }
+  const int prev = __shfl_up(inc, 1, 64);
+  if (lane == 63) red[wave] = inc;
+  __syncthreads();
+  int before = none, all = none;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    const int r = red[w];
+    if (w < wave) before = max(before, r);
+    all = max(all, r);
+  }
+  __syncthreads();
+  *total = all;
+  return lane ? max(before, prev) : before;
+}
+
+// One workgroup per image, over the n workgroups of the flags pass: clast becomes the last nz block in front of the workgroup (-1),
+// cfirst the first one behind it (nblocks), ctb the trailing bits in front of it
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_link_kernel(int32_t *__restrict__ clast, int32_t *__restrict__ cfirst,
+                                                                uint32_t *__restrict__ ctb, int stride, int n, int nblocks, int B) {
+  __shared__ unsigned red[NT / 64];
+  __shared__ int redi[NT / 64];
+  for (int img = blockIdx.x; img < B; img += gridDim.x) {
+    int32_t *la = clast + (size_t)img * stride, *fi = cfirst + (size_t)img * stride;
+    uint32_t *tb = ctb + (size_t)img * stride;
+    int last = -1, first = -nblocks;      // first: the negated minimum, so that it is a maximum scan from the back
+    unsigned bits = 0;
+    for (int base = 0; base < n; base += NT) {
+      const int i = base + threadIdx.x, j = n - 1 - i;
+      const int x = i < n ? la[i] : -1, y = i < n ? -fi[j] : -nblocks;
+      const unsigned z = i < n ? tb[i] : 0;
+      int xt, yt;
+      unsigned zt;
+      const int xe = wg_exclusive_max(x, -1, redi, &xt), ye = wg_exclusive_max(y, -nblocks, redi, &yt);
+      const unsigned ze = wg_exclusive_scan(z, red, &zt);
+      if (i < n) {
+        la[i] = max(last, xe);
+        fi[j] = -max(first, ye);
+        tb[i] = bits + ze;
+      }
+      last = max(last, xt);
+      first = max(first, yt);
+      bits += zt;
+    }
+  }
+}
+
+// One thread per block of an AC scan: the run it lies in.  mark: first scans, the block heads a segment; refinement scans, it starts a
+// run.  cnt: first scans, the blocks from here to the segment's end.  re: refinement scans, the run's end (0: the block is in no run).
+// pre (B, nblk + 1): refinement scans, the trailing bits in front of every block of the scan and their sum.
+template <bool REFINE>
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_runs_kernel(const uint8_t *__restrict__ blk, const int32_t *__restrict__ clast,
+                                                                const int32_t *__restrict__ cfirst, const uint32_t *__restrict__ ctb,
+                                                                uint8_t *__restrict__ mark, uint16_t *__restrict__ cnt,
+                                                                uint32_t *__restrict__ re, uint32_t *__restrict__ pre, EPlan p, PScan s) {
+  __shared__ unsigned long long masks[NT / 64];
+  __shared__ unsigned red[NT / 64];
+  const int i = blockIdx.x * NT + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const uint8_t *bi = blk + (size_t)img * p.nblk;
+    const size_t cb = (size_t)img * p.nchunk + blockIdx.x;
+    const unsigned f = i < s.n ? bi[i] : 0;
+    const bool nz = f & 1;
+    const unsigned long long mask = __ballot(nz);
+    if (lane == 0) masks[wave] = mask;
+    __syncthreads();
+    // the last nz block at or in front of i, the first one behind i
+    int last = clast[cb], next = cfirst[cb];
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+      const unsigned long long m = masks[w];
+      if (w < wave && m) last = blockIdx.x * NT + w * 64 + 63 - __clzll(m);
+    }
+#pragma unroll
+    for (int w = NT / 64 - 1; w >= 0; --w) {
+      const unsigned long long m = masks[w];
+      if (w > wave && m) next = blockIdx.x * NT + w * 64 + __ffsll(m) - 1;
+    }
+    const unsigned long long upto = lane == 63 ? mask : mask & ((2ull << lane) - 1), behind = lane == 63 ? 0ull : mask >> (lane + 1);
+    if (upto) last = blockIdx.x * NT + wave * 64 + 63 - __clzll(upto);
+    if (behind) next = i + __ffsll(behind);
+    // an nz block with a tail starts a run; other blocks follow the nz block in front of them, which starts their run if it has a tail
+    const bool inrun = !nz || (f & 2);
+    int start = i;
+    if (!nz) start = last < 0 ? 0 : (bi[last] & 2) ? last : last + 1;
+    if (REFINE) {
+      unsigned total;
+      const unsigned off = ctb[cb] + wg_exclusive_scan(f >> 2, red, &total);
+      if (i < s.n) {
+        uint32_t *pi = pre + (size_t)img * (p.nblk + 1);
+        pi[i] = off;
+        if (i == s.n - 1) pi[s.n] = off + (f >> 2);
+        re[(size_t)img * p.nblk + i] = inrun ? (uint32_t)next : 0u;
+        mark[(size_t)img * p.nblk + i] = inrun && start == i;
+      }
+    } else if (i < s.n) {
+      mark[(size_t)img * p.nblk + i] = inrun && (i - start) % EOBRUN_MAX == 0;
+      cnt[(size_t)img * p.nblk + i] = (uint16_t)min(EOBRUN_MAX, next - i);
+    }
+    __syncthreads();
+  }
+}
+
+// Refinement scans, one thread per block in a run: the segment from it ends with the block that fills EOBRUN_MAX or takes the
+// correction bits past CORR_BITS, at the run's end at the latest.  cnt: its blocks; next: the head behind it, s.n if the run ends.
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_next_kernel(const uint32_t *__restrict__ re, const uint32_t *__restrict__ pre,
+                                                                uint16_t *__restrict__ cnt, uint32_t *__restrict__ next, EPlan p, PScan s) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= s.n) return;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const int end = (int)re[(size_t)img * p.nblk + i];
+    int c = 0, nx = s.n;
+    if (end) {
+      const uint32_t *pi = pre + (size_t)img * (p.nblk + 1);
+      const unsigned t0 = pi[i];
+      int lo = i, hi = min(end, i + EOBRUN_MAX) - 1;       // the segment's last block lies in [lo, hi]
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pi[mid + 1] - t0 > CORR_BITS) hi = mid; else lo = mid + 1;
+      }
+      c = lo + 1 - i;
+      if (lo + 1 < end) nx = lo + 1;
+    }
+    cnt[(size_t)img * p.nblk + i] = (uint16_t)c;
+    next[(size_t)img * p.nblk + i] = (uint32_t)nx;
+  }
+}
+
+// One doubling round: a marked block marks the head `from` names, and to = from o from.  mark is read and written in the same
+// launch without atomics: the only writes are byte stores of the constant 1, to bytes that are heads.  A mark that appears while the
+// round runs is a head too, so it may or may not act in this round: the marks after the last round are the same.
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_round_kernel(const uint32_t *__restrict__ from, uint32_t *__restrict__ to,
+                                                                 uint8_t *mark, EPlan p, PScan s) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= s.n) return;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const size_t o = (size_t)img * p.nblk;
+    const uint32_t nx = from[o + i];
+    uint32_t nn = (uint32_t)s.n;
+    if (nx < (uint32_t)s.n) {
+      if (mark[o + i]) mark[o + nx] = 1;
+      nn = from[o + nx];
+    }
+    to[o + i] = nn;
+  }
+}
+
+__device__ __forceinline__ unsigned head_of(const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt, size_t at) {
+  return mark[at] ? cnt[at] : 0u;
+}
+
+// hist (B, TAB_WORDS), zeroed by the call for this scan
+template <int K>
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_hist_kernel(const int16_t *__restrict__ coef, const uint8_t *__restrict__ mark,
+                                                                const uint16_t *__restrict__ cnt, uint32_t *__restrict__ hist, EPlan p,
+                                                                PScan s) {
+  __shared__ unsigned h[TAB_WORDS];
+  const int i = blockIdx.x * NT + threadIdx.x;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    for (int j = threadIdx.x; j < TAB_WORDS; j += NT) h[j] = 0;
+    __syncthreads();
+    if (i < s.n) {
+      HistSink sink{h};
+      prog_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, K >= K_AC_FIRST ? head_of(mark, cnt, (size_t)img * p.nblk + i) : 0u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < TAB_WORDS; j += NT)
+      if (h[j]) atomicAdd(&hist[(size_t)img * TAB_WORDS + j], h[j]);
+    __syncthreads();
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_bits_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
+                                                                const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt,
+                                                                uint32_t *__restrict__ local, uint32_t *__restrict__ csum, EPlan p, PScan s) {
+  __shared__ uint32_t tab[TAB_WORDS];
+  __shared__ unsigned red[NT / 64];
+  const int i = blockIdx.x * NT + threadIdx.x;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    if (K != K_DC_REFINE) stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);     // the scan below ends with a barrier, so nobody still reads tab
+    CountSink sink{tab, 0};
+    if (i < s.n)
+      prog_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, K >= K_AC_FIRST ? head_of(mark, cnt, (size_t)img * p.nblk + i) : 0u);
+    unsigned total;
+    const unsigned off = wg_exclusive_scan(sink.bits, red, &total);
+    if (i < s.n) local[(size_t)img * p.nblk + i] = off;
+    if (threadIdx.x == 0) csum[(size_t)img * p.nchunk + blockIdx.x] = total;
+  }
+}
+
+// bits: the scan's zeroed streams (B, s.words)
+template <int K>
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
+                                                                const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt,
+                                                                const uint32_t *__restrict__ local, const uint32_t *__restrict__ csum,
+                                                                uint32_t *__restrict__ bits, EPlan p, PScan s) {
+  __shared__ uint32_t tab[TAB_WORDS];
+  const int i = blockIdx.x * NT + threadIdx.x;
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    if (K != K_DC_REFINE) {
+      __syncthreads();                    // the image before this one has been coded from tab
+      stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);
+    }
+    if (i >= s.n) continue;
+    const unsigned pos = csum[(size_t)img * p.nchunk + blockIdx.x] + local[(size_t)img * p.nblk + i];
+    PackSink sink{tab, bits + (size_t)img * s.words, pos >> 5, 0ull, (int)(pos & 31), true};
+    prog_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, K >= K_AC_FIRST ? head_of(mark, cnt, (size_t)img * p.nblk + i) : 0u);
+    if (sink.n) atomicOr(&sink.words[sink.wi], (uint32_t)(sink.acc << (32 - sink.n)));
+  }
+}
+
+// The scan's stuffed bytes follow those of the scans before it in the image's slot: pos (NSCAN + 1, B) holds where every scan
+// begins.  lens (B, NSCAN).  The scan's tables move from where jpeg_enc_tables_kernel left them (huff4, nval4: four per image) to
+// their slots of huff (B, NSCAN, HUFF_BYTES) and nval (B, NSCAN).  The last scan also sets the error word: 2 if a table had a code
+// that libjpeg refuses, 1 if the slot was too small; the image's lengths are then zero.
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
+                                                                const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
+                                                                int32_t *__restrict__ lens, int32_t *__restrict__ err,
+                                                                const uint8_t *__restrict__ huff4, const int32_t *__restrict__ nval4,
+                                                                uint8_t *__restrict__ huff, int32_t *__restrict__ nval,
+                                                                unsigned long long *__restrict__ pos, int scan, EPlan p, PScan s) {
+  __shared__ unsigned red[NT / 64];
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const unsigned tbits = tot[(size_t)img * 2];
+    const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
+    const unsigned long long at = pos[(size_t)scan * p.B + img];
+    const size_t room = at < cap ? cap - (size_t)at : 0;
+    emit_stuffed(bits + (size_t)img * s.words, tbits, nbytes, ffsum + (size_t)img * p.nbchunk, out + (size_t)img * cap + (cap - room), room, red);
+    if (blockIdx.x == 0) {
+      for (int j = 0; j < s.ntab; ++j) {
+        const uint8_t *src = huff4 + ((size_t)img * 4 + s.tw[j]) * HUFF_BYTES;
+        uint8_t *dst = huff + ((size_t)img * NSCAN + s.slot + j) * HUFF_BYTES;
+        for (int b = threadIdx.x; b < HUFF_BYTES; b += NT) dst[b] = src[b];
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      for (int j = 0; j < s.ntab; ++j) nval[(size_t)img * NSCAN + s.slot + j] = nval4[(size_t)img * 4 + s.tw[j]];
+      const unsigned long long len = (unsigned long long)nbytes + tot[(size_t)img * 2 + 1], end = at + len;
+      pos[(size_t)(scan + 1) * p.B + img] = end;
+      lens[(size_t)img * NSCAN + scan] = (int32_t)len;
+      if (scan == NSCAN - 1) {
+        bool coded = true;
+        for (int j = 0; j < NSCAN; ++j) coded = coded && nval[(size_t)img * NSCAN + j] >= 0;
+        const bool fits = end <= cap;
+        if (!fits || !coded)
+          for (int j = 0; j < NSCAN; ++j) lens[(size_t)img * NSCAN + j] = 0;
+        err[img] = !coded ? 2 : fits ? 0 : 1;
+      }
+    }
+  }
+}
+
+// the workspace arrays that the chain of a scan shares
+struct PWork {
+  const int16_t *coef;
+  uint32_t *hist, *tabs;
+  uint8_t *huff4;
+  int32_t *nval4;
+  const uint8_t *mark;
+  const uint16_t *cnt;
+  uint32_t *local, *csum, *tot;
+};
+
+// hist, tables, bits, scan and pack of one scan.  The tables are built by the optimised encoder's kernel as it is: the scan's symbols
+// are counted where that kernel's layout has the table, the other histograms stay zero and give empty tables.
+template <int K>
+void launch_prog_chain(const EPlan &p, const PScan &sc, dim3 grid, unsigned gy, const PWork &w, uint32_t *bits, hipStream_t st) {
+  if constexpr (K != K_DC_REFINE) {
+    jpeg_enc_prog_hist_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.mark, w.cnt, w.hist, p, sc);
+    jpeg_enc_tables_kernel<<<gy, NT, 0, st>>>(w.hist, w.tabs, w.huff4, w.nval4, p.B);
+  }
+  jpeg_enc_prog_bits_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.tabs, w.mark, w.cnt, w.local, w.csum, p, sc);
+  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(w.csum, p.nchunk, sc.nchunk, w.tot, 0, 0, p.B);
+  jpeg_enc_prog_pack_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.tabs, w.mark, w.cnt, w.local, w.csum, bits, p, sc);
+}
+
+#define JPEG_ENC_PROG_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2675992 coded blocks per image and a slot below 2^31 bytes"
+
+int encode_prog_batch(const char *name, const PPlan &pp, const uint8_t *d_rgb, int B, const uint16_t *h_qt, uint8_t *d_work,
+                      size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff, int32_t *d_nval,
+                      sgic_stream_t stream) {
+  const EPlan &p = pp.e;
+  SGIC_REQUIRE_AS(name, d_rgb && h_qt && d_work && d_out && d_len && d_err && d_huff && d_nval, "null pointer");
+  SGIC_REQUIRE_AS(name, ((uintptr_t)d_work & 15) == 0, "the workspace must be 16-byte aligned");
+  SGIC_REQUIRE_AS(name, ((uintptr_t)h_qt & 1) == 0 && ((uintptr_t)d_len & 3) == 0 && ((uintptr_t)d_err & 3) == 0 &&
+                            ((uintptr_t)d_huff & 3) == 0 && ((uintptr_t)d_nval & 3) == 0, "misaligned pointer");
+  SGIC_REQUIRE_AS(name, work_bytes >= p.bytes, "the workspace is smaller than sgic_jpeg_encode_prog_work_bytes says");
+  SGIC_REQUIRE_AS(name, cap >= p.cap && cap <= 0x7fffffff, "the slots are smaller than sgic_jpeg_encode_prog_cap says");
+  for (size_t i = 0; i < (size_t)B * 128; ++i) SGIC_REQUIRE_AS(name, h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
+  hipStream_t st = to_stream(stream);
+  int16_t *coef = reinterpret_cast<int16_t *>(d_work);
+  uint16_t *qt = reinterpret_cast<uint16_t *>(d_work + p.off_qt);
+  uint32_t *local = reinterpret_cast<uint32_t *>(d_work + p.off_local);
+  uint32_t *csum = reinterpret_cast<uint32_t *>(d_work + p.off_csum);
+  uint32_t *tabs = reinterpret_cast<uint32_t *>(d_work + p.off_tabs);
+  uint8_t *blk = d_work + pp.off_blk, *mark = d_work + pp.off_mark;
+  uint16_t *cnt = reinterpret_cast<uint16_t *>(d_work + pp.off_cnt);
+  uint32_t *re = reinterpret_cast<uint32_t *>(d_work + pp.off_re);
+  uint32_t *pre = reinterpret_cast<uint32_t *>(d_work + pp.off_pre);
+  uint32_t *next[2] = {reinterpret_cast<uint32_t *>(d_work + pp.off_next), reinterpret_cast<uint32_t *>(d_work + pp.off_next) + (size_t)B * p.nblk};
+  int32_t *clast = reinterpret_cast<int32_t *>(d_work + pp.off_clast), *cfirst = reinterpret_cast<int32_t *>(d_work + pp.off_cfirst);
+  uint32_t *ctb = reinterpret_cast<uint32_t *>(d_work + pp.off_ctb);
+  unsigned long long *pos = reinterpret_cast<unsigned long long *>(d_work + pp.off_pos);
+  uint32_t *ffsum = reinterpret_cast<uint32_t *>(d_work + p.off_ffsum);
+  uint32_t *tot = reinterpret_cast<uint32_t *>(d_work + p.off_tot);
+  uint32_t *hist = reinterpret_cast<uint32_t *>(d_work + p.off_hist);
+  uint8_t *huff4 = d_work + pp.off_huff4;
+  int32_t *nval4 = reinterpret_cast<int32_t *>(d_work + pp.off_nval4);
+  const PWork w{coef, hist, tabs, huff4, nval4, mark, cnt, local, csum, tot};
+  SGIC_HIP(hipMemcpyAsync(qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+  SGIC_HIP(hipMemsetAsync(d_work + pp.off_pos, 0, p.off_ffsum - pp.off_pos, st));
+  const unsigned gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+  jpeg_enc_coef_kernel<<<dim3(p.nchunk, gy), NT, 0, st>>>(d_rgb, qt, coef, p);
+  for (int k = 0; k < NSCAN; ++k) {
+    const PScan &sc = pp.scan[k];
+    const dim3 grid(sc.nchunk, gy), gbytes(sc.nbchunk < MAX_CHUNK_GRID ? sc.nbchunk : MAX_CHUNK_GRID, gy);
+    if (k && sc.kind != K_DC_REFINE) SGIC_HIP(hipMemsetAsync(hist, 0, (size_t)B * TAB_WORDS * sizeof(uint32_t), st));
+    uint32_t *bits = reinterpret_cast<uint32_t *>(d_work + sc.off_bits);
+    if (sc.kind == K_AC_FIRST) {
+      jpeg_enc_prog_flags_kernel<false><<<grid, NT, 0, st>>>(coef, blk, clast, cfirst, ctb, p, sc);
+      jpeg_enc_prog_link_kernel<<<gy, NT, 0, st>>>(clast, cfirst, ctb, p.nchunk, sc.nchunk, sc.n, B);
+      jpeg_enc_prog_runs_kernel<false><<<grid, NT, 0, st>>>(blk, clast, cfirst, ctb, mark, cnt, re, pre, p, sc);
+    } else if (sc.kind == K_AC_REFINE) {
+      jpeg_enc_prog_flags_kernel<true><<<grid, NT, 0, st>>>(coef, blk, clast, cfirst, ctb, p, sc);
+      jpeg_enc_prog_link_kernel<<<gy, NT, 0, st>>>(clast, cfirst, ctb, p.nchunk, sc.nchunk, sc.n, B);
+      jpeg_enc_prog_runs_kernel<true><<<grid, NT, 0, st>>>(blk, clast, cfirst, ctb, mark, cnt, re, pre, p, sc);
+      jpeg_enc_prog_next_kernel<<<grid, NT, 0, st>>>(re, pre, cnt, next[0], p, sc);
+      for (int r = 0; r < sc.rounds; ++r) jpeg_enc_prog_round_kernel<<<grid, NT, 0, st>>>(next[r & 1], next[~r & 1], mark, p, sc);
+    }
+    switch (sc.kind) {
+      case K_DC_FIRST: launch_prog_chain<K_DC_FIRST>(p, sc, grid, gy, w, bits, st); break;
+      case K_DC_REFINE: launch_prog_chain<K_DC_REFINE>(p, sc, grid, gy, w, bits, st); break;
+      case K_AC_FIRST: launch_prog_chain<K_AC_FIRST>(p, sc, grid, gy, w, bits, st); break;
+      default: launch_prog_chain<K_AC_REFINE>(p, sc, grid, gy, w, bits, st); break;
+    }
+    // count, scan and emit take the scan's stream through a plan that carries its word count; the stuffing counts keep p.nbchunk as stride
+    EPlan ps = p;
+    ps.words = sc.words;
+    jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, ps);
+    jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(ffsum, p.nbchunk, 0, tot, 1, 1, B);
+    jpeg_enc_prog_emit_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, d_out, cap, d_len, d_err, huff4, nval4, d_huff, d_nval, pos, k, p, sc);
+  }
+  return sgic::check_launch(name);
 }
 
 #define JPEG_ENC_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2581110 coded blocks per image"
@@ -843,4 +1508,28 @@ extern "C" int sgic_jpeg_encode_opt_batch(const uint8_t *d_rgb, int B, int H, in
   SGIC_REQUIRE(d_huff && d_nval, "null pointer");
   SGIC_REQUIRE(((uintptr_t)d_huff & 3) == 0 && ((uintptr_t)d_nval & 3) == 0, "misaligned pointer");
   return encode_batch(__func__, true, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
+}
+
+extern "C" int sgic_jpeg_encode_prog_cap(int H, int W, int subsampling, size_t *cap) {
+  SGIC_REQUIRE(cap != nullptr, "null output");
+  PPlan p;
+  SGIC_REQUIRE(make_prog_plan(1, H, W, subsampling, &p), JPEG_ENC_PROG_LIMITS);
+  *cap = p.e.cap;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_jpeg_encode_prog_work_bytes(int B, int H, int W, int subsampling, size_t *bytes) {
+  SGIC_REQUIRE(bytes != nullptr, "null output");
+  PPlan p;
+  SGIC_REQUIRE(make_prog_plan(B, H, W, subsampling, &p), JPEG_ENC_PROG_LIMITS);
+  *bytes = p.e.bytes;
+  return SGIC_OK;
+}
+
+extern "C" int sgic_jpeg_encode_prog_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt,
+                                           uint8_t *d_work, size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err,
+                                           uint8_t *d_huff, int32_t *d_nval, sgic_stream_t stream) {
+  PPlan p;
+  SGIC_REQUIRE(make_prog_plan(B, H, W, subsampling, &p), JPEG_ENC_PROG_LIMITS);
+  return encode_prog_batch(__func__, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
 }

@@ -2,7 +2,8 @@
 """Counterpart of the reference driver src/decompress.py (same flags; writes save_dir/results/<stem>.png),
 running the MI355X decode path.  Files with identical shapes are decoded as one batch.  --format jpg writes baseline JPEG files
 encoded on the GPU instead (jpeg_enc: the bytes Pillow's save(quality, subsampling) would write for the same pixels; with --optimize
-those of save(quality, subsampling, optimize=True): Huffman tables fitted to every image).  --max_side N reduces results whose longer
+those of save(quality, subsampling, optimize=True): Huffman tables fitted to every image; with --progressive those of
+save(quality, subsampling, progressive=True): ten scans, tables fitted to every scan).  --max_side N reduces results whose longer
 side exceeds N on the device before they are written (ops.resize_u8, Lanczos: the pixels of Pillow's Image.resize)."""
 import argparse
 import os
@@ -43,6 +44,8 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=90, help="JPEG quality, 1..100 (--format jpg)")
     ap.add_argument("--subsampling", type=int, choices=(0, 1, 2), default=2, help="JPEG chroma layout: 0 4:4:4, 1 4:2:2, 2 4:2:0")
     ap.add_argument("--optimize", action="store_true", help="JPEG with Huffman tables fitted to every image, as Pillow's optimize=True (--format jpg)")
+    ap.add_argument("--progressive", action="store_true",
+                    help="progressive JPEG, as Pillow's progressive=True: ten scans, tables fitted to every scan (--format jpg; --optimize changes nothing then)")
     ap.add_argument("--max_side", type=int, default=None, metavar="N",
                     help="reduce results whose longer side exceeds N (1..16384) to that side, Lanczos, before they are written")
     args = ap.parse_args(argv)
@@ -52,6 +55,8 @@ def main(argv=None):
         ap.error("--quality must be in 1..100")
     if args.optimize and args.format != "jpg":
         ap.error("--optimize fits the Huffman tables of a JPEG file: give --format jpg")
+    if args.progressive and args.format != "jpg":
+        ap.error("--progressive orders the scans of a JPEG file: give --format jpg")
 
     from . import weights as W
     from .codec import Codec
@@ -110,7 +115,8 @@ def main(argv=None):
                         for (path, _), arr in zip(members, images.cpu().numpy()):
                             pending.append(pool.submit(lambda arr, p: Image.fromarray(arr).save(p), arr, path))
                         continue
-                    files = jpeg_enc.encode_batch(images, args.quality, args.subsampling, optimize=args.optimize)   # only the coded bytes cross the bus
+                    files = jpeg_enc.encode_batch(images, args.quality, args.subsampling, optimize=args.optimize,
+                                                  progressive=args.progressive)   # only the coded bytes cross the bus
                     for (path, _), data in zip(members, files):
                         pending.append(pool.submit(_write_bytes, path, data))
         for f in pending:

@@ -1,7 +1,9 @@
 """Baseline JPEG files from RGB u8 images on the device, byte for byte what `PIL.Image.save(format="JPEG", quality=q, subsampling=s)`
 writes (Pillow on libjpeg-turbo).  The host builds the quantisation tables of a quality and the header, which
 depends only on (H, W, tables, subsampling); colour conversion, downsampling, DCT, quantisation, Huffman coding and byte stuffing
-run on the GPU (ops.jpeg_encode, csrc/jpeg_enc.hip), and only the coded bytes cross the bus."""
+run on the GPU (ops.jpeg_encode, csrc/jpeg_enc.hip), and only the coded bytes cross the bus.  optimize=True gives the files of
+save(optimize=True), progressive=True those of save(progressive=True): there the host also places the DHT and SOS segments
+between the ten scans (progressive_file)."""
 import numpy as np
 
 ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49,
@@ -53,8 +55,8 @@ def header(H, W, tables, subsampling, huffman=None):
 _SOS = _segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
 
 
-def _header_front(H, W, tables, subsampling):
-    """SOI .. SOF0: what an image's Huffman tables do not touch"""
+def _header_front(H, W, tables, subsampling, sof=0xC0):
+    """SOI .. SOF0 (sof: another frame marker): what an image's Huffman tables do not touch"""
     H, W = int(H), int(W)
     if not (1 <= H <= 65535 and 1 <= W <= 65535):
         raise ValueError(f"a JPEG frame is 1..65535 on a side, got {H}x{W}")
@@ -64,7 +66,7 @@ def _header_front(H, W, tables, subsampling):
     out = [b"\xff\xd8", _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
     for i in range(2):
         out.append(_segment(0xDB, bytes((i,)) + bytes(int(tables[i][z]) for z in ZIGZAG)))
-    out.append(_segment(0xC0, bytes((8,)) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes((3, 1, h << 4 | v, 0, 2, 0x11, 1, 3, 0x11, 1))))
+    out.append(_segment(sof, bytes((8,)) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes((3, 1, h << 4 | v, 0, 2, 0x11, 1, 3, 0x11, 1))))
     return b"".join(out)
 
 
@@ -79,6 +81,34 @@ def _header_back(huffman=None):
     return b"".join(out)
 
 
+# libjpeg's jpeg_simple_progression for Y Cb Cr: (components, Ss, Se, Ah, Al) of the ten scans Pillow's progressive=True writes
+PROGRESSION = (((0, 1, 2), 0, 0, 0, 1), ((0,), 1, 5, 0, 2), ((2,), 1, 63, 0, 1), ((1,), 1, 63, 0, 1), ((0,), 6, 63, 0, 2),
+               ((0,), 1, 63, 2, 1), ((0, 1, 2), 0, 0, 1, 0), ((2,), 1, 63, 1, 0), ((1,), 1, 63, 1, 0), ((0,), 1, 63, 1, 0))
+
+
+def progressive_file(H, W, tables, subsampling, huffman, segments):
+    """a whole progressive file: SOI, APP0, two DQT, SOF2, then per scan its DHT segments (one per table), SOS and entropy-coded
+    segment, then EOI.  huffman: the ten (BITS, HUFFVAL) pairs in file order: DC 0 and DC 1 of the first scan, then one AC table for
+    every AC scan (id 0 for luma, 1 for chroma); the DC refinement scan has none.  segments: the ten entropy-coded segments."""
+    if len(huffman) != 10 or len(segments) != 10 or any(len(b) != 16 or sum(b) != len(v) or len(v) > 256 for b, v in huffman):
+        raise ValueError("a progressive file takes ten (BITS of 16 counts, HUFFVAL of their sum) pairs and ten segments")
+    out = [_header_front(H, W, tables, subsampling, sof=0xC2)]
+    tabs = iter(huffman)
+    for (comps, ss, se, ah, al), seg in zip(PROGRESSION, segments):
+        if ss == 0:      # a DC scan: the selector names Td; the refinement scan sends raw bits and needs no table
+            if ah == 0:
+                out += [_segment(0xC4, bytes((th,)) + bytes(b) + bytes(v)) for th, (b, v) in zip((0x00, 0x01), (next(tabs), next(tabs)))]
+            sel = bytes(x for c in comps for x in (c + 1, 0 if ah or c == 0 else 0x10))
+        else:            # an AC scan: one table, the selector names Ta
+            th = 0 if comps[0] == 0 else 1
+            b, v = next(tabs)
+            out.append(_segment(0xC4, bytes((0x10 | th,)) + bytes(b) + bytes(v)))
+            sel = bytes((comps[0] + 1, th))
+        out += [_segment(0xDA, bytes((len(comps),)) + sel + bytes((ss, se, ah << 4 | al))), bytes(seg)]
+    out.append(b"\xff\xd9")
+    return b"".join(out)
+
+
 def pick_quality(sizes_by_quality, budget):
     """the anchor rule: sizes_by_quality {quality: file size in bytes} -> (quality, over_rate): the largest quality whose file is not
     larger than budget; (the smallest quality, True) if no file fits.  Every entry is looked at: sizes need not grow with quality."""
@@ -89,7 +119,8 @@ def pick_quality(sizes_by_quality, budget):
 
 
 def _raise_for(err):
-    """the encoder's error words, not all zero: 1 a slot was too small, 2 (optimised tables) a code past 32 bits before limiting"""
+    """the encoder's error words, not all zero: 1 a slot was too small, 2 (fitted tables: optimize, progressive) a code past 32 bits
+    before limiting"""
     if (np.asarray(err) == 2).any():
         raise RuntimeError("JPEG encoder: a Huffman code longer than 32 bits before the length limiter; libjpeg refuses such an image too")
     raise RuntimeError(f"JPEG encoder: slot overflow, error words {np.asarray(err).ravel().tolist()}")
@@ -113,9 +144,33 @@ def encode_scans(rgb_u8, tables, subsampling, optimize=False):
     return scans, [pairs[4 * b:4 * b + 4] for b in range(len(scans))]
 
 
-def encode_batch(rgb_u8, quality, subsampling=2, optimize=False):
+def encode_progressive(rgb_u8, tables, subsampling):
+    """(B, H, W, 3) u8 on the device, tables (B, 2, 64) -> list of B whole progressive files.  The lengths, error words and table
+    counts come back in one read, the tables in one, the coded bytes in one (the longest image's, not the slots)."""
+    import torch
+
+    from . import ops
+    buf, lens, err, huff, nval = ops.jpeg_encode(rgb_u8, tables, subsampling, progressive=True)
+    B, H, W, _ = rgb_u8.shape
+    meta = torch.cat([lens, nval, err[:, None]], dim=1).cpu().numpy()
+    lens_h, nval_h, err_h = meta[:, :10], meta[:, 10:20], meta[:, 20]
+    if err_h.any():
+        _raise_for(err_h)
+    host = buf[:, :int(lens_h.sum(axis=1).max())].cpu().numpy()
+    raw = huff.cpu().numpy()
+    files = []
+    for b in range(B):
+        ends = np.cumsum(lens_h[b])
+        segments = [host[b, e - n:e].tobytes() for e, n in zip(ends, lens_h[b])]
+        pairs = [(raw[b, j, :16].tobytes(), raw[b, j, 16:16 + int(n)].tobytes()) for j, n in enumerate(nval_h[b])]
+        files.append(progressive_file(H, W, tables[b], subsampling, pairs, segments))
+    return files
+
+
+def encode_batch(rgb_u8, quality, subsampling=2, optimize=False, progressive=False):
     """(B, H, W, 3) u8 RGB on the device -> list of B whole JPEG files (bytes).  quality: an int, or one int per image.  optimize:
-    the files of Pillow's save(optimize=True), every image with Huffman tables fitted to it."""
+    the files of Pillow's save(optimize=True), every image with Huffman tables fitted to it.  progressive: the files of Pillow's
+    save(progressive=True), ten scans with tables fitted to every scan; optimize changes nothing then, as in Pillow."""
     assert rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3, "images are (B, H, W, 3)"
     B, H, W, _ = rgb_u8.shape
     qs = [int(quality)] * B if np.ndim(quality) == 0 else [int(q) for q in quality]
@@ -125,6 +180,8 @@ def encode_batch(rgb_u8, quality, subsampling=2, optimize=False):
         raise ValueError(f"subsampling must be 0, 1 or 2, got {subsampling}")
     by_q = {q: quant_tables(q) for q in set(qs)}
     tables = np.stack([by_q[q] for q in qs])
+    if progressive:
+        return encode_progressive(rgb_u8.contiguous(), tables, int(subsampling))
     if optimize:
         scans, huffman = encode_scans(rgb_u8.contiguous(), tables, int(subsampling), True)
         fronts = {q: _header_front(H, W, t, subsampling) for q, t in by_q.items()}

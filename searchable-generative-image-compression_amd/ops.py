@@ -1578,36 +1578,39 @@ def gram_f64(a, b=None, ia=None, ib=None, out=None):
     return out
 
 
-def jpeg_encode(rgb_u8, tables, subsampling, optimize=False):
+def jpeg_encode(rgb_u8, tables, subsampling, optimize=False, progressive=False):
     """baseline JPEG encode of B equal-size images (csrc/jpeg_enc.hip): rgb_u8 (B, H, W, 3) u8, contiguous on the device; tables
     (B, 2, 64) u16 numpy array on the host (luma and chroma quantisation table of every image, natural order); subsampling 0 / 1 / 2
     as Pillow's -> (buf (B, cap) u8: image b's entropy-coded segment and FF D9 in buf[b, :lens[b]], lens (B,) int32, err (B,) int32,
     nonzero where a slot was too small).  The header is jpeg_enc.header's.  optimize: Huffman tables fitted to every image (Pillow's
     optimize=True); the result is then (buf, lens, err, huff (B, 4, 272) u8: BITS and HUFFVAL of the image's tables DC0, AC0, DC1,
-    AC1, nval (B, 4) int32: their HUFFVAL counts), which the header needs.  No synchronisation."""
+    AC1, nval (B, 4) int32: their HUFFVAL counts), which the header needs.  progressive: the ten scans of Pillow's progressive=True
+    (optimize is then implied): buf[b] holds the ten entropy-coded segments back to back without EOI, lens is (B, 10), huff
+    (B, 10, 272) and nval (B, 10) are the ten tables in file order (sgic_jpeg_encode_prog_batch).  No synchronisation."""
     require_gpu()
     assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.is_contiguous()
     assert rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
     B, H, W, _ = rgb_u8.shape
     tables = np.ascontiguousarray(tables, dtype=np.uint16)
     assert tables.shape == (B, 2, 64), f"tables must be ({B}, 2, 64), got {tables.shape}"
-    stem = "sgic_jpeg_encode_opt" if optimize else "sgic_jpeg_encode"
+    stem = "sgic_jpeg_encode_prog" if progressive else "sgic_jpeg_encode_opt" if optimize else "sgic_jpeg_encode"
     cap, nbytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
     call(stem + "_cap", H, W, int(subsampling), ctypes.byref(cap))
     call(stem + "_work_bytes", B, H, W, int(subsampling), ctypes.byref(nbytes))
     dev = rgb_u8.device
     work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     buf = torch.empty(B, cap.value, dtype=torch.uint8, device=dev)
-    lens = torch.empty(B, dtype=torch.int32, device=dev)
+    lens = torch.empty((B, 10) if progressive else (B,), dtype=torch.int32, device=dev)
     err = torch.empty(B, dtype=torch.int32, device=dev)
     args = (_p(rgb_u8), B, H, W, int(subsampling), ctypes.c_void_p(tables.ctypes.data), _p(work), ctypes.c_size_t(nbytes.value), _p(buf),
             ctypes.c_size_t(cap.value), _p(lens), _p(err))
-    if not optimize:
+    if not (optimize or progressive):
         call("sgic_jpeg_encode_batch", *args)
         return buf, lens, err
-    huff = torch.empty(B, 4, 272, dtype=torch.uint8, device=dev)
-    nval = torch.empty(B, 4, dtype=torch.int32, device=dev)
-    call("sgic_jpeg_encode_opt_batch", *args, _p(huff), _p(nval))
+    ntab = 10 if progressive else 4
+    huff = torch.empty(B, ntab, 272, dtype=torch.uint8, device=dev)
+    nval = torch.empty(B, ntab, dtype=torch.int32, device=dev)
+    call(stem + "_batch", *args, _p(huff), _p(nval))
     return buf, lens, err, huff, nval
 
 
