@@ -60,7 +60,9 @@ int sgic_rans_encode_batch(const sgic_cdf_table *t, const int16_t *d_sym, const 
 
 /* RansDecoder.set_stream for B images (py_rans.cpp:150-185, rans.cpp:280-285).  Streams are
  * (B, cap) with d_off/d_len as produced above (or d_off = 0 for front-aligned uploads).
- * d_state: (B, 4) uint32 cursor {x, pos, err, _}. */
+ * d_state: (B, 4) uint32 cursor {x, pos, err, _}.  err: 0, 1 = the stream ended too soon, 2 = not a header this
+ * coder writes (a multi-stream flag byte, or a state below the coder's lower bound 2^23, from which decoding need
+ * not end), 3 = an index past the table's rows (set by decode).  Once set it stays, and decode writes zeros. */
 int sgic_rans_decode_init_batch(const uint8_t *d_streams, int cap, const int32_t *d_off, const int32_t *d_len,
                                 int B, uint32_t *d_state, sgic_stream_t stream);
 /* RansDecoder.decode_stream (rans.cpp:303-362): continues from the cursor.  Image b reads its indexes at

@@ -298,6 +298,11 @@ __global__ void rans_decode_init_kernel(const uint8_t *streams, int cap, const i
   x |= c.next() << 8;
   x |= c.next() << 16;
   x |= c.next() << 24;
+  // An encoder leaves x in [RANS_L, 2^31).  From there every renormalisation of rans_decode_kernel ends by itself: a step gives
+  // x >= 128 and two bytes, even zeros past the end, bring that back over RANS_L.  From x = 0 (a corrupt header) a step can give 0
+  // again, which shifting in zeros never changes -- that stream would be decoded for ever.  It is refused here; decode skips a
+  // cursor whose err is set.
+  if (!c.err && x < RANS_L) c.err = 2;
   state[b * 4 + 0] = x;
   state[b * 4 + 1] = (uint32_t)c.pos;
   state[b * 4 + 2] = (uint32_t)c.err;

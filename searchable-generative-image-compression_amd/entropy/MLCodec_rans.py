@@ -120,7 +120,9 @@ class RansDecoder:
     def set_stream(self, encoded):
         buf = np.ascontiguousarray(encoded, dtype=np.uint8).reshape(-1)
         dev = torch.device("cuda", torch.cuda.current_device())
-        self._buf = torch.from_numpy(buf.copy()).to(dev)
+        # an empty stream still needs a device address: one byte that is never read (len 0), so the cursor starts out failed
+        # and decode_stream raises, as for any other stream that ends too soon
+        self._buf = torch.from_numpy(buf.copy() if len(buf) else np.zeros(1, dtype=np.uint8)).to(dev)
         self._len = torch.tensor([len(buf)], dtype=torch.int32, device=dev)
         self._state = torch.zeros(4, dtype=torch.int32, device=dev)
         self._cap = max(len(buf), 1)
