@@ -1,33 +1,80 @@
-// Baseline JPEG encode of a batch of B equal-geometry RGB u8 images (sgic_jpeg_encode_batch, include/sgic.h): the entropy-coded
-// segment and EOI of the file that Pillow / libjpeg-turbo writes for the same pixels, quantisation tables and sampling layout, byte
-// for byte.  Integer arithmetic only (jccolor, jcsample without smoothing, jfdctint islow, division by 8 q with rounding, the
-// Annex K Huffman tables); DESIGN.md section 13 has the definition.  Six passes, every one parallel in 8 x 8 blocks or in bytes:
-//   coef   one thread per coded block: colour, downsampling, edge replication, DCT, quantisation -> i16 coefficients in zigzag order
-//   bits   one thread per block: its code length; a workgroup scan leaves offsets within 256 blocks and the sum of the 256
-//   scan   one workgroup per image: exclusive scan of those sums (used again for the stuffing counts)
-//   pack   one thread per block: its codes go to the zeroed bit stream; blocks share at most their first and last word, which take an
-//          integer atomicOr (order-free, so two runs give the same bytes), words in between are plain stores
-//   count  one workgroup per 4 KiB of the stream: the 0xFF bytes (the 1-bit padding of the last byte included)
-//   emit   the same split: bytes move to their slot, a 0x00 follows every 0xFF, then FF D9, the length and the error word
-// sgic_jpeg_encode_opt_batch writes the file of save(..., optimize=True) instead: the same passes, but bits and pack read the image's
-// own tables from the workspace, and two passes in front of them make those tables:
-//   hist   one thread per block: the symbols its codes would use, counted in LDS, then added to the image's four histograms
-//   tables one wavefront per (image, table): libjpeg's jpeg_gen_optimal_table -> code words, BITS and HUFFVAL
-// sgic_jpeg_encode_prog_batch writes the ten scans of save(..., progressive=True) from the same coefficients; its passes are listed
-// where it begins, below the optimised encoder's kernels.
+// JPEG encode of a batch of B equal-geometry RGB u8 images (include/sgic.h): the entropy-coded bytes of the file that Pillow /
+// libjpeg-turbo writes for the same pixels, quantisation tables and sampling layout, byte for byte.  Integer arithmetic only (jccolor,
+// jcsample without smoothing, jfdctint islow, division by 8 q with rounding); DESIGN.md section 13 has the definition.  Three calls, one
+// chain.  A call's mode says which tables code the file and which scans it has:
+//   sgic_jpeg_encode_batch       ANNEX_K      save(...): one sequential scan, the Annex K Huffman tables
+//   sgic_jpeg_encode_opt_batch   FITTED       save(..., optimize=True): one sequential scan, tables fitted to the image
+//   sgic_jpeg_encode_prog_batch  PROGRESSIVE  save(..., progressive=True): the ten scans of libjpeg's jpeg_simple_progression, every
+//                                             scan with tables fitted to it (section 13.3)
+// The coefficients are made once; then every scan of the script runs the same passes over its own blocks, every pass parallel in
+// 8 x 8 blocks or in bytes (send_block<K> says what a block sends in a scan of kind K; hist, bits and pack are its three sinks):
+//   coef    one thread per coded block: colour, downsampling, edge replication, DCT, quantisation -> i16 coefficients in zigzag order
+//   (AC scans only: flags, link, runs, next, round find the blocks that lead an end-of-band run; listed where they begin)
+//   hist    fitted tables: one thread per block: the symbols its codes would use, counted in LDS, then added to the image's histograms
+//   tables  fitted tables: one wavefront per (image, table): libjpeg's jpeg_gen_optimal_table -> code words, BITS and HUFFVAL
+//   bits    one thread per block: its code length; a workgroup scan leaves offsets within 256 blocks and the sum of the 256
+//   scan    one workgroup per image: exclusive scan of those sums (used again for the stuffing counts)
+//   pack    one thread per block: its codes go to the zeroed bit stream; blocks share at most their first and last word, which take an
+//           integer atomicOr (order-free, so two runs give the same bytes), words in between are plain stores
+//   count   one workgroup per 4 KiB of the stream: the 0xFF bytes (the 1-bit padding of the last byte included)
+//   emit    the same split: bytes move to their place in the slot behind the scans before them, a 0x00 follows every 0xFF; a
+//           sequential file then gets FF D9; every scan writes its length, the last one the error word (two kernels: the
+//           sequential file's and the progressive scan's)
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
 constexpr int NT = 256;
 constexpr int MAX_GRID_Y = 32768;
-constexpr int WORDS_PER_BLOCK = 52;        // a block codes to at most 20 + 63 * 26 = 1658 bits <= 208 bytes
-constexpr int WORDS_PER_BLOCK_OPT = 53;    // fitted tables: any code may have 16 bits, so 16 + 11 + 63 * (16 + 10) = 1665 bits
 constexpr int CHUNK_WORDS = NT * 4;        // words of the bit stream that a workgroup of count / emit takes at a time
 constexpr int MAX_CHUNK_GRID = 1024;
-constexpr unsigned MAX_BLOCKS = 2581110;   // 1664 bits each stay below 2^32: bit offsets within an image are 32-bit
-constexpr unsigned MAX_BLOCKS_OPT = 2579559;   // the same with 1665 bits each
-static_assert((unsigned long long)MAX_BLOCKS_OPT * 1665 < (1ull << 32) && 1665 <= WORDS_PER_BLOCK_OPT * 32, "32-bit bit offsets");
+constexpr int HUFF_BYTES = 272;            // BITS (16) and HUFFVAL (256, zeros after the table's symbols)
+
+// The kinds of scan.  A sequential scan codes whole blocks (coefficients 0 .. 63, no end-of-band runs) in the MCU order of coef, dummy
+// blocks included; the two DC kinds run over the same blocks; an AC scan runs over its component's raster without dummy blocks.
+constexpr int K_SEQ = 0, K_DC_FIRST = 1, K_DC_REFINE = 2, K_AC_FIRST = 3, K_AC_REFINE = 4;
+// Where bits and pack take the code words from: the Annex K tables (staged once per workgroup), the image's own (staged for every
+// image of the loop), none (a DC refinement scan sends raw bits only)
+constexpr int T_ANNEX_K = 0, T_IMAGE = 1, T_NONE = 2;
+constexpr int NSCAN = 10;                 // scans of a progressive file
+constexpr int EOBRUN_MAX = 0x7FFF;
+constexpr unsigned CORR_BITS = 937;       // libjpeg's MAX_CORR_BITS - DCTSIZE2 + 1: a run is cut once its correction bits pass this
+constexpr int EOBRUN_BITS = 16 + 14;      // the symbol and its extra bits
+// The bits of a block in a scan at the most.  Sequential, in whole words: 20 + 63 * 26 = 1658 bits with the Annex K tables; with
+// fitted tables any code may have 16 bits, so 16 + 11 + 63 * (16 + 10) = 1665.  Progressive: a DC difference of at most 11 bits; a
+// refinement bit; in a first scan (10 - Al)-bit values behind 16-bit codes; in a refinement scan a code, a sign and no correction
+// bit per coefficient at the most, three ZRL at the most
+constexpr unsigned seq_bits(bool fitted) { return fitted ? 53 * 32 : 52 * 32; }
+constexpr unsigned dc_first_bits() { return 16 + 11; }
+constexpr unsigned ac_first_bits(int ss, int se, int al) { return (unsigned)(se - ss + 1) * (16 + 10 - al) + EOBRUN_BITS; }
+constexpr unsigned ac_refine_bits(int ss, int se) { return (unsigned)(se - ss + 1) * 17 + 3 * 16 + EOBRUN_BITS; }
+constexpr unsigned MAX_SCAN_BITS = ac_first_bits(1, 63, 1);       // the largest of the ten scans: chroma, 1 .. 63 at Al = 1
+constexpr size_t MAX_SLOT_BYTES = 0x7fffffff;      // an image's slot, which d_len and cap count in 31 bits
+
+// What a call's tables and scans are.  max_blocks: bit offsets within a scan of an image are 32-bit, so the coded blocks of an image
+// times the largest per-block bound stay below 2^32.  limits, work, slots: the texts of its refusals
+struct Mode {
+  unsigned max_blocks;
+  bool fitted, progressive;
+  const char *limits, *work, *slots;
+};
+#define JPEG_ENC_GEOMETRY "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most "
+constexpr Mode ANNEX_K{2581110, false, false, JPEG_ENC_GEOMETRY "2581110 coded blocks per image",
+                       "the workspace is smaller than sgic_jpeg_encode_work_bytes says", "the slots are smaller than sgic_jpeg_encode_cap says"};
+constexpr Mode FITTED{2579559, true, false, JPEG_ENC_GEOMETRY "2579559 coded blocks per image",
+                      "the workspace is smaller than sgic_jpeg_encode_opt_work_bytes says",
+                      "the slots are smaller than sgic_jpeg_encode_opt_cap says"};
+constexpr Mode PROGRESSIVE{2675992, true, true, JPEG_ENC_GEOMETRY "2675992 coded blocks per image and a slot below 2^31 bytes",
+                           "the workspace is smaller than sgic_jpeg_encode_prog_work_bytes says",
+                           "the slots are smaller than sgic_jpeg_encode_prog_cap says"};
+static_assert((unsigned long long)ANNEX_K.max_blocks * seq_bits(false) < (1ull << 32) && (unsigned long long)FITTED.max_blocks * 1665 < (1ull << 32) &&
+              1665 <= seq_bits(true), "32-bit bit offsets within a sequential image");
+static_assert(MAX_SCAN_BITS == 1605 && ac_first_bits(6, 63, 2) < MAX_SCAN_BITS && ac_refine_bits(1, 63) == 1149, "per-block bounds");
+static_assert((unsigned long long)PROGRESSIVE.max_blocks * MAX_SCAN_BITS < (1ull << 32) &&
+              (unsigned long long)(PROGRESSIVE.max_blocks + 1) * MAX_SCAN_BITS >= (1ull << 32), "32-bit bit offsets within a scan of an image");
+static_assert((CORR_BITS + 1 + 62) / 63 == 15, "a segment that the correction bits cut holds at least 15 blocks");
 
 constexpr int ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -91,46 +138,137 @@ struct EPlan {
   int wb, hb;        // luma blocks that are not dummy blocks: ceil(W / 8) x ceil(H / 8)
   int ny, bpm;       // luma blocks and all blocks of an MCU
   int nblk;          // coded blocks of an image, dummy blocks included
-  int nchunk;        // workgroups of bits / pack per image
-  int nbchunk;       // CHUNK_WORDS pieces of an image's worst-case bit stream
-  size_t words;      // u32 words of one image's bit stream (a multiple of 4, one spare word for the last flush)
-  size_t off_qt, off_local, off_csum, off_bits, off_ffsum, off_tot;   // bytes from d_work; the coefficients lie at 0
-  size_t off_hist, off_tabs;   // optimised tables only: TAB_WORDS counters (directly in front of the bit stream) and code words per image
+  int nchunk;        // workgroups of NT blocks per image
+  int nbchunk;       // CHUNK_WORDS pieces of an image's worst-case bit stream in its largest scan
+};
+
+struct Scan {
+  int kind;
+  int comp;          // AC scans: the component
+  int ss, se, al;
+  int tab;           // AC scans: the table's place in the table layout
+  int slot;          // progressive: the scan's first table in d_huff / d_nval
+  int ntab, tw[2];   // progressive: its tables and the wavefronts of jpeg_enc_tables_kernel that build them (0 DC 0, 1 AC 0, 2 DC 1, 3 AC 1)
+  int n;             // blocks of the scan per image
+  int nchunk;        // workgroups of NT blocks
+  int rounds;
+  unsigned bound;    // bits of a block at the most
+  int nbchunk;
+  size_t words;      // u32 words of one image's bit stream in this scan (a multiple of 4, one spare word for the last flush)
+};
+
+// The workspace as typed arrays, in their order in d_work; the arrays of other modes are empty.  Everything from zero to ffsum is
+// zeroed by one memset: the byte positions of the scans in the slots (progressive), the histograms (fitted tables; zeroed again
+// for every later scan), the bit streams of all scans
+struct Work {
+  int16_t *coef;
+  uint16_t *qt;
+  uint32_t *local, *csum, *tabs;
+  uint8_t *blk, *mark;
+  uint16_t *cnt;
+  uint32_t *re, *pre, *next;      // next: two arrays of B x nblk
+  int32_t *clast, *cfirst;
+  uint32_t *ctb;
+  uint8_t *huff4;                 // what jpeg_enc_tables_kernel writes for the progressive scan at hand
+  int32_t *nval4;
+  uint8_t *zero;
+  unsigned long long *pos;
+  uint32_t *hist, *bits[NSCAN], *ffsum, *tot;
+};
+
+struct Plan {
+  EPlan e;
+  int nscan;
+  Scan scan[NSCAN];
+  Work w;
   size_t bytes, cap;
 };
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// max_blocks: the caller's own block limit; 0: that of the baseline or the optimised call
-bool make_plan(int B, int H, int W, int sub, bool opt, EPlan *p, unsigned max_blocks = 0) {
+// The plan of a call in mode m: the geometry, the script of scans (one sequential scan, or the ten of libjpeg's
+// jpeg_simple_progression) and the workspace carved from d_work (null where only the sizes are asked for).  false: outside the
+// mode's limits
+bool make_plan(const Mode &m, int B, int H, int W, int sub, uint8_t *d_work, Plan *pl) {
   if (B < 1 || H < 1 || W < 1 || H > 16384 || W > 16384 || sub < 0 || sub > 2) return false;
-  p->B = B; p->H = H; p->W = W;
-  p->hs = sub == 0 ? 1 : 2;
-  p->vs = sub == 2 ? 2 : 1;
-  p->mx = (W + 8 * p->hs - 1) / (8 * p->hs);
-  p->my = (H + 8 * p->vs - 1) / (8 * p->vs);
-  p->wb = (W + 7) / 8;
-  p->hb = (H + 7) / 8;
-  p->ny = p->hs * p->vs;
-  p->bpm = p->ny + 2;
-  const size_t nblk = (size_t)p->mx * p->my * p->bpm;
-  if (nblk > (max_blocks ? max_blocks : opt ? MAX_BLOCKS_OPT : MAX_BLOCKS)) return false;
-  p->nblk = (int)nblk;
-  p->nchunk = (int)((nblk + NT - 1) / NT);
-  const size_t wpb = opt ? WORDS_PER_BLOCK_OPT : WORDS_PER_BLOCK;
-  p->words = (nblk * wpb + 1 + 3) & ~(size_t)3;
-  p->nbchunk = (int)((p->words + CHUNK_WORDS - 1) / CHUNK_WORDS);
-  size_t o = align16((size_t)B * nblk * 64 * sizeof(int16_t));
-  p->off_qt = o;     o += align16((size_t)B * 128 * sizeof(uint16_t));
-  p->off_local = o;  o += align16((size_t)B * nblk * sizeof(uint32_t));
-  p->off_csum = o;   o += align16((size_t)B * p->nchunk * sizeof(uint32_t));
-  p->off_tabs = o;   o += opt ? (size_t)B * TAB_WORDS * sizeof(uint32_t) : 0;
-  p->off_hist = o;   o += opt ? (size_t)B * TAB_WORDS * sizeof(uint32_t) : 0;
-  p->off_bits = o;   o += (size_t)B * p->words * sizeof(uint32_t);
-  p->off_ffsum = o;  o += align16((size_t)B * p->nbchunk * sizeof(uint32_t));
-  p->off_tot = o;    o += align16((size_t)B * 2 * sizeof(uint32_t));
-  p->bytes = o;
-  p->cap = nblk * (2 * wpb * 4) + 2;
+  EPlan &p = pl->e;
+  p.B = B; p.H = H; p.W = W;
+  p.hs = sub == 0 ? 1 : 2;
+  p.vs = sub == 2 ? 2 : 1;
+  p.mx = (W + 8 * p.hs - 1) / (8 * p.hs);
+  p.my = (H + 8 * p.vs - 1) / (8 * p.vs);
+  p.wb = (W + 7) / 8;
+  p.hb = (H + 7) / 8;
+  p.ny = p.hs * p.vs;
+  p.bpm = p.ny + 2;
+  const size_t nblk = (size_t)p.mx * p.my * p.bpm;
+  if (nblk > m.max_blocks) return false;
+  p.nblk = (int)nblk;
+  p.nchunk = (int)((nblk + NT - 1) / NT);
+  pl->nscan = m.progressive ? NSCAN : 1;
+  // (kind, component, Ss, Se, Al, first table)
+  const int sequential[6] = {K_SEQ, 0, 0, 63, 0, 0};
+  const int progression[NSCAN][6] = {{K_DC_FIRST, 0, 0, 0, 1, 0},  {K_AC_FIRST, 0, 1, 5, 2, 2},   {K_AC_FIRST, 2, 1, 63, 1, 3},
+                                     {K_AC_FIRST, 1, 1, 63, 1, 4}, {K_AC_FIRST, 0, 6, 63, 2, 5},  {K_AC_REFINE, 0, 1, 63, 1, 6},
+                                     {K_DC_REFINE, 0, 0, 0, 0, 0}, {K_AC_REFINE, 2, 1, 63, 0, 7}, {K_AC_REFINE, 1, 1, 63, 0, 8},
+                                     {K_AC_REFINE, 0, 1, 63, 0, 9}};
+  pl->cap = 0;
+  p.nbchunk = 0;
+  for (int s = 0; s < pl->nscan; ++s) {
+    const int *script = m.progressive ? progression[s] : sequential;
+    Scan &sc = pl->scan[s];
+    sc.kind = script[0]; sc.comp = script[1]; sc.ss = script[2]; sc.se = script[3]; sc.al = script[4]; sc.slot = script[5];
+    sc.tab = TAB_AC + (sc.comp ? 256 : 0);
+    // a sequential scan's four tables are written where the caller reads them; a progressive scan's move to their slots
+    sc.ntab = sc.kind == K_DC_FIRST ? 2 : sc.kind >= K_AC_FIRST ? 1 : 0;
+    sc.tw[0] = sc.kind == K_DC_FIRST ? 0 : sc.comp ? 3 : 1;
+    sc.tw[1] = 2;
+    sc.n = sc.kind < K_AC_FIRST ? p.nblk : sc.comp ? p.mx * p.my : p.wb * p.hb;
+    sc.nchunk = (sc.n + NT - 1) / NT;
+    sc.rounds = 0;
+    if (sc.kind == K_AC_REFINE) {
+      int k = 0;
+      while (((size_t)15 << k) < (size_t)sc.n) ++k;
+      sc.rounds = k + 1;
+    }
+    sc.bound = sc.kind == K_SEQ ? seq_bits(m.fitted) : sc.kind == K_DC_FIRST ? dc_first_bits() : sc.kind == K_DC_REFINE ? 1
+               : sc.kind == K_AC_FIRST ? ac_first_bits(sc.ss, sc.se, sc.al) : ac_refine_bits(sc.ss, sc.se);
+    sc.words = (((size_t)sc.n * sc.bound + 31) / 32 + 1 + 3) & ~(size_t)3;
+    sc.nbchunk = (int)((sc.words + CHUNK_WORDS - 1) / CHUNK_WORDS);
+    if (sc.nbchunk > p.nbchunk) p.nbchunk = sc.nbchunk;
+    // every byte of a stream may be 0xFF and take a stuffed zero; a sequential file ends with FF D9
+    pl->cap += sc.kind == K_SEQ ? (size_t)sc.n * (sc.bound / 4) + 2 : sc.words * 8;
+  }
+  if (pl->cap > MAX_SLOT_BYTES) return false;      // lengths and the caller's cap are 31-bit
+  // every array starts on a multiple of 16 bytes; n: its elements per image
+  size_t o = 0;
+  auto take = [&o, d_work, B](auto *&array, size_t n) {
+    array = reinterpret_cast<std::remove_reference_t<decltype(array)>>((uintptr_t)d_work + o);
+    o += ((size_t)B * n * sizeof(*array) + 15) & ~(size_t)15;
+  };
+  const size_t fitted = m.fitted ? 1 : 0, runs = m.progressive ? 1 : 0;
+  Work &w = pl->w;
+  take(w.coef, nblk * 64);
+  take(w.qt, 128);
+  take(w.local, nblk);
+  take(w.csum, p.nchunk);
+  take(w.tabs, fitted * TAB_WORDS);
+  take(w.blk, runs * nblk);
+  take(w.mark, runs * nblk);
+  take(w.cnt, runs * nblk);
+  take(w.re, runs * nblk);
+  take(w.pre, runs * (nblk + 1));
+  take(w.next, runs * 2 * nblk);
+  take(w.clast, runs * p.nchunk);
+  take(w.cfirst, runs * p.nchunk);
+  take(w.ctb, runs * p.nchunk);
+  take(w.huff4, runs * 4 * HUFF_BYTES);
+  take(w.nval4, runs * 4);
+  w.zero = reinterpret_cast<uint8_t *>((uintptr_t)d_work + o);
+  take(w.pos, runs * (NSCAN + 1));
+  take(w.hist, fitted * TAB_WORDS);
+  for (int s = 0; s < pl->nscan; ++s) take(w.bits[s], pl->scan[s].words);
+  take(w.ffsum, p.nbchunk);
+  take(w.tot, 2);
+  pl->bytes = o;
   return true;
 }
 
@@ -326,11 +464,30 @@ struct PackSink {
   }
 };
 
-// the symbols of one block: c holds its 64 coefficients in zigzag order (8 x uint4 of i16 pairs)
+// for the walks of the AC run passes, which only look at what a block would send
+struct NullSink {
+  __device__ __forceinline__ void sym(int, unsigned, int) {}
+  __device__ __forceinline__ void raw(unsigned long long, int) {}
+};
+
+// a block's 64 coefficients in zigzag order: 8 x uint4 of i16 pairs
+__device__ __forceinline__ void load_block(uint4 (&c)[8], const int16_t *__restrict__ ci, int t) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) c[j] = src[j];
+}
+
+// coefficient k (a constant under unrolling) of a block in c
+__device__ __forceinline__ int coef_of(const uint4 (&c)[8], int k) {
+  const unsigned w = (k & 7) < 2 ? c[k >> 3].x : (k & 7) < 4 ? c[k >> 3].y : (k & 7) < 6 ? c[k >> 3].z : c[k >> 3].w;
+  return (int)(short)((k & 1) ? (w >> 16) : (w & 0xffff));
+}
+
+// the symbols of one block of a sequential scan
 template <typename Sink>
 __device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int pred, int chroma) {
   const int dc = TAB_DC + 12 * chroma, ac = TAB_AC + 256 * chroma;
-  const int diff = (int)(short)(c[0].x & 0xffff) - pred;
+  const int diff = coef_of(c, 0) - pred;
   {
     const int nb = min(32 - __clz(abs(diff)), 11);
     sink.sym(dc + nb, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1), nb);
@@ -338,8 +495,7 @@ __device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int 
   int run = 0;
 #pragma unroll
   for (int k = 1; k < 64; ++k) {
-    const unsigned w = (k & 7) < 2 ? c[k >> 3].x : (k & 7) < 4 ? c[k >> 3].y : (k & 7) < 6 ? c[k >> 3].z : c[k >> 3].w;
-    const int v = (int)(short)((k & 1) ? (w >> 16) : (w & 0xffff));
+    const int v = coef_of(c, k);
     if (v == 0) {
       ++run;
     } else {
@@ -352,10 +508,10 @@ __device__ __forceinline__ void code_block(Sink &sink, const uint4 (&c)[8], int 
   if (run) sink.sym(ac, 0, 0);
 }
 
-// the tables go to LDS: the Annex K ones, or (OPT) those that the tables pass has written for an image
-template <bool OPT>
+// the tables go to LDS: the Annex K ones, or (T_IMAGE) those that the tables pass has written for an image
+template <int T>
 __device__ __forceinline__ void stage_tabs(uint32_t *tab, const uint32_t *__restrict__ src) {
-  for (int i = threadIdx.x; i < TAB_WORDS; i += NT) tab[i] = OPT ? src[i] : kTabs.w[i];
+  for (int i = threadIdx.x; i < TAB_WORDS; i += NT) tab[i] = T == T_IMAGE ? src[i] : kTabs.w[i];
   __syncthreads();
 }
 
@@ -380,51 +536,6 @@ __device__ __forceinline__ unsigned wg_exclusive_scan(unsigned v, unsigned *red,
   __syncthreads();
   *total = all;
   return before + inc - v;
-}
-
-// The codes of a dummy block: a zero DC difference in the luma table (00) and EOB (1010).
-constexpr unsigned DUMMY_CODE = 0x0A, DUMMY_BITS = 6;
-
-// With fitted tables a dummy block takes the image's own codes for those two symbols, DC first.
-__device__ __forceinline__ void dummy_code(const uint32_t *tab, unsigned &code, unsigned &len) {
-  const uint32_t d = tab[TAB_DC], e = tab[TAB_AC];
-  code = ((d >> 8) << (e & 0xff)) | (e >> 8);
-  len = (d & 0xff) + (e & 0xff);
-}
-
-// OPT: the tables are the image's own (tabs, TAB_WORDS per image), staged for every image of the loop
-template <bool OPT>
-__global__ __launch_bounds__(NT) void jpeg_enc_bits_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
-                                                           uint32_t *__restrict__ local, uint32_t *__restrict__ csum, EPlan p) {
-  __shared__ uint32_t tab[TAB_WORDS];
-  __shared__ unsigned red[NT / 64];
-  if (!OPT) stage_tabs<false>(tab, nullptr);
-  const int t = blockIdx.x * NT + threadIdx.x;
-  int comp = 0, bx, by;
-  const bool real = t < p.nblk && block_of(p, t, comp, bx, by);
-  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    unsigned dummy_bits = DUMMY_BITS;
-    if (OPT) {
-      stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);     // the scan below ends with a barrier, so nobody still reads tab
-      unsigned code;
-      dummy_code(tab, code, dummy_bits);
-    }
-    unsigned bits = t < p.nblk ? dummy_bits : 0;
-    if (real) {
-      const int16_t *ci = coef + (size_t)img * p.nblk * 64;
-      const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
-      uint4 c[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) c[j] = src[j];
-      CountSink sink{tab, 0};
-      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
-      bits = sink.bits;
-    }
-    unsigned total;
-    const unsigned off = wg_exclusive_scan(bits, red, &total);
-    if (t < p.nblk) local[(size_t)img * p.nblk + t] = off;
-    if (threadIdx.x == 0) csum[(size_t)img * p.nchunk + blockIdx.x] = total;
-  }
 }
 
 // One workgroup per image: v[img][0 .. n) becomes its exclusive scan and tot[img * 2 + slot] the sum.  With from_bits, n is the
@@ -452,75 +563,6 @@ __global__ __launch_bounds__(NT) void jpeg_enc_scan_kernel(uint32_t *__restrict_
   }
 }
 
-template <bool OPT>
-__global__ __launch_bounds__(NT) void jpeg_enc_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
-                                                           const uint32_t *__restrict__ local, const uint32_t *__restrict__ csum,
-                                                           uint32_t *__restrict__ bits, EPlan p) {
-  __shared__ uint32_t tab[TAB_WORDS];
-  if (!OPT) stage_tabs<false>(tab, nullptr);
-  const int t = blockIdx.x * NT + threadIdx.x;
-  if (!OPT && t >= p.nblk) return;      // with OPT every thread stays for the barriers of the image loop
-  int comp = 0, bx, by;
-  const bool coded = t < p.nblk;
-  const bool real = coded && block_of(p, t, comp, bx, by);
-  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    if (OPT) {
-      __syncthreads();                    // the image before this one has been coded from tab
-      stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);
-    }
-    if (!coded) continue;
-    const unsigned pos = csum[(size_t)img * p.nchunk + blockIdx.x] + local[(size_t)img * p.nblk + t];
-    // the bits of the word in front of this block count as zeros of the accumulator, so that whole words leave it
-    PackSink sink{tab, bits + (size_t)img * p.words, pos >> 5, 0ull, (int)(pos & 31), true};
-    if (real) {
-      const int16_t *ci = coef + (size_t)img * p.nblk * 64;
-      const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
-      uint4 c[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) c[j] = src[j];
-      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
-    } else if (OPT) {
-      unsigned code, len;
-      dummy_code(tab, code, len);
-      sink.put(code, (int)len);
-    } else {
-      sink.put(DUMMY_CODE, DUMMY_BITS);
-    }
-    if (sink.n) atomicOr(&sink.words[sink.wi], (uint32_t)(sink.acc << (32 - sink.n)));
-  }
-}
-
-// One thread per coded block counts the symbols that its codes use (dummy blocks: a zero DC difference and EOB in the luma tables) in
-// the workgroup's histogram, which then joins the image's: hist (B, TAB_WORDS), zeroed by the call.  Integer atomics in LDS and in
-// memory are order-free, so two runs give the same counts.
-__global__ __launch_bounds__(NT) void jpeg_enc_hist_kernel(const int16_t *__restrict__ coef, uint32_t *__restrict__ hist, EPlan p) {
-  __shared__ unsigned h[TAB_WORDS];
-  const int t = blockIdx.x * NT + threadIdx.x;
-  int comp = 0, bx, by;
-  const bool coded = t < p.nblk;
-  const bool real = coded && block_of(p, t, comp, bx, by);
-  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    for (int i = threadIdx.x; i < TAB_WORDS; i += NT) h[i] = 0;
-    __syncthreads();
-    HistSink sink{h};
-    if (real) {
-      const int16_t *ci = coef + (size_t)img * p.nblk * 64;
-      const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
-      uint4 c[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) c[j] = src[j];
-      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
-    } else if (coded) {
-      sink.sym(TAB_DC, 0, 0);
-      sink.sym(TAB_AC, 0, 0);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < TAB_WORDS; i += NT)
-      if (h[i]) atomicAdd(&hist[(size_t)img * TAB_WORDS + i], h[i]);
-    __syncthreads();
-  }
-}
-
 // key of a symbol for the two smallest counts: the lower count wins, on equal counts the larger symbol; no count: the largest key
 __device__ __forceinline__ unsigned long long merge_key(unsigned count, int sym) {
   return count ? ((unsigned long long)count << 9) | (unsigned)(256 - sym) : ~0ull;
@@ -544,7 +586,6 @@ __device__ __forceinline__ void wave_min2(unsigned long long &k1, unsigned long 
   }
 }
 
-constexpr int HUFF_BYTES = 272;     // BITS (16) and HUFFVAL (256, zeros after the table's symbols)
 constexpr int MAX_CLEN = 32;        // libjpeg's bound, where it ends with an error: a longer code needs counts in Fibonacci proportions
                                     // that sum past 9.2 million in one table.  Here the image's error word becomes 2.
 
@@ -679,13 +720,14 @@ __device__ __forceinline__ unsigned count_ff(unsigned w) {
          (unsigned)((w & 0xff) == 0xff);
 }
 
-__global__ __launch_bounds__(NT) void jpeg_enc_count_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
+// bits: a scan's streams, nwords per image
+__global__ __launch_bounds__(NT) void jpeg_enc_count_kernel(const uint32_t *__restrict__ bits, size_t nwords, const uint32_t *__restrict__ tot,
                                                             uint32_t *__restrict__ ffsum, EPlan p) {
   __shared__ unsigned red[NT / 64];
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
     const unsigned tbits = tot[(size_t)img * 2];
     const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
-    const uint32_t *words = bits + (size_t)img * p.words;
+    const uint32_t *words = bits + (size_t)img * nwords;
     for (unsigned c = blockIdx.x; (size_t)c * CHUNK_WORDS * 4 < nbytes; c += gridDim.x) {
       const unsigned wi = c * CHUNK_WORDS + threadIdx.x * 4;
       unsigned n = 0;
@@ -734,7 +776,10 @@ __device__ __forceinline__ void emit_stuffed(const uint32_t *__restrict__ words,
   }
 }
 
-__global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
+// The emit pass of a sequential file: its one scan lies at the slot's start, then FF D9, the length and the error word.  bits: the
+// scan's streams, nwords per image.  One kernel for both kinds of file measured slower here (profiles/jpeg_enc_refactor.txt), so
+// the two share emit_stuffed only.
+__global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__restrict__ bits, size_t nwords, const uint32_t *__restrict__ tot,
                                                            const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
                                                            int32_t *__restrict__ lens, int32_t *__restrict__ err,
                                                            const int32_t *__restrict__ nval, EPlan p) {
@@ -743,7 +788,7 @@ __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__res
     const unsigned tbits = tot[(size_t)img * 2];
     const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
     uint8_t *slot = out + (size_t)img * cap;
-    emit_stuffed(bits + (size_t)img * p.words, tbits, nbytes, ffsum + (size_t)img * p.nbchunk, slot, cap, red);
+    emit_stuffed(bits + (size_t)img * nwords, tbits, nbytes, ffsum + (size_t)img * p.nbchunk, slot, cap, red);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       const size_t len = (size_t)nbytes + tot[(size_t)img * 2 + 1] + 2;
       const bool fits = len <= cap;
@@ -759,11 +804,49 @@ __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__res
   }
 }
 
-// ---- progressive: sgic_jpeg_encode_prog_batch -----------------------------------------------------------------
-// The file of save(..., progressive=True): the coefficients of coef, coded in the ten scans of libjpeg's jpeg_simple_progression, every
-// scan with tables fitted to it.  A scan runs the chain of the optimised encoder (hist, tables, bits, scan, pack, count, scan, emit)
-// over its own blocks: the two DC scans over the MCU order of coef, an AC scan over its component's raster without dummy blocks.
-// An AC scan's end-of-band runs span blocks, so three or more passes in front of the chain say which blocks lead an EOBRUN symbol:
+// The emit pass of a progressive scan: its stuffed bytes follow those of the scans before it in the image's slot: pos (NSCAN + 1, B)
+// holds where every scan begins.  lens (B, NSCAN).  The scan's tables move from where jpeg_enc_tables_kernel left them (huff4, nval4:
+// four per image) to their slots of huff (B, NSCAN, HUFF_BYTES) and nval (B, NSCAN).  The last scan also sets the error word: 2 if a
+// table had a code that libjpeg refuses, 1 if the slot was too small; the image's lengths are then zero.
+__global__ __launch_bounds__(NT) void jpeg_enc_prog_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
+                                                                const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
+                                                                int32_t *__restrict__ lens, int32_t *__restrict__ err,
+                                                                const uint8_t *__restrict__ huff4, const int32_t *__restrict__ nval4,
+                                                                uint8_t *__restrict__ huff, int32_t *__restrict__ nval,
+                                                                unsigned long long *__restrict__ pos, int scan, EPlan p, Scan s) {
+  __shared__ unsigned red[NT / 64];
+  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
+    const unsigned tbits = tot[(size_t)img * 2];
+    const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
+    const unsigned long long at = pos[(size_t)scan * p.B + img];
+    const size_t room = at < cap ? cap - (size_t)at : 0;
+    emit_stuffed(bits + (size_t)img * s.words, tbits, nbytes, ffsum + (size_t)img * p.nbchunk, out + (size_t)img * cap + (cap - room), room, red);
+    if (blockIdx.x == 0) {
+      for (int j = 0; j < s.ntab; ++j) {
+        const uint8_t *src = huff4 + ((size_t)img * 4 + s.tw[j]) * HUFF_BYTES;
+        uint8_t *dst = huff + ((size_t)img * NSCAN + s.slot + j) * HUFF_BYTES;
+        for (int b = threadIdx.x; b < HUFF_BYTES; b += NT) dst[b] = src[b];
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      for (int j = 0; j < s.ntab; ++j) nval[(size_t)img * NSCAN + s.slot + j] = nval4[(size_t)img * 4 + s.tw[j]];
+      const unsigned long long len = (unsigned long long)nbytes + tot[(size_t)img * 2 + 1], end = at + len;
+      pos[(size_t)(scan + 1) * p.B + img] = end;
+      lens[(size_t)img * NSCAN + scan] = (int32_t)len;
+      if (scan == NSCAN - 1) {
+        bool coded = true;
+        for (int j = 0; j < NSCAN; ++j) coded = coded && nval[(size_t)img * NSCAN + j] >= 0;
+        const bool fits = end <= cap;
+        if (!fits || !coded)
+          for (int j = 0; j < NSCAN; ++j) lens[(size_t)img * NSCAN + j] = 0;
+        err[img] = !coded ? 2 : fits ? 0 : 1;
+      }
+    }
+  }
+}
+
+// ---- what a block sends in a scan; the passes that find an AC scan's end-of-band runs ------------------------------------------------
+// An AC scan's end-of-band runs span blocks, so three or more passes in front of its chain say which blocks lead an EOBRUN symbol:
 //   flags  one thread per block: does it code a coefficient (nz), does it end in zeros or pending correction bits (tail), how many
 //          correction bits trail it; per workgroup the last and the first nz block and the sum of those bits
 //   link   one workgroup per image: the last nz block in front of every workgroup, the first one behind it, the bits in front of it
@@ -771,125 +854,10 @@ __global__ __launch_bounds__(NT) void jpeg_enc_emit_kernel(const uint32_t *__res
 //          are every 0x7FFF blocks from the run's start.  Refinement scans: prefix sums of the correction bits, the run starts
 //   next   refinement: the head that follows if this block is one (binary search in the prefix sums: 0x7FFF blocks or 937 bits)
 //   round  refinement: every marked head marks its successor, then next := next o next; ceil(log2(n / 15)) + 1 rounds mark all
-constexpr int K_DC_FIRST = 0, K_DC_REFINE = 1, K_AC_FIRST = 2, K_AC_REFINE = 3;
-constexpr int NSCAN = 10;
-constexpr int EOBRUN_MAX = 0x7FFF;
-constexpr unsigned CORR_BITS = 937;       // libjpeg's MAX_CORR_BITS - DCTSIZE2 + 1: a run is cut once its correction bits pass this
-constexpr int EOBRUN_BITS = 16 + 14;      // the symbol and its extra bits
-// the bits of a block in a scan: a DC difference of at most 11 bits; a refinement bit; in a first scan (10 - Al)-bit values behind
-// 16-bit codes; in a refinement scan a code, a sign and no correction bit per coefficient at the most, three ZRL at the most
-constexpr unsigned dc_first_bits() { return 16 + 11; }
-constexpr unsigned ac_first_bits(int ss, int se, int al) { return (unsigned)(se - ss + 1) * (16 + 10 - al) + EOBRUN_BITS; }
-constexpr unsigned ac_refine_bits(int ss, int se) { return (unsigned)(se - ss + 1) * 17 + 3 * 16 + EOBRUN_BITS; }
-constexpr unsigned MAX_SCAN_BITS = ac_first_bits(1, 63, 1);       // the largest of the ten scans: chroma, 1 .. 63 at Al = 1
-constexpr unsigned MAX_BLOCKS_PROG = 2675992;
-constexpr size_t MAX_SLOT_BYTES = 0x7fffffff;      // the second limit: an image's slot, which d_len and cap count in 31 bits
-static_assert(MAX_SCAN_BITS == 1605 && ac_first_bits(6, 63, 2) < MAX_SCAN_BITS && ac_refine_bits(1, 63) == 1149, "per-block bounds");
-static_assert((unsigned long long)MAX_BLOCKS_PROG * MAX_SCAN_BITS < (1ull << 32) &&
-              (unsigned long long)(MAX_BLOCKS_PROG + 1) * MAX_SCAN_BITS >= (1ull << 32), "32-bit bit offsets within a scan of an image");
-static_assert((CORR_BITS + 1 + 62) / 63 == 15, "a segment that the correction bits cut holds at least 15 blocks");
-
-struct PScan {
-  int kind;
-  int comp;          // AC scans: the component
-  int ss, se, al;
-  int tab;           // AC scans: the table's place in the table layout
-  int slot;          // the scan's first table in d_huff / d_nval; -1: none
-  int ntab, tw[2];   // its tables and the wavefronts of jpeg_enc_tables_kernel that build them (0 DC 0, 1 AC 0, 2 DC 1, 3 AC 1)
-  int n;             // blocks of the scan per image
-  int nchunk;        // workgroups of NT blocks
-  int rounds;
-  unsigned bound;    // bits of a block at the most
-  int nbchunk;
-  size_t words;      // u32 words of one image's bit stream in this scan
-  size_t off_bits;
-};
-
-struct PPlan {
-  EPlan e;
-  PScan scan[NSCAN];
-  size_t off_blk, off_mark, off_cnt, off_re, off_pre, off_next, off_clast, off_cfirst, off_ctb, off_huff4, off_nval4, off_pos;
-};
-
-bool make_prog_plan(int B, int H, int W, int sub, PPlan *pp) {
-  EPlan &p = pp->e;
-  if (!make_plan(B, H, W, sub, true, &p, MAX_BLOCKS_PROG)) return false;
-  // jpeg_simple_progression for three components: (kind, component, Ss, Se, Al, first table)
-  const int script[NSCAN][6] = {{K_DC_FIRST, 0, 0, 0, 1, 0},  {K_AC_FIRST, 0, 1, 5, 2, 2},   {K_AC_FIRST, 2, 1, 63, 1, 3},
-                                {K_AC_FIRST, 1, 1, 63, 1, 4}, {K_AC_FIRST, 0, 6, 63, 2, 5},  {K_AC_REFINE, 0, 1, 63, 1, 6},
-                                {K_DC_REFINE, 0, 0, 0, 0, -1}, {K_AC_REFINE, 2, 1, 63, 0, 7}, {K_AC_REFINE, 1, 1, 63, 0, 8},
-                                {K_AC_REFINE, 0, 1, 63, 0, 9}};
-  const size_t nblk = (size_t)p.nblk;
-  size_t o = p.off_tabs + align16((size_t)B * TAB_WORDS * sizeof(uint32_t));      // coef, qt, local, csum and tabs are the optimised plan's
-  pp->off_blk = o;     o += align16((size_t)B * nblk);
-  pp->off_mark = o;    o += align16((size_t)B * nblk);
-  pp->off_cnt = o;     o += align16((size_t)B * nblk * sizeof(uint16_t));
-  pp->off_re = o;      o += align16((size_t)B * nblk * sizeof(uint32_t));
-  pp->off_pre = o;     o += align16((size_t)B * (nblk + 1) * sizeof(uint32_t));
-  pp->off_next = o;    o += align16((size_t)2 * B * nblk * sizeof(uint32_t));
-  pp->off_clast = o;   o += align16((size_t)B * p.nchunk * sizeof(int32_t));
-  pp->off_cfirst = o;  o += align16((size_t)B * p.nchunk * sizeof(int32_t));
-  pp->off_ctb = o;     o += align16((size_t)B * p.nchunk * sizeof(uint32_t));
-  pp->off_huff4 = o;   o += align16((size_t)B * 4 * HUFF_BYTES);      // what jpeg_enc_tables_kernel writes for the scan at hand
-  pp->off_nval4 = o;   o += align16((size_t)B * 4 * sizeof(int32_t));
-  // zeroed by one memset: the byte positions of the scans in the slots, the histograms of a scan (zeroed again for every later
-  // scan), the bit streams of the ten scans
-  pp->off_pos = o;     o += align16((size_t)(NSCAN + 1) * B * sizeof(unsigned long long));
-  p.off_hist = o;      o += (size_t)B * TAB_WORDS * sizeof(uint32_t);
-  p.cap = 0;
-  p.nbchunk = 0;
-  for (int s = 0; s < NSCAN; ++s) {
-    PScan &sc = pp->scan[s];
-    sc.kind = script[s][0]; sc.comp = script[s][1]; sc.ss = script[s][2]; sc.se = script[s][3]; sc.al = script[s][4];
-    sc.slot = script[s][5];
-    sc.tab = TAB_AC + (sc.comp ? 256 : 0);
-    sc.ntab = sc.kind == K_DC_FIRST ? 2 : sc.kind == K_DC_REFINE ? 0 : 1;
-    sc.tw[0] = sc.kind == K_DC_FIRST ? 0 : sc.comp ? 3 : 1;
-    sc.tw[1] = 2;
-    sc.n = sc.kind < K_AC_FIRST ? p.nblk : sc.comp ? p.mx * p.my : p.wb * p.hb;
-    sc.nchunk = (sc.n + NT - 1) / NT;
-    sc.rounds = 0;
-    if (sc.kind == K_AC_REFINE) {
-      int k = 0;
-      while (((size_t)15 << k) < (size_t)sc.n) ++k;
-      sc.rounds = k + 1;
-    }
-    sc.bound = sc.kind == K_DC_FIRST ? dc_first_bits() : sc.kind == K_DC_REFINE ? 1 : sc.kind == K_AC_FIRST ? ac_first_bits(sc.ss, sc.se, sc.al)
-                                                                                                           : ac_refine_bits(sc.ss, sc.se);
-    sc.words = (((size_t)sc.n * sc.bound + 31) / 32 + 1 + 3) & ~(size_t)3;
-    sc.nbchunk = (int)((sc.words + CHUNK_WORDS - 1) / CHUNK_WORDS);
-    if (sc.nbchunk > p.nbchunk) p.nbchunk = sc.nbchunk;
-    sc.off_bits = o;   o += (size_t)B * sc.words * sizeof(uint32_t);
-    p.cap += sc.words * 8;        // every byte of a stream may be 0xFF and take a stuffed zero
-  }
-  if (p.cap > MAX_SLOT_BYTES) return false;      // lengths and the caller's cap are 31-bit
-  p.off_bits = p.off_hist;        // nothing of the optimised plan's single stream is left
-  p.off_ffsum = o;   o += align16((size_t)B * p.nbchunk * sizeof(uint32_t));
-  p.off_tot = o;     o += align16((size_t)B * 2 * sizeof(uint32_t));
-  p.bytes = o;
-  return true;
-}
-
-struct NullSink {
-  __device__ __forceinline__ void sym(int, unsigned, int) {}
-  __device__ __forceinline__ void raw(unsigned long long, int) {}
-};
-
-// coefficient k (a constant under unrolling) of a block in c
-__device__ __forceinline__ int coef_of(const uint4 (&c)[8], int k) {
-  const unsigned w = (k & 7) < 2 ? c[k >> 3].x : (k & 7) < 4 ? c[k >> 3].y : (k & 7) < 6 ? c[k >> 3].z : c[k >> 3].w;
-  return (int)(short)((k & 1) ? (w >> 16) : (w & 0xffff));
-}
-
-__device__ __forceinline__ void load_block(uint4 (&c)[8], const int16_t *__restrict__ ci, int t) {
-  const uint4 *src = reinterpret_cast<const uint4 *>(ci + (size_t)t * 64);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) c[j] = src[j];
-}
 
 // block i of a scan -> its place in coef
 template <int K>
-__device__ __forceinline__ int scan_block(const EPlan &p, const PScan &s, int i) {
+__device__ __forceinline__ int scan_block(const EPlan &p, const Scan &s, int i) {
   if (K < K_AC_FIRST) return i;
   if (s.comp) return i * p.bpm + p.ny + s.comp - 1;
   const int by = i / p.wb, bx = i - by * p.wb;
@@ -898,7 +866,7 @@ __device__ __forceinline__ int scan_block(const EPlan &p, const PScan &s, int i)
 
 // A first AC scan's symbols of one block without its EOBRUN: -> tail (the band ends in zeros); nz: a coefficient was coded
 template <typename Sink>
-__device__ __forceinline__ bool walk_ac_first(Sink &sink, const uint4 (&c)[8], const PScan &s, bool &nz) {
+__device__ __forceinline__ bool walk_ac_first(Sink &sink, const uint4 (&c)[8], const Scan &s, bool &nz) {
   int run = 0;
   nz = false;
 #pragma unroll
@@ -922,7 +890,7 @@ __device__ __forceinline__ bool walk_ac_first(Sink &sink, const uint4 (&c)[8], c
 // A refinement AC scan's symbols of one block without its EOBRUN and without the nbr correction bits br that trail it:
 // -> tail (zeros or correction bits are pending at the band's end); nz: a symbol was coded
 template <typename Sink>
-__device__ __forceinline__ bool walk_ac_refine(Sink &sink, const uint4 (&c)[8], const PScan &s, bool &nz, unsigned long long &br, int &nbr) {
+__device__ __forceinline__ bool walk_ac_refine(Sink &sink, const uint4 (&c)[8], const Scan &s, bool &nz, unsigned long long &br, int &nbr) {
   // one pass over the coefficients leaves four masks by position: non-zero, becomes non-zero in this scan, negative, correction bit
   unsigned long long nonzero = 0, one = 0, neg = 0, low = 0;
 #pragma unroll
@@ -972,11 +940,24 @@ __device__ __forceinline__ bool walk_ac_refine(Sink &sink, const uint4 (&c)[8], 
   return run > 0 || nbr > 0;
 }
 
-// Everything block i of a scan sends, in stream order: its own symbols, the EOBRUN symbol if it heads a segment of head blocks, its
+// Everything block i of a scan of kind K sends, in stream order.  Sequential: the whole block; a dummy block is a zero DC difference
+// and EOB in the luma tables.  AC scans: the block's own symbols, the EOBRUN symbol if it heads a segment of head blocks, its
 // trailing correction bits.  ci: the image's coefficients.
 template <int K, typename Sink>
-__device__ __forceinline__ void prog_block(Sink &sink, const EPlan &p, const PScan &s, const int16_t *__restrict__ ci, int i, unsigned head) {
+__device__ __forceinline__ void send_block(Sink &sink, const EPlan &p, const Scan &s, const int16_t *__restrict__ ci, int i, unsigned head) {
   const int t = scan_block<K>(p, s, i);
+  if (K == K_SEQ) {
+    int comp, bx, by;
+    if (block_of(p, t, comp, bx, by)) {
+      uint4 c[8];
+      load_block(c, ci, t);
+      code_block(sink, c, dc_before(p, ci, t), comp ? 1 : 0);
+    } else {
+      sink.sym(TAB_DC, 0, 0);
+      sink.sym(TAB_AC, 0, 0);
+    }
+    return;
+  }
   if (K == K_DC_FIRST || K == K_DC_REFINE) {
     int comp, bx, by;
     const bool real = block_of(p, t, comp, bx, by);
@@ -1012,7 +993,7 @@ __device__ __forceinline__ void prog_block(Sink &sink, const EPlan &p, const PSc
 template <bool REFINE>
 __global__ __launch_bounds__(NT) void jpeg_enc_prog_flags_kernel(const int16_t *__restrict__ coef, uint8_t *__restrict__ blk,
                                                                  int32_t *__restrict__ clast, int32_t *__restrict__ cfirst,
-                                                                 uint32_t *__restrict__ ctb, EPlan p, PScan s) {
+                                                                 uint32_t *__restrict__ ctb, EPlan p, Scan s) {
   __shared__ unsigned red[NT / 64];
   __shared__ int s_last, s_first;
   const int i = blockIdx.x * NT + threadIdx.x;
@@ -1112,7 +1093,7 @@ template <bool REFINE>
 __global__ __launch_bounds__(NT) void jpeg_enc_prog_runs_kernel(const uint8_t *__restrict__ blk, const int32_t *__restrict__ clast,
                                                                 const int32_t *__restrict__ cfirst, const uint32_t *__restrict__ ctb,
                                                                 uint8_t *__restrict__ mark, uint16_t *__restrict__ cnt,
-                                                                uint32_t *__restrict__ re, uint32_t *__restrict__ pre, EPlan p, PScan s) {
+                                                                uint32_t *__restrict__ re, uint32_t *__restrict__ pre, EPlan p, Scan s) {
   __shared__ unsigned long long masks[NT / 64];
   __shared__ unsigned red[NT / 64];
   const int i = blockIdx.x * NT + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1164,7 +1145,7 @@ __global__ __launch_bounds__(NT) void jpeg_enc_prog_runs_kernel(const uint8_t *_
 // Refinement scans, one thread per block in a run: the segment from it ends with the block that fills EOBRUN_MAX or takes the
 // correction bits past CORR_BITS, at the run's end at the latest.  cnt: its blocks; next: the head behind it, s.n if the run ends.
 __global__ __launch_bounds__(NT) void jpeg_enc_prog_next_kernel(const uint32_t *__restrict__ re, const uint32_t *__restrict__ pre,
-                                                                uint16_t *__restrict__ cnt, uint32_t *__restrict__ next, EPlan p, PScan s) {
+                                                                uint16_t *__restrict__ cnt, uint32_t *__restrict__ next, EPlan p, Scan s) {
   const int i = blockIdx.x * NT + threadIdx.x;
   if (i >= s.n) return;
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
@@ -1190,7 +1171,7 @@ __global__ __launch_bounds__(NT) void jpeg_enc_prog_next_kernel(const uint32_t *
 // launch without atomics: the only writes are byte stores of the constant 1, to bytes that are heads.  A mark that appears while the
 // round runs is a head too, so it may or may not act in this round: the marks after the last round are the same.
 __global__ __launch_bounds__(NT) void jpeg_enc_prog_round_kernel(const uint32_t *__restrict__ from, uint32_t *__restrict__ to,
-                                                                 uint8_t *mark, EPlan p, PScan s) {
+                                                                 uint8_t *mark, EPlan p, Scan s) {
   const int i = blockIdx.x * NT + threadIdx.x;
   if (i >= s.n) return;
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
@@ -1205,15 +1186,20 @@ __global__ __launch_bounds__(NT) void jpeg_enc_prog_round_kernel(const uint32_t 
   }
 }
 
+// the blocks of the segment that block `at` of an AC scan heads; 0: it heads none.  The other kinds have no segments
+template <int K>
 __device__ __forceinline__ unsigned head_of(const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt, size_t at) {
+  if (K < K_AC_FIRST) return 0u;
   return mark[at] ? cnt[at] : 0u;
 }
 
-// hist (B, TAB_WORDS), zeroed by the call for this scan
+// ---- the chain of a scan: hist, tables, bits, scan, pack, count, scan, emit --------------------------------------------------------
+// One thread per block of the scan counts the symbols that its codes use in the workgroup's histogram, which then joins the
+// image's: hist (B, TAB_WORDS), zeroed by the call for this scan.  Integer atomics in LDS and in memory are order-free, so two runs
+// give the same counts.
 template <int K>
-__global__ __launch_bounds__(NT) void jpeg_enc_prog_hist_kernel(const int16_t *__restrict__ coef, const uint8_t *__restrict__ mark,
-                                                                const uint16_t *__restrict__ cnt, uint32_t *__restrict__ hist, EPlan p,
-                                                                PScan s) {
+__global__ __launch_bounds__(NT) void jpeg_enc_hist_kernel(const int16_t *__restrict__ coef, const uint8_t *__restrict__ mark,
+                                                           const uint16_t *__restrict__ cnt, uint32_t *__restrict__ hist, EPlan p, Scan s) {
   __shared__ unsigned h[TAB_WORDS];
   const int i = blockIdx.x * NT + threadIdx.x;
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
@@ -1221,7 +1207,7 @@ __global__ __launch_bounds__(NT) void jpeg_enc_prog_hist_kernel(const int16_t *_
     __syncthreads();
     if (i < s.n) {
       HistSink sink{h};
-      prog_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, K >= K_AC_FIRST ? head_of(mark, cnt, (size_t)img * p.nblk + i) : 0u);
+      send_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, head_of<K>(mark, cnt, (size_t)img * p.nblk + i));
     }
     __syncthreads();
     for (int j = threadIdx.x; j < TAB_WORDS; j += NT)
@@ -1230,18 +1216,19 @@ __global__ __launch_bounds__(NT) void jpeg_enc_prog_hist_kernel(const int16_t *_
   }
 }
 
-template <int K>
-__global__ __launch_bounds__(NT) void jpeg_enc_prog_bits_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
-                                                                const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt,
-                                                                uint32_t *__restrict__ local, uint32_t *__restrict__ csum, EPlan p, PScan s) {
+// T: where the code words come from; T_IMAGE: tabs (B, TAB_WORDS)
+template <int K, int T>
+__global__ __launch_bounds__(NT) void jpeg_enc_bits_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
+                                                           const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt,
+                                                           uint32_t *__restrict__ local, uint32_t *__restrict__ csum, EPlan p, Scan s) {
   __shared__ uint32_t tab[TAB_WORDS];
   __shared__ unsigned red[NT / 64];
+  if (T == T_ANNEX_K) stage_tabs<T>(tab, nullptr);
   const int i = blockIdx.x * NT + threadIdx.x;
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    if (K != K_DC_REFINE) stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);     // the scan below ends with a barrier, so nobody still reads tab
+    if (T == T_IMAGE) stage_tabs<T>(tab, tabs + (size_t)img * TAB_WORDS);     // the scan below ends with a barrier, so nobody still reads tab
     CountSink sink{tab, 0};
-    if (i < s.n)
-      prog_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, K >= K_AC_FIRST ? head_of(mark, cnt, (size_t)img * p.nblk + i) : 0u);
+    if (i < s.n) send_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, head_of<K>(mark, cnt, (size_t)img * p.nblk + i));
     unsigned total;
     const unsigned off = wg_exclusive_scan(sink.bits, red, &total);
     if (i < s.n) local[(size_t)img * p.nblk + i] = off;
@@ -1250,286 +1237,166 @@ __global__ __launch_bounds__(NT) void jpeg_enc_prog_bits_kernel(const int16_t *_
 }
 
 // bits: the scan's zeroed streams (B, s.words)
-template <int K>
-__global__ __launch_bounds__(NT) void jpeg_enc_prog_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
-                                                                const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt,
-                                                                const uint32_t *__restrict__ local, const uint32_t *__restrict__ csum,
-                                                                uint32_t *__restrict__ bits, EPlan p, PScan s) {
+template <int K, int T>
+__global__ __launch_bounds__(NT) void jpeg_enc_pack_kernel(const int16_t *__restrict__ coef, const uint32_t *__restrict__ tabs,
+                                                           const uint8_t *__restrict__ mark, const uint16_t *__restrict__ cnt,
+                                                           const uint32_t *__restrict__ local, const uint32_t *__restrict__ csum,
+                                                           uint32_t *__restrict__ bits, EPlan p, Scan s) {
   __shared__ uint32_t tab[TAB_WORDS];
+  if (T == T_ANNEX_K) stage_tabs<T>(tab, nullptr);
   const int i = blockIdx.x * NT + threadIdx.x;
+  if (T != T_IMAGE && i >= s.n) return;      // with T_IMAGE every thread stays for the barriers of the image loop
   for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    if (K != K_DC_REFINE) {
+    if (T == T_IMAGE) {
       __syncthreads();                    // the image before this one has been coded from tab
-      stage_tabs<true>(tab, tabs + (size_t)img * TAB_WORDS);
+      stage_tabs<T>(tab, tabs + (size_t)img * TAB_WORDS);
     }
     if (i >= s.n) continue;
     const unsigned pos = csum[(size_t)img * p.nchunk + blockIdx.x] + local[(size_t)img * p.nblk + i];
+    // the bits of the word in front of this block count as zeros of the accumulator, so that whole words leave it
     PackSink sink{tab, bits + (size_t)img * s.words, pos >> 5, 0ull, (int)(pos & 31), true};
-    prog_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, K >= K_AC_FIRST ? head_of(mark, cnt, (size_t)img * p.nblk + i) : 0u);
+    send_block<K>(sink, p, s, coef + (size_t)img * p.nblk * 64, i, head_of<K>(mark, cnt, (size_t)img * p.nblk + i));
     if (sink.n) atomicOr(&sink.words[sink.wi], (uint32_t)(sink.acc << (32 - sink.n)));
   }
 }
 
-// The scan's stuffed bytes follow those of the scans before it in the image's slot: pos (NSCAN + 1, B) holds where every scan
-// begins.  lens (B, NSCAN).  The scan's tables move from where jpeg_enc_tables_kernel left them (huff4, nval4: four per image) to
-// their slots of huff (B, NSCAN, HUFF_BYTES) and nval (B, NSCAN).  The last scan also sets the error word: 2 if a table had a code
-// that libjpeg refuses, 1 if the slot was too small; the image's lengths are then zero.
-__global__ __launch_bounds__(NT) void jpeg_enc_prog_emit_kernel(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tot,
-                                                                const uint32_t *__restrict__ ffsum, uint8_t *__restrict__ out, size_t cap,
-                                                                int32_t *__restrict__ lens, int32_t *__restrict__ err,
-                                                                const uint8_t *__restrict__ huff4, const int32_t *__restrict__ nval4,
-                                                                uint8_t *__restrict__ huff, int32_t *__restrict__ nval,
-                                                                unsigned long long *__restrict__ pos, int scan, EPlan p, PScan s) {
-  __shared__ unsigned red[NT / 64];
-  for (int img = blockIdx.y; img < p.B; img += gridDim.y) {
-    const unsigned tbits = tot[(size_t)img * 2];
-    const unsigned nbytes = (tbits >> 3) + ((tbits & 7) ? 1 : 0);
-    const unsigned long long at = pos[(size_t)scan * p.B + img];
-    const size_t room = at < cap ? cap - (size_t)at : 0;
-    emit_stuffed(bits + (size_t)img * s.words, tbits, nbytes, ffsum + (size_t)img * p.nbchunk, out + (size_t)img * cap + (cap - room), room, red);
-    if (blockIdx.x == 0) {
-      for (int j = 0; j < s.ntab; ++j) {
-        const uint8_t *src = huff4 + ((size_t)img * 4 + s.tw[j]) * HUFF_BYTES;
-        uint8_t *dst = huff + ((size_t)img * NSCAN + s.slot + j) * HUFF_BYTES;
-        for (int b = threadIdx.x; b < HUFF_BYTES; b += NT) dst[b] = src[b];
-      }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      for (int j = 0; j < s.ntab; ++j) nval[(size_t)img * NSCAN + s.slot + j] = nval4[(size_t)img * 4 + s.tw[j]];
-      const unsigned long long len = (unsigned long long)nbytes + tot[(size_t)img * 2 + 1], end = at + len;
-      pos[(size_t)(scan + 1) * p.B + img] = end;
-      lens[(size_t)img * NSCAN + scan] = (int32_t)len;
-      if (scan == NSCAN - 1) {
-        bool coded = true;
-        for (int j = 0; j < NSCAN; ++j) coded = coded && nval[(size_t)img * NSCAN + j] >= 0;
-        const bool fits = end <= cap;
-        if (!fits || !coded)
-          for (int j = 0; j < NSCAN; ++j) lens[(size_t)img * NSCAN + j] = 0;
-        err[img] = !coded ? 2 : fits ? 0 : 1;
-      }
-    }
-  }
-}
-
-// the workspace arrays that the chain of a scan shares
-struct PWork {
-  const int16_t *coef;
-  uint32_t *hist, *tabs;
-  uint8_t *huff4;
-  int32_t *nval4;
-  const uint8_t *mark;
-  const uint16_t *cnt;
-  uint32_t *local, *csum, *tot;
-};
-
-// hist, tables, bits, scan and pack of one scan.  The tables are built by the optimised encoder's kernel as it is: the scan's symbols
-// are counted where that kernel's layout has the table, the other histograms stay zero and give empty tables.
-template <int K>
-void launch_prog_chain(const EPlan &p, const PScan &sc, dim3 grid, unsigned gy, const PWork &w, uint32_t *bits, hipStream_t st) {
-  if constexpr (K != K_DC_REFINE) {
-    jpeg_enc_prog_hist_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.mark, w.cnt, w.hist, p, sc);
-    jpeg_enc_tables_kernel<<<gy, NT, 0, st>>>(w.hist, w.tabs, w.huff4, w.nval4, p.B);
-  }
-  jpeg_enc_prog_bits_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.tabs, w.mark, w.cnt, w.local, w.csum, p, sc);
-  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(w.csum, p.nchunk, sc.nchunk, w.tot, 0, 0, p.B);
-  jpeg_enc_prog_pack_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.tabs, w.mark, w.cnt, w.local, w.csum, bits, p, sc);
-}
-
-#define JPEG_ENC_PROG_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2675992 coded blocks per image and a slot below 2^31 bytes"
-
-int encode_prog_batch(const char *name, const PPlan &pp, const uint8_t *d_rgb, int B, const uint16_t *h_qt, uint8_t *d_work,
-                      size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff, int32_t *d_nval,
-                      sgic_stream_t stream) {
-  const EPlan &p = pp.e;
-  SGIC_REQUIRE_AS(name, d_rgb && h_qt && d_work && d_out && d_len && d_err && d_huff && d_nval, "null pointer");
+// the checks that the three batch calls share; d_huff and d_nval are required where the mode fits tables
+int check_args(const char *name, const Mode &m, const Plan &pl, const uint8_t *d_rgb, const uint16_t *h_qt, const uint8_t *d_work,
+               size_t work_bytes, const uint8_t *d_out, size_t cap, const int32_t *d_len, const int32_t *d_err, const uint8_t *d_huff,
+               const int32_t *d_nval) {
+  SGIC_REQUIRE_AS(name, d_rgb && h_qt && d_work && d_out && d_len && d_err && (!m.fitted || (d_huff && d_nval)), "null pointer");
   SGIC_REQUIRE_AS(name, ((uintptr_t)d_work & 15) == 0, "the workspace must be 16-byte aligned");
   SGIC_REQUIRE_AS(name, ((uintptr_t)h_qt & 1) == 0 && ((uintptr_t)d_len & 3) == 0 && ((uintptr_t)d_err & 3) == 0 &&
                             ((uintptr_t)d_huff & 3) == 0 && ((uintptr_t)d_nval & 3) == 0, "misaligned pointer");
-  SGIC_REQUIRE_AS(name, work_bytes >= p.bytes, "the workspace is smaller than sgic_jpeg_encode_prog_work_bytes says");
-  SGIC_REQUIRE_AS(name, cap >= p.cap && cap <= 0x7fffffff, "the slots are smaller than sgic_jpeg_encode_prog_cap says");
-  for (size_t i = 0; i < (size_t)B * 128; ++i) SGIC_REQUIRE_AS(name, h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
+  SGIC_REQUIRE_AS(name, work_bytes >= pl.bytes, m.work);
+  SGIC_REQUIRE_AS(name, cap >= pl.cap && cap <= 0x7fffffff, m.slots);
+  for (size_t i = 0; i < (size_t)pl.e.B * 128; ++i) SGIC_REQUIRE_AS(name, h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
+  return SGIC_OK;
+}
+
+// hist and tables (fitted tables only), bits, scan and pack of one scan.  The tables kernel always builds four tables per image: a
+// progressive scan's symbols are counted where its layout has the table, the other histograms stay zero and give empty tables.
+// huff, nval: where it leaves BITS, HUFFVAL and the symbol counts
+template <int K, int T>
+void launch_chain(const EPlan &p, const Scan &sc, dim3 grid, unsigned gy, const Work &w, uint8_t *huff, int32_t *nval, uint32_t *bits,
+                  hipStream_t st) {
+  if constexpr (T == T_IMAGE) {
+    jpeg_enc_hist_kernel<K><<<grid, NT, 0, st>>>(w.coef, w.mark, w.cnt, w.hist, p, sc);
+    jpeg_enc_tables_kernel<<<gy, NT, 0, st>>>(w.hist, w.tabs, huff, nval, p.B);
+  }
+  jpeg_enc_bits_kernel<K, T><<<grid, NT, 0, st>>>(w.coef, w.tabs, w.mark, w.cnt, w.local, w.csum, p, sc);
+  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(w.csum, p.nchunk, sc.nchunk, w.tot, 0, 0, p.B);
+  jpeg_enc_pack_kernel<K, T><<<grid, NT, 0, st>>>(w.coef, w.tabs, w.mark, w.cnt, w.local, w.csum, bits, p, sc);
+}
+
+// The three batch calls: the plan of the mode, the checks, then the coefficients and the chain of every scan of the script
+int encode(const char *name, const Mode &m, const uint8_t *d_rgb, int B, int H, int W, int sub, const uint16_t *h_qt, uint8_t *d_work,
+           size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff, int32_t *d_nval,
+           sgic_stream_t stream) {
+  Plan pl;
+  SGIC_REQUIRE_AS(name, make_plan(m, B, H, W, sub, d_work, &pl), m.limits);
+  if (const int rc = check_args(name, m, pl, d_rgb, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval)) return rc;
+  const EPlan &p = pl.e;
+  const Work &w = pl.w;
   hipStream_t st = to_stream(stream);
-  int16_t *coef = reinterpret_cast<int16_t *>(d_work);
-  uint16_t *qt = reinterpret_cast<uint16_t *>(d_work + p.off_qt);
-  uint32_t *local = reinterpret_cast<uint32_t *>(d_work + p.off_local);
-  uint32_t *csum = reinterpret_cast<uint32_t *>(d_work + p.off_csum);
-  uint32_t *tabs = reinterpret_cast<uint32_t *>(d_work + p.off_tabs);
-  uint8_t *blk = d_work + pp.off_blk, *mark = d_work + pp.off_mark;
-  uint16_t *cnt = reinterpret_cast<uint16_t *>(d_work + pp.off_cnt);
-  uint32_t *re = reinterpret_cast<uint32_t *>(d_work + pp.off_re);
-  uint32_t *pre = reinterpret_cast<uint32_t *>(d_work + pp.off_pre);
-  uint32_t *next[2] = {reinterpret_cast<uint32_t *>(d_work + pp.off_next), reinterpret_cast<uint32_t *>(d_work + pp.off_next) + (size_t)B * p.nblk};
-  int32_t *clast = reinterpret_cast<int32_t *>(d_work + pp.off_clast), *cfirst = reinterpret_cast<int32_t *>(d_work + pp.off_cfirst);
-  uint32_t *ctb = reinterpret_cast<uint32_t *>(d_work + pp.off_ctb);
-  unsigned long long *pos = reinterpret_cast<unsigned long long *>(d_work + pp.off_pos);
-  uint32_t *ffsum = reinterpret_cast<uint32_t *>(d_work + p.off_ffsum);
-  uint32_t *tot = reinterpret_cast<uint32_t *>(d_work + p.off_tot);
-  uint32_t *hist = reinterpret_cast<uint32_t *>(d_work + p.off_hist);
-  uint8_t *huff4 = d_work + pp.off_huff4;
-  int32_t *nval4 = reinterpret_cast<int32_t *>(d_work + pp.off_nval4);
-  const PWork w{coef, hist, tabs, huff4, nval4, mark, cnt, local, csum, tot};
-  SGIC_HIP(hipMemcpyAsync(qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-  SGIC_HIP(hipMemsetAsync(d_work + pp.off_pos, 0, p.off_ffsum - pp.off_pos, st));
+  SGIC_HIP(hipMemcpyAsync(w.qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+  SGIC_HIP(hipMemsetAsync(w.zero, 0, (size_t)(reinterpret_cast<uint8_t *>(w.ffsum) - w.zero), st));
   const unsigned gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
-  jpeg_enc_coef_kernel<<<dim3(p.nchunk, gy), NT, 0, st>>>(d_rgb, qt, coef, p);
-  for (int k = 0; k < NSCAN; ++k) {
-    const PScan &sc = pp.scan[k];
+  jpeg_enc_coef_kernel<<<dim3(p.nchunk, gy), NT, 0, st>>>(d_rgb, w.qt, w.coef, p);
+  // a sequential call's four tables are the caller's; a progressive scan's go to scratch, from where the emit pass moves them
+  uint8_t *huff = m.progressive ? w.huff4 : d_huff;
+  int32_t *nval = m.progressive ? w.nval4 : d_nval;
+  for (int k = 0; k < pl.nscan; ++k) {
+    const Scan &sc = pl.scan[k];
     const dim3 grid(sc.nchunk, gy), gbytes(sc.nbchunk < MAX_CHUNK_GRID ? sc.nbchunk : MAX_CHUNK_GRID, gy);
-    if (k && sc.kind != K_DC_REFINE) SGIC_HIP(hipMemsetAsync(hist, 0, (size_t)B * TAB_WORDS * sizeof(uint32_t), st));
-    uint32_t *bits = reinterpret_cast<uint32_t *>(d_work + sc.off_bits);
+    if (k && sc.kind != K_DC_REFINE) SGIC_HIP(hipMemsetAsync(w.hist, 0, (size_t)B * TAB_WORDS * sizeof(uint32_t), st));
+    uint32_t *bits = w.bits[k];
     if (sc.kind == K_AC_FIRST) {
-      jpeg_enc_prog_flags_kernel<false><<<grid, NT, 0, st>>>(coef, blk, clast, cfirst, ctb, p, sc);
-      jpeg_enc_prog_link_kernel<<<gy, NT, 0, st>>>(clast, cfirst, ctb, p.nchunk, sc.nchunk, sc.n, B);
-      jpeg_enc_prog_runs_kernel<false><<<grid, NT, 0, st>>>(blk, clast, cfirst, ctb, mark, cnt, re, pre, p, sc);
+      jpeg_enc_prog_flags_kernel<false><<<grid, NT, 0, st>>>(w.coef, w.blk, w.clast, w.cfirst, w.ctb, p, sc);
+      jpeg_enc_prog_link_kernel<<<gy, NT, 0, st>>>(w.clast, w.cfirst, w.ctb, p.nchunk, sc.nchunk, sc.n, B);
+      jpeg_enc_prog_runs_kernel<false><<<grid, NT, 0, st>>>(w.blk, w.clast, w.cfirst, w.ctb, w.mark, w.cnt, w.re, w.pre, p, sc);
     } else if (sc.kind == K_AC_REFINE) {
-      jpeg_enc_prog_flags_kernel<true><<<grid, NT, 0, st>>>(coef, blk, clast, cfirst, ctb, p, sc);
-      jpeg_enc_prog_link_kernel<<<gy, NT, 0, st>>>(clast, cfirst, ctb, p.nchunk, sc.nchunk, sc.n, B);
-      jpeg_enc_prog_runs_kernel<true><<<grid, NT, 0, st>>>(blk, clast, cfirst, ctb, mark, cnt, re, pre, p, sc);
-      jpeg_enc_prog_next_kernel<<<grid, NT, 0, st>>>(re, pre, cnt, next[0], p, sc);
-      for (int r = 0; r < sc.rounds; ++r) jpeg_enc_prog_round_kernel<<<grid, NT, 0, st>>>(next[r & 1], next[~r & 1], mark, p, sc);
+      jpeg_enc_prog_flags_kernel<true><<<grid, NT, 0, st>>>(w.coef, w.blk, w.clast, w.cfirst, w.ctb, p, sc);
+      jpeg_enc_prog_link_kernel<<<gy, NT, 0, st>>>(w.clast, w.cfirst, w.ctb, p.nchunk, sc.nchunk, sc.n, B);
+      jpeg_enc_prog_runs_kernel<true><<<grid, NT, 0, st>>>(w.blk, w.clast, w.cfirst, w.ctb, w.mark, w.cnt, w.re, w.pre, p, sc);
+      jpeg_enc_prog_next_kernel<<<grid, NT, 0, st>>>(w.re, w.pre, w.cnt, w.next, p, sc);
+      uint32_t *next[2] = {w.next, w.next + (size_t)B * p.nblk};
+      for (int r = 0; r < sc.rounds; ++r) jpeg_enc_prog_round_kernel<<<grid, NT, 0, st>>>(next[r & 1], next[~r & 1], w.mark, p, sc);
     }
     switch (sc.kind) {
-      case K_DC_FIRST: launch_prog_chain<K_DC_FIRST>(p, sc, grid, gy, w, bits, st); break;
-      case K_DC_REFINE: launch_prog_chain<K_DC_REFINE>(p, sc, grid, gy, w, bits, st); break;
-      case K_AC_FIRST: launch_prog_chain<K_AC_FIRST>(p, sc, grid, gy, w, bits, st); break;
-      default: launch_prog_chain<K_AC_REFINE>(p, sc, grid, gy, w, bits, st); break;
+      case K_SEQ:
+        if (m.fitted)
+          launch_chain<K_SEQ, T_IMAGE>(p, sc, grid, gy, w, huff, nval, bits, st);
+        else
+          launch_chain<K_SEQ, T_ANNEX_K>(p, sc, grid, gy, w, huff, nval, bits, st);
+        break;
+      case K_DC_FIRST: launch_chain<K_DC_FIRST, T_IMAGE>(p, sc, grid, gy, w, huff, nval, bits, st); break;
+      case K_DC_REFINE: launch_chain<K_DC_REFINE, T_NONE>(p, sc, grid, gy, w, huff, nval, bits, st); break;
+      case K_AC_FIRST: launch_chain<K_AC_FIRST, T_IMAGE>(p, sc, grid, gy, w, huff, nval, bits, st); break;
+      default: launch_chain<K_AC_REFINE, T_IMAGE>(p, sc, grid, gy, w, huff, nval, bits, st); break;
     }
-    // count, scan and emit take the scan's stream through a plan that carries its word count; the stuffing counts keep p.nbchunk as stride
-    EPlan ps = p;
-    ps.words = sc.words;
-    jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, ps);
-    jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(ffsum, p.nbchunk, 0, tot, 1, 1, B);
-    jpeg_enc_prog_emit_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, d_out, cap, d_len, d_err, huff4, nval4, d_huff, d_nval, pos, k, p, sc);
+    jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, sc.words, w.tot, w.ffsum, p);
+    jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(w.ffsum, p.nbchunk, 0, w.tot, 1, 1, B);
+    if (m.progressive)
+      jpeg_enc_prog_emit_kernel<<<gbytes, NT, 0, st>>>(bits, w.tot, w.ffsum, d_out, cap, d_len, d_err, w.huff4, w.nval4, d_huff, d_nval, w.pos, k, p, sc);
+    else
+      jpeg_enc_emit_kernel<<<gbytes, NT, 0, st>>>(bits, sc.words, w.tot, w.ffsum, d_out, cap, d_len, d_err, d_nval, p);
   }
   return sgic::check_launch(name);
 }
 
-#define JPEG_ENC_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2581110 coded blocks per image"
-#define JPEG_ENC_OPT_LIMITS "1 <= B, 1 <= H, W <= 16384, subsampling 0, 1 or 2, at most 2579559 coded blocks per image"
+int plan_cap(const char *name, const Mode &m, int H, int W, int sub, size_t *cap) {
+  SGIC_REQUIRE_AS(name, cap != nullptr, "null output");
+  Plan pl;
+  SGIC_REQUIRE_AS(name, make_plan(m, 1, H, W, sub, nullptr, &pl), m.limits);
+  *cap = pl.cap;
+  return SGIC_OK;
+}
 
-bool make_plan(int B, int H, int W, int sub, EPlan *p) { return make_plan(B, H, W, sub, false, p); }
-bool make_opt_plan(int B, int H, int W, int sub, EPlan *p) { return make_plan(B, H, W, sub, true, p); }
-
-// The checks that both entry points share, then the launches; p is the entry point's plan, opt says whether it is make_opt_plan's.
-// d_huff and d_nval are those of sgic_jpeg_encode_opt_batch (checked there), null for the Annex K tables.
-int encode_batch(const char *name, bool opt, const EPlan &p, const uint8_t *d_rgb, int B, const uint16_t *h_qt, uint8_t *d_work,
-                 size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err, uint8_t *d_huff, int32_t *d_nval,
-                 sgic_stream_t stream) {
-  SGIC_REQUIRE_AS(name, d_rgb && h_qt && d_work && d_out && d_len && d_err, "null pointer");
-  SGIC_REQUIRE_AS(name, ((uintptr_t)d_work & 15) == 0, "the workspace must be 16-byte aligned");
-  SGIC_REQUIRE_AS(name, ((uintptr_t)h_qt & 1) == 0 && ((uintptr_t)d_len & 3) == 0 && ((uintptr_t)d_err & 3) == 0, "misaligned pointer");
-  SGIC_REQUIRE_AS(name, work_bytes >= p.bytes,
-                  opt ? "the workspace is smaller than sgic_jpeg_encode_opt_work_bytes says"
-                      : "the workspace is smaller than sgic_jpeg_encode_work_bytes says");
-  SGIC_REQUIRE_AS(name, cap >= p.cap && cap <= 0x7fffffff,
-                  opt ? "the slots are smaller than sgic_jpeg_encode_opt_cap says" : "the slots are smaller than sgic_jpeg_encode_cap says");
-  for (size_t i = 0; i < (size_t)B * 128; ++i) SGIC_REQUIRE_AS(name, h_qt[i] >= 1 && h_qt[i] <= 255, "a quantisation table entry outside [1, 255]");
-  hipStream_t st = to_stream(stream);
-  int16_t *coef = reinterpret_cast<int16_t *>(d_work);
-  uint16_t *qt = reinterpret_cast<uint16_t *>(d_work + p.off_qt);
-  uint32_t *local = reinterpret_cast<uint32_t *>(d_work + p.off_local);
-  uint32_t *csum = reinterpret_cast<uint32_t *>(d_work + p.off_csum);
-  uint32_t *tabs = reinterpret_cast<uint32_t *>(d_work + p.off_tabs);
-  uint32_t *hist = reinterpret_cast<uint32_t *>(d_work + p.off_hist);
-  uint32_t *bits = reinterpret_cast<uint32_t *>(d_work + p.off_bits);
-  uint32_t *ffsum = reinterpret_cast<uint32_t *>(d_work + p.off_ffsum);
-  uint32_t *tot = reinterpret_cast<uint32_t *>(d_work + p.off_tot);
-  SGIC_HIP(hipMemcpyAsync(qt, h_qt, (size_t)B * 128 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-  // the histograms lie directly in front of the bit stream (make_plan), so one memset zeroes both
-  SGIC_HIP(hipMemsetAsync(opt ? hist : bits, 0, p.off_ffsum - (opt ? p.off_hist : p.off_bits), st));
-  const unsigned gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
-  const dim3 gblocks(p.nchunk, gy), gbytes(p.nbchunk < MAX_CHUNK_GRID ? p.nbchunk : MAX_CHUNK_GRID, gy);
-  jpeg_enc_coef_kernel<<<gblocks, NT, 0, st>>>(d_rgb, qt, coef, p);
-  if (opt) {
-    jpeg_enc_hist_kernel<<<gblocks, NT, 0, st>>>(coef, hist, p);
-    jpeg_enc_tables_kernel<<<gy, NT, 0, st>>>(hist, tabs, d_huff, d_nval, B);
-    jpeg_enc_bits_kernel<true><<<gblocks, NT, 0, st>>>(coef, tabs, local, csum, p);
-  } else {
-    jpeg_enc_bits_kernel<false><<<gblocks, NT, 0, st>>>(coef, nullptr, local, csum, p);
-  }
-  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(csum, p.nchunk, p.nchunk, tot, 0, 0, B);
-  if (opt)
-    jpeg_enc_pack_kernel<true><<<gblocks, NT, 0, st>>>(coef, tabs, local, csum, bits, p);
-  else
-    jpeg_enc_pack_kernel<false><<<gblocks, NT, 0, st>>>(coef, nullptr, local, csum, bits, p);
-  jpeg_enc_count_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, p);
-  jpeg_enc_scan_kernel<<<gy, NT, 0, st>>>(ffsum, p.nbchunk, 0, tot, 1, 1, B);
-  jpeg_enc_emit_kernel<<<gbytes, NT, 0, st>>>(bits, tot, ffsum, d_out, cap, d_len, d_err, opt ? d_nval : nullptr, p);
-  return sgic::check_launch(name);
+int plan_work_bytes(const char *name, const Mode &m, int B, int H, int W, int sub, size_t *bytes) {
+  SGIC_REQUIRE_AS(name, bytes != nullptr, "null output");
+  Plan pl;
+  SGIC_REQUIRE_AS(name, make_plan(m, B, H, W, sub, nullptr, &pl), m.limits);
+  *bytes = pl.bytes;
+  return SGIC_OK;
 }
 
 }  // namespace
 
-extern "C" int sgic_jpeg_encode_cap(int H, int W, int subsampling, size_t *cap) {
-  SGIC_REQUIRE(cap != nullptr, "null output");
-  EPlan p;
-  SGIC_REQUIRE(make_plan(1, H, W, subsampling, &p), JPEG_ENC_LIMITS);
-  *cap = p.cap;
-  return SGIC_OK;
-}
+extern "C" int sgic_jpeg_encode_cap(int H, int W, int subsampling, size_t *cap) { return plan_cap(__func__, ANNEX_K, H, W, subsampling, cap); }
 
 extern "C" int sgic_jpeg_encode_work_bytes(int B, int H, int W, int subsampling, size_t *bytes) {
-  SGIC_REQUIRE(bytes != nullptr, "null output");
-  EPlan p;
-  SGIC_REQUIRE(make_plan(B, H, W, subsampling, &p), JPEG_ENC_LIMITS);
-  *bytes = p.bytes;
-  return SGIC_OK;
+  return plan_work_bytes(__func__, ANNEX_K, B, H, W, subsampling, bytes);
 }
 
 extern "C" int sgic_jpeg_encode_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt, uint8_t *d_work,
                                       size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err,
                                       sgic_stream_t stream) {
-  EPlan p;
-  SGIC_REQUIRE(make_plan(B, H, W, subsampling, &p), JPEG_ENC_LIMITS);
-  return encode_batch(__func__, false, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, nullptr, nullptr, stream);
+  return encode(__func__, ANNEX_K, d_rgb, B, H, W, subsampling, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, nullptr, nullptr, stream);
 }
 
-extern "C" int sgic_jpeg_encode_opt_cap(int H, int W, int subsampling, size_t *cap) {
-  SGIC_REQUIRE(cap != nullptr, "null output");
-  EPlan p;
-  SGIC_REQUIRE(make_opt_plan(1, H, W, subsampling, &p), JPEG_ENC_OPT_LIMITS);
-  *cap = p.cap;
-  return SGIC_OK;
-}
+extern "C" int sgic_jpeg_encode_opt_cap(int H, int W, int subsampling, size_t *cap) { return plan_cap(__func__, FITTED, H, W, subsampling, cap); }
 
 extern "C" int sgic_jpeg_encode_opt_work_bytes(int B, int H, int W, int subsampling, size_t *bytes) {
-  SGIC_REQUIRE(bytes != nullptr, "null output");
-  EPlan p;
-  SGIC_REQUIRE(make_opt_plan(B, H, W, subsampling, &p), JPEG_ENC_OPT_LIMITS);
-  *bytes = p.bytes;
-  return SGIC_OK;
+  return plan_work_bytes(__func__, FITTED, B, H, W, subsampling, bytes);
 }
 
 extern "C" int sgic_jpeg_encode_opt_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt,
                                           uint8_t *d_work, size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err,
                                           uint8_t *d_huff, int32_t *d_nval, sgic_stream_t stream) {
-  EPlan p;
-  SGIC_REQUIRE(make_opt_plan(B, H, W, subsampling, &p), JPEG_ENC_OPT_LIMITS);
-  SGIC_REQUIRE(d_huff && d_nval, "null pointer");
-  SGIC_REQUIRE(((uintptr_t)d_huff & 3) == 0 && ((uintptr_t)d_nval & 3) == 0, "misaligned pointer");
-  return encode_batch(__func__, true, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
+  return encode(__func__, FITTED, d_rgb, B, H, W, subsampling, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
 }
 
 extern "C" int sgic_jpeg_encode_prog_cap(int H, int W, int subsampling, size_t *cap) {
-  SGIC_REQUIRE(cap != nullptr, "null output");
-  PPlan p;
-  SGIC_REQUIRE(make_prog_plan(1, H, W, subsampling, &p), JPEG_ENC_PROG_LIMITS);
-  *cap = p.e.cap;
-  return SGIC_OK;
+  return plan_cap(__func__, PROGRESSIVE, H, W, subsampling, cap);
 }
 
 extern "C" int sgic_jpeg_encode_prog_work_bytes(int B, int H, int W, int subsampling, size_t *bytes) {
-  SGIC_REQUIRE(bytes != nullptr, "null output");
-  PPlan p;
-  SGIC_REQUIRE(make_prog_plan(B, H, W, subsampling, &p), JPEG_ENC_PROG_LIMITS);
-  *bytes = p.e.bytes;
-  return SGIC_OK;
+  return plan_work_bytes(__func__, PROGRESSIVE, B, H, W, subsampling, bytes);
 }
 
 extern "C" int sgic_jpeg_encode_prog_batch(const uint8_t *d_rgb, int B, int H, int W, int subsampling, const uint16_t *h_qt,
                                            uint8_t *d_work, size_t work_bytes, uint8_t *d_out, size_t cap, int32_t *d_len, int32_t *d_err,
                                            uint8_t *d_huff, int32_t *d_nval, sgic_stream_t stream) {
-  PPlan p;
-  SGIC_REQUIRE(make_prog_plan(B, H, W, subsampling, &p), JPEG_ENC_PROG_LIMITS);
-  return encode_prog_batch(__func__, p, d_rgb, B, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
+  return encode(__func__, PROGRESSIVE, d_rgb, B, H, W, subsampling, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, d_huff, d_nval, stream);
 }

@@ -54,6 +54,41 @@ def test_200x300_single(sub):
     assert jpeg_enc.encode_batch(_dev(img[None]), 90, sub) == [ref.pillow_bytes(img, 90, sub)]
 
 
+@pytest.fixture(scope="module")
+def pair():
+    """two 8 x 8 images and Pillow's two baseline files at q = 75, 4:2:0"""
+    imgs = [ref.image("natural", 8, 8, 31), ref.image("noise", 8, 8, 32)]
+    want = [ref.pillow_bytes(im, 75, 2) for im in imgs]
+    assert want[0] != want[1]
+    return np.stack(imgs), want
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_image_loop_past_the_grid_cap(pair, shift):
+    """32 770 images of 8 x 8: blockIdx.y stops at 32 768, so workgroups 0 and 1 of every pass take a second image; with shift 1 it
+    is of the other kind than their first one (test_gpu_jpeg_enc_opt has the reasoning)"""
+    import torch
+    import sgic_amd  # noqa: F401
+    from sgic_amd import jpeg_enc, ops
+    imgs, want = pair
+    B = 32770
+    kind = (np.arange(B) + shift * (np.arange(B) // 32768)) % 2
+    assert [int(kind[b]) for b in (0, 1, 32767, 32768, 32769)] == ([0, 1, 1, 0, 1] if shift == 0 else [0, 1, 1, 1, 0])
+    x = _dev(imgs)[torch.from_numpy(kind).to("cuda:0")].contiguous()
+    tables = np.broadcast_to(jpeg_enc.quant_tables(75), (B, 2, 64))
+    buf, lens, err = ops.jpeg_encode(x, tables, 2)
+    assert not err.cpu().numpy().any()
+    lens_h = lens.cpu().numpy()
+    host = buf[:, :int(lens_h.max())].cpu().numpy()
+    head = jpeg_enc.header(8, 8, tables[0], 2)
+    files = set()
+    for b in range(B):
+        data = host[b, :lens_h[b]].tobytes()
+        files.add(data)
+        assert head + data == want[kind[b]], b
+    assert len(files) == 2
+
+
 def test_decoder_takes_the_output(trio):
     from PIL import Image
     import sgic_amd  # noqa: F401
