@@ -368,23 +368,30 @@ __global__ __launch_bounds__(256, (NBUF * UP >= 4 || (S3 && UP > 1)) ? 2 : 3) vo
   // one tile of this wave's item: S^T, online softmax, O^T update, reading region `reg`
   auto compute_s = [&](const float *sK, f32x16 &s) {
     if constexpr (S3) {
-      // four 16-d steps, six bf16 MFMAs each (terms smallest first, as gemm_split.hip), ONE accumulation chain: a dependent
-      // v_mfma_f32_32x32x16_bf16 issues back to back, so a second accumulator would only cost its zeroing and the final add
+      // four 16-d steps, six bf16 MFMAs each, TWO accumulation chains: the leading term k1 q1 alone in s (four roundings per score),
+      // the five small terms (smallest first, as gemm_split.hip) in sl, which stays below 2^-7 of the score, so its twenty roundings
+      // are far below an fp32 ulp of s.  With all six terms in one chain a score took 24 roundings at its full magnitude -- more
+      // than the f32 variant's 17 of half-length partial sums -- and where the scores carry the output's error (a few keys per row)
+      // the variant was 1.2 - 1.3 x the f32 variant's rms error (tests/test_gpu_split3_accuracy.py).  The chains are independent,
+      // so the MFMAs still issue back to back; the cost is 16 registers, their zeroing and one add per element and tile.
+      f32x16 sl;
 #pragma unroll
-      for (int e = 0; e < 16; e++) s[e] = 0.f;
+      for (int e = 0; e < 16; e++) s[e] = 0.f, sl[e] = 0.f;
       const unsigned char *kb = reinterpret_cast<const unsigned char *>(sK) + lq * AT_K3_ROWB + lh * 16;
 #pragma unroll
       for (int c = 0; c < 4; c++) {
         const at_bf16x8 k1 = *reinterpret_cast<const at_bf16x8 *>(kb + c * 32);
         const at_bf16x8 k2 = *reinterpret_cast<const at_bf16x8 *>(kb + AT_KT * AT_K3_ROWB + c * 32);
         const at_bf16x8 k3 = *reinterpret_cast<const at_bf16x8 *>(kb + 2 * AT_KT * AT_K3_ROWB + c * 32);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k3, q3[c][0], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q3[c][2], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k2, q3[c][1], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k2, q3[c][0], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q3[c][1], s, 0, 0, 0);
+        sl = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k3, q3[c][0], sl, 0, 0, 0);
+        sl = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q3[c][2], sl, 0, 0, 0);
+        sl = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k2, q3[c][1], sl, 0, 0, 0);
+        sl = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k2, q3[c][0], sl, 0, 0, 0);
+        sl = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q3[c][1], sl, 0, 0, 0);
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q3[c][0], s, 0, 0, 0);
       }
+#pragma unroll
+      for (int e = 0; e < 16; e++) s[e] += sl[e];
       return;
     } else {
     f32x16 sb;

@@ -1,6 +1,7 @@
 """CPU restatements of the glue, layout and entropy-index kernels (csrc/misc.hip, csrc/decode.hip, csrc/entropy.hip), built from
 library operations (F.unfold, F.pixel_shuffle, reshape / permute, torch.sort, torch.argmax, torch.clamp, torch.where) and fp64
-arithmetic, not from the kernels' index arithmetic.  tests/test_kernels_ref_cpu.py checks them against each other and against the C
+arithmetic, not from the kernels' index arithmetic (dwconv_ordered32 restates an operation ORDER, in slices of whole tensors).
+tests/test_kernels_ref_cpu.py checks them against each other and against the C
 oracle; tests/test_gpu_kernels.py and tests/test_gpu_kernels_entropy.py compare the kernels with them.  The fp64 attention with
 Swin-shaped bias variants, the window partition and the fp64 3x3 convolution serve tests/test_gpu_attention_rowmap.py,
 tests/test_swin_rowmap_cpu.py and tests/test_gpu_conv_chain.py.
@@ -142,6 +143,25 @@ def gated_lrelu(x):
     a, b = np.split(x.numpy(), 2, axis=1)
     o = np.where(a >= 0, a, np.float32(0.1) * a) + np.where(b >= 0, b, np.float32(0.01) * b)
     return torch.from_numpy(o.astype(np.float32))
+
+
+def dwconv_ordered32(x, w, bias, prescale, k):
+    """depthwise k x k convolution, stride 1, zero padding k // 2, in the kernels' own fp32 operation order, so that dwconv_kernel and
+    dwconv_x4_kernel (csrc/misc.hip, built without contraction) must equal it bit for bit: x (B, H, W, C), w (k*k, C), bias (C) or
+    None, prescale (C) or None.  The accumulator starts at the bias or at +0; taps go in (ky, kx) order; v = x * prescale when a
+    prescale is given; acc = acc + v * w as two rounded operations; taps outside the image are skipped."""
+    B, H, W, C = x.shape
+    pad = k // 2
+    acc = bias.expand(B, H, W, C).clone() if bias is not None else torch.zeros(B, H, W, C)
+    v = x * prescale if prescale is not None else x
+    for ky in range(k):
+        for kx in range(k):
+            dy, dx = ky - pad, kx - pad
+            y0, y1, x0, x1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)
+            if y0 < y1 and x0 < x1:
+                acc[:, y0:y1, x0:x1] = acc[:, y0:y1, x0:x1] + v[:, y0 + dy:y1 + dy, x0 + dx:x1 + dx] * w[ky * k + kx]
+    assert acc.dtype == torch.float32
+    return acc
 
 
 # ---- the 4-step mask and the index builder --------------------------------------------------------------------------------------

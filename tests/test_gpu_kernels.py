@@ -29,9 +29,9 @@ def test_layernorm_vs_torch(M, C, act):
     if M >= 20:
         n = M // 5
         out = torch.zeros(n * 4, C, device=DEV)
-        ops.layernorm(x.to(DEV), w.to(DEV), b.to(DEV), out=out, M=n * 3, x_seg=(3, 5), y_seg=(3, 4))
+        ops.layernorm(x.to(DEV), w.to(DEV), b.to(DEV), out=out, M=n * 3, x_seg=(3, 5), y_seg=(3, 4), act=act)
         o = out.cpu().double().view(n, 4, C)
-        assert float((o[:, :3] - ref.view(-1, C)[:n * 5].view(n, 5, C)[:, :3]).abs().max()) < 2e-5 if act == 0 else True
+        assert float((o[:, :3] - ref.view(-1, C)[:n * 5].view(n, 5, C)[:, :3]).abs().max()) < 2e-5     # ref is silu(ref) when act == 2
         assert float(o[:, 3].abs().max()) == 0.0
 
 

@@ -36,8 +36,10 @@ def test_split_is_exact(ops):
     assert float(d[~big].max()) <= 1e-30
 
 
-@pytest.mark.parametrize("M,N,K", [(256, 256, 4096), (512, 1024, 1024), (289, 768, 768)])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 4096), (512, 1024, 1024), (289, 768, 768), (70, 52, 96)])
 def test_error_not_above_fp32_path(ops, M, N, K):
+    """(70, 52, 96): ragged M and N, three K slices.  The same two assertions on the wide-exponent family, and on inputs the CPU
+    emulation of the arithmetic ran on, are in test_gpu_split3_accuracy.py::test_gemm_error_not_above_fp32_path_shared_inputs."""
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = torch.randn(M, K, device="cuda", generator=g)
     w = torch.randn(N, K, device="cuda", generator=g) * 0.03

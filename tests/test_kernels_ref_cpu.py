@@ -142,3 +142,20 @@ def test_attention_and_conv_refs_against_direct_loops():
         row = (n * 5 + y) * 6 + xx
         assert float((pre[row] - want).abs().max()) < 1e-12
         assert float((out[row] - (want * torch.sigmoid(want) + res[n, :, y, xx].double())).abs().max()) < 1e-12
+
+
+def test_dwconv_ordered_ref_against_fp64_conv2d():
+    """the ordered fp32 restatement is a depthwise convolution: within fp32 rounding of F.conv2d in fp64 for every combination of
+    bias and prescale, an image smaller than the window included.  Bound: each of the k * k taps adds three roundings (prescale,
+    product, sum) of at most 2^-24 of a partial sum that stays below 10: 3 * 10 * 6e-8 < 2e-6 per tap"""
+    g = torch.Generator().manual_seed(4)
+    for (B, H, W, C, k) in [(2, 6, 10, 8, 3), (1, 2, 4, 8, 5), (1, 9, 7, 4, 7), (2, 3, 3, 4, 1)]:
+        x = torch.randn(B, H, W, C, generator=g)
+        w = torch.randn(k * k, C, generator=g)
+        for bias in (None, torch.randn(C, generator=g)):
+            for ps in (None, torch.rand(C, generator=g) + 0.5):
+                got = kr.dwconv_ordered32(x, w, bias, ps, k)
+                xin = (x.double() * ps.double() if ps is not None else x.double()).permute(0, 3, 1, 2)
+                ref = torch.nn.functional.conv2d(xin, w.double().t().reshape(C, 1, k, k), None if bias is None else bias.double(),
+                                                 padding=k // 2, groups=C).permute(0, 2, 3, 1)
+                assert got.shape == ref.shape and float((got.double() - ref).abs().max()) < 2e-6 * k * k, (B, H, W, C, k)
