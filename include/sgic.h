@@ -468,6 +468,48 @@ int sgic_niqe_u8_work_bytes(int B, int H, int W, size_t *bytes);
 int sgic_niqe_u8(const uint8_t *d_img, int B, int H, int W, const double *h_weights, uint8_t *d_work, size_t work_bytes,
                  double *d_stats, double *d_sharp, sgic_stream_t stream);
 
+/* The hand-crafted full-reference measures of evaluate.py --hvs (quality.measure_hvs), all on fp64 luma and
+ * all in fp64.  sgic_hvs_luma_u8: d_img (B, H, W, 3) interleaved RGB -> d_y (B, H, W), Y = (0.299 R + 0.587 G) + 0.114 B on the
+ * 0..255 scale, unrounded, one multiply or add per written operation.  The three measures take the luma planes of the originals
+ * (d_ya) and of the reconstructions (d_yb).  Each reduces a tile (block group) in a workgroup and combines the partials of one image
+ * in a fixed order (no float atomics): the same image gives the same bits whatever batch it comes in.
+ *
+ * sgic_hvs_vifp: pixel-domain VIF with sigma_n^2 = 2.  Scales s = 1..4 with the N x N window N = 2^(5 - s) + 1 (17, 9, 5, 3),
+ * g_i = exp(-(i - N / 2)^2 / (2 (N / 5)^2)) / sum along each axis; for s > 1 both planes are first filtered with that window (valid
+ * support) and every second row and column is kept, starting at 0 (planes kept in d_work).  At every scale, with the same window
+ * and valid support: mu1, mu2, s1 = E[xx] - mu1^2, s2 = E[yy] - mu2^2, s12 = E[xy] - mu1 mu2; then with eps = 1e-10, in this
+ * order: s1, s2 < 0 -> 0; g = s12 / (s1 + eps), sv = s2 - g s12; s1 < eps: g = 0, sv = s2, s1 = 0; s2 < eps: g = 0, sv = 0;
+ * g < 0: sv = s2, g = 0; sv <= eps: sv = eps.  d_out[b] = {sum log10(1 + g^2 s1 / (sv + 2)), sum log10(1 + s1 / 2)} over all
+ * scales and samples; the caller divides.  41 <= H, W: below that scale 4 has no sample.
+ *
+ * sgic_hvs_gmsd: the 2 x 2 mean of Y at every second row and column starting at 0 (samples past the plane count 0: MATLAB's
+ * conv2(Y, ones(2) / 4, 'same') then (1:2:end, 1:2:end)), Prewitt gradients [[1, 0, -1]] x 3 / 3 and its transpose with zero
+ * padding, m = sqrt(gx^2 + gy^2), GMS = (2 m1 m2 + 170) / (m1^2 + m2^2 + 170); d_out[b] = the population standard deviation of
+ * the GMS map, from per-tile (count, mean, sum of squared deviations from the tile's mean) merged pairwise in a fixed order.
+ *
+ * sgic_hvs_psnr: non-overlapping 8 x 8 blocks from the top left (partial blocks ignored), orthonormal DCT-II D of both blocks.
+ * h_q: HOST array, the 64 steps of a quantisation table in natural order, each in 1..255 (T.81 Annex K.1 luminance for the
+ * published measure); MaskCof = (10 / Q)^2, CSFCof = 2.5735088 (10 / Q).  Per image's block: m = sum over the 63 AC coefficients
+ * of D^2 MaskCof; vari(X) = the unbiased variance of X times its element count; pop = vari(block), and where that is not 0,
+ * pop = (sum of vari over the four 4 x 4 quadrants) / pop; mask = sqrt(m pop) / 32, the larger of the two images' masks.
+ * u = |Da - Db|; with masking every AC coefficient has u = 0 where u < mask / MaskCof and u - mask / MaskCof elsewhere; the
+ * block's error is sum (u CSFCof)^2.  d_out[b] = {sum of the block errors without masking (PSNR-HVS), with masking (PSNR-HVS-M)};
+ * the caller divides by 64 (H / 8) (W / 8) and takes 10 log10(255^2 / .).  8 <= H, W.
+ *
+ * d_work: 16-byte aligned, at least the *bytes the measure's _work_bytes call returns (host-only, takes no stream).
+ * 1 <= B <= 65536, H, W <= 16384; anything else, a null pointer, a misaligned or too small workspace is SGIC_EINVAL before any
+ * launch. */
+int sgic_hvs_luma_u8(const uint8_t *d_img, int B, int H, int W, double *d_y, sgic_stream_t stream);
+int sgic_hvs_vifp_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_hvs_vifp(const double *d_ya, const double *d_yb, int B, int H, int W, uint8_t *d_work, size_t work_bytes, double *d_out,
+                  sgic_stream_t stream);
+int sgic_hvs_gmsd_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_hvs_gmsd(const double *d_ya, const double *d_yb, int B, int H, int W, uint8_t *d_work, size_t work_bytes, double *d_out,
+                  sgic_stream_t stream);
+int sgic_hvs_psnr_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_hvs_psnr(const double *d_ya, const double *d_yb, int B, int H, int W, const int *h_q, uint8_t *d_work, size_t work_bytes,
+                  double *d_out, sgic_stream_t stream);
+
 /* LPIPS with the VGG16 trunk (lpips.LpipsVGG, evaluate.py --lpips_ckpt; the reference's taming/modules/losses/lpips.py): the
  * memory-bound glue around sgic_conv3x3_split3_f32, which runs the thirteen convolutions.  All planes are slice-major (a_packed = 1).
  *

@@ -24,6 +24,14 @@ lib.sgic_quality_u8.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_
 # sgic_niqe_u8 (csrc/niqe.hip): (d_img, B, H, W, h_weights, d_work, work_bytes, d_stats, d_sharp, stream)
 lib.sgic_niqe_u8_work_bytes.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_niqe_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
+# csrc/hvs.hip: sgic_hvs_luma_u8 (d_img, B, H, W, d_y, stream); sgic_hvs_{vifp,gmsd} (d_ya, d_yb, B, H, W, d_work, work_bytes, d_out,
+# stream); sgic_hvs_psnr the same with h_q in front of d_work
+lib.sgic_hvs_luma_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+for _m in ("vifp", "gmsd", "psnr"):
+    getattr(lib, f"sgic_hvs_{_m}_work_bytes").argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
+lib.sgic_hvs_vifp.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+lib.sgic_hvs_gmsd.argtypes = lib.sgic_hvs_vifp.argtypes
+lib.sgic_hvs_psnr.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
 # sgic_jpeg_encode_batch (csrc/jpeg_enc.hip): (d_rgb, B, H, W, subsampling, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, stream)
 lib.sgic_jpeg_encode_cap.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_jpeg_encode_work_bytes.argtypes = [c_int, c_int, c_int, c_int, C.POINTER(c_size_t)]
@@ -105,7 +113,8 @@ _NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profil
               "sgic_search_codes_f32q_work_bytes", "sgic_search_rank_work_bytes", "sgic_assign_codes_f32c_work_bytes", "sgic_quality_u8_work_bytes", "sgic_jpeg_encode_cap",
               "sgic_jpeg_encode_work_bytes", "sgic_jpeg_encode_opt_cap", "sgic_jpeg_encode_opt_work_bytes", "sgic_jpeg_encode_prog_cap",
               "sgic_jpeg_encode_prog_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes",
-              "sgic_niqe_u8_work_bytes", "sgic_resize_u8_coeffs"}
+              "sgic_niqe_u8_work_bytes", "sgic_resize_u8_coeffs", "sgic_hvs_vifp_work_bytes", "sgic_hvs_gmsd_work_bytes",
+              "sgic_hvs_psnr_work_bytes"}
 
 
 def call(name, *args):

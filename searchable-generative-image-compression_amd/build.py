@@ -13,10 +13,12 @@ LIB = os.path.join(HERE, "libsgic.so")
 # equality; the DISTS head needs x == y to give exactly 0.  lpips_alex.hip: the same input layer, compared the same way.  fid.hip: its
 # producers and pools are compared for equality, its resize and Gram with restatements that have no fma.  niqe.hip: the sign of its
 # MSCN samples (a sum of ten products) has to be the CPU restatement's, which has no fma.  resize.hip: the double arithmetic of Pillow's
-# coefficient tables (pil_resample.h, shared with misc.hip) must stay single operations.
+# coefficient tables (pil_resample.h, shared with misc.hip) must stay single operations.  hvs.hip: its luma has to be the CPU
+# restatement's bits (identical and constant images give the special values exactly), its maps are compared with a restatement
+# that has no fma.
 FLAGS = {"entropy.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "quality.hip": ["-ffp-contract=off"],
          "lpips.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "lpips_alex.hip": ["-ffp-contract=off"], "fid.hip": ["-ffp-contract=off"],
-         "niqe.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"]}
+         "niqe.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"], "hvs.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src_list, out):

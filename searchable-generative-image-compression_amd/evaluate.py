@@ -57,6 +57,13 @@
                                                                 usable 96 x 96 blocks; P: the pristine model, an .npz with
                                                                 mu_pris_param and cov_pris_param (BasicSR's file, or the output of
                                                                 `python -m sgic_amd.niqe fit`) or MATLAB's .mat
+  evaluate.py ... --hvs                                         adds "vifp", "gmsd", "psnr_hvs" and "psnr_hvs_m" to every record and
+                                                                to its anchor, directly after "ms_ssim_db", and their means to the
+                                                                summary ("anchor_*" with an anchor): pixel-domain VIF, gradient
+                                                                magnitude similarity deviation and PSNR-HVS / PSNR-HVS-M on fp64 luma
+                                                                (quality.measure_hvs); they need no file.  An image too small for a
+                                                                measure (VIFp: a side below 41; PSNR-HVS: below 8) carries null there
+                                                                and is counted in the summary's "hvs_skipped"
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -69,6 +76,8 @@ from glob import glob
 
 import numpy as np
 import torch
+
+from .quality import HVS_FIELDS      # --hvs: directly after FIELDS, in a record and in its anchor
 
 torch.set_grad_enabled(False)
 
@@ -104,8 +113,9 @@ def _json_number(v):
 
 def summarise(records, fid_sets=None, clip_sets=None):
     """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
-    lpips, lpips_alex and dists when the records carry them; clip_sets (ClipSets, --clip_ckpt): its keys after the perceptual means
-    (the anchor's after the anchor's); fid_sets (FidSets, --fid_ckpt): its keys after all the others"""
+    vifp, gmsd, psnr_hvs, psnr_hvs_m (finite values) and the count hvs_skipped of records with a null among them when the records
+    carry them (--hvs); the mean of lpips, lpips_alex and dists when the records carry them; clip_sets (ClipSets, --clip_ckpt): its
+    keys after the perceptual means (the anchor's after the anchor's); fid_sets (FidSets, --fid_ckpt): its keys after all the others"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
     ms = mean([r["ms_ssim"] for r in records if r["ms_ssim"] is not None])
@@ -113,6 +123,10 @@ def summarise(records, fid_sets=None, clip_sets=None):
         db = None if ms is None else float(0.0 - 10.0 * np.log10(1.0 - ms))
     out = {"images": len(records), "bpp": mean([r["bpp"] for r in records if r["bpp"] is not None]),
            "psnr": mean([r["psnr"] for r in records if isinstance(r["psnr"], float)]), "ms_ssim": ms, "ms_ssim_db": _json_number(db)}
+    if any("vifp" in r for r in records):
+        for k in HVS_FIELDS:
+            out[k] = mean([r[k] for r in records if isinstance(r.get(k), float)])
+        out["hvs_skipped"] = sum(1 for r in records if any(r.get(k) is None for k in HVS_FIELDS))
     for k in PAIR_METRICS:
         if any(k in r for r in records):
             out[k] = mean([r[k] for r in records if r.get(k) is not None])
@@ -129,6 +143,9 @@ def summarise(records, fid_sets=None, clip_sets=None):
         out.update({"anchor_bpp": mean([a["bpp"] for a in anchors]),
                     "anchor_psnr": mean([a["psnr"] for a in anchors if isinstance(a["psnr"], float)]), "anchor_ms_ssim": ams,
                     "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
+        if any("vifp" in a for a in anchors):
+            for k in HVS_FIELDS:
+                out["anchor_" + k] = mean([a[k] for a in anchors if isinstance(a.get(k), float)])
         for k in PAIR_METRICS:
             if any(k in a for a in anchors):
                 out["anchor_" + k] = mean([a[k] for a in anchors if a.get(k) is not None])
@@ -264,7 +281,8 @@ def choose_scale(candidates):
     return min(range(len(candidates)), key=lambda i: (candidates[i][2], i))
 
 
-def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None, optimize=False, scales=None):
+def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None, optimize=False, scales=None,
+                 hvs=False):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
@@ -277,7 +295,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
     with Lanczos (ops.resize_u8; r = 1: the image as it is), picked and encoded as above against the same budgets, decoded, enlarged
     to (H, W) with bicubic and measured; every image keeps the scale choose_scale names.  The records then carry "scale",
     "coded_height" and "coded_width" after "subsampling" ("optimize"); "bytes" is the reduced file and "bpp" counts the original's
-    pixels."""
+    pixels.
+    hvs: every record also carries HVS_FIELDS (quality.measure_hvs of the decoded anchor), directly after FIELDS."""
     from . import jpeg, ops, quality
     from .resize import reduced_size
     B, H, W, _ = a_u8.shape
@@ -303,6 +322,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
     if decoded_out is not None:
         decoded_out.append(decoded)
     m = quality.measure(a_u8, decoded)
+    if hvs:
+        m.update(quality.measure_hvs(a_u8, decoded))
     pm = [(k, model.measure(a_u8, decoded)) for k, model in pair_metrics]
     out = []
     for j, ((q, over), data) in enumerate(zip(picks, files)):
@@ -314,7 +335,7 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
         if coded is not None:
             rec.update({"scale": coded[j][0], "coded_height": coded[j][1][0], "coded_width": coded[j][1][1]})
         rec.update({"bytes": len(data), "bpp": 8 * len(data) / (H * W)})
-        for k in FIELDS:
+        for k in FIELDS + (HVS_FIELDS if hvs else ()):
             rec[k] = None if m[k] is None else _json_number(m[k][j])
         for k, v in pm:
             rec[k] = None if v is None else float(v[0][j])
@@ -358,6 +379,8 @@ def main(argv=None):
     ap.add_argument("--niqe_params", type=str, default=None,
                     help="the pristine model of NIQE (.npz with mu_pris_param, cov_pris_param, or .mat): adds \"niqe\" and \"niqe_orig\" "
                          "to every record")
+    ap.add_argument("--hvs", action="store_true",
+                    help="add \"vifp\", \"gmsd\", \"psnr_hvs\" and \"psnr_hvs_m\" (luma measures that need no file) to every record")
     ap.add_argument("--fid_patch", type=int, default=256,
                     help="side of the windows FID and KID are computed on (the HiFiC protocol); 0: whole images")
     args = ap.parse_args(argv)
@@ -438,11 +461,13 @@ def main(argv=None):
             a = torch.from_numpy(np.stack([m[1] for m in members])).to(dev)
             b = torch.stack([m[2] for m in members])
             m = quality.measure(a, b)
+            if args.hvs:
+                m.update(quality.measure_hvs(a, b))
             pm = [(k, model.measure(a, b)) for k, model in pair_metrics]
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
             decoded = [] if fid_sets is not None or clip_sets is not None or niqe_model is not None else None
             anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded, args.anchor_optimize,
-                                   args.anchor_scales) if anchor else None
+                                   args.anchor_scales, args.hvs) if anchor else None
             if clip_sets is not None:
                 from .search import embedded_clip_codes
                 ua, qa = clip_sets.embed(a)
@@ -464,7 +489,7 @@ def main(argv=None):
             for j, (stem, _, _) in enumerate(members):
                 nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
-                for k in FIELDS:
+                for k in FIELDS + (HVS_FIELDS if args.hvs else ()):
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
                 for k, v in pm:
                     rec[k] = None if v is None else float(v[0][j])

@@ -1334,6 +1334,51 @@ def niqe_blocks_u8(x):
     return stats, sharp
 
 
+def hvs_luma_u8(x):
+    """x (B, H, W, 3) u8 RGB, contiguous -> (B, H, W) float64 on x's device: Y = 0.299 R + 0.587 G + 0.114 B on the 0..255 scale,
+    unrounded (csrc/hvs.hip), what the three measures below take.  No synchronisation."""
+    require_gpu()
+    assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and x.dim() == 4 and x.shape[3] == 3
+    B, H, W, _ = x.shape
+    y = torch.empty(B, H, W, dtype=torch.float64, device=x.device)
+    call("sgic_hvs_luma_u8", _p(x), B, H, W, _p(y))
+    return y
+
+
+def _hvs_measure(name, ya, yb, out_cols, *extra):
+    require_gpu()
+    for t in (ya, yb):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == ya.device
+    assert ya.dim() == 3 and ya.shape == yb.shape
+    B, H, W = ya.shape
+    nbytes = ctypes.c_size_t(0)
+    call(f"sgic_hvs_{name}_work_bytes", B, H, W, ctypes.byref(nbytes))
+    work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=ya.device)
+    out = torch.empty((B, out_cols) if out_cols else (B,), dtype=torch.float64, device=ya.device)
+    call(f"sgic_hvs_{name}", _p(ya), _p(yb), B, H, W, *extra, _p(work), ctypes.c_size_t(nbytes.value), _p(out))
+    return out
+
+
+def hvs_vifp(ya, yb):
+    """the two sums of pixel-domain VIF (csrc/hvs.hip): ya (original), yb (reconstruction) (B, H, W) float64
+    luma, min(H, W) >= 41 -> (B, 2) float64 {numerator, denominator} over the four scales.  No synchronisation."""
+    return _hvs_measure("vifp", ya, yb, 2)
+
+
+def hvs_gmsd(ya, yb):
+    """gradient magnitude similarity deviation of B luma pairs (csrc/hvs.hip) -> (B,) float64.  No synchronisation."""
+    return _hvs_measure("gmsd", ya, yb, 0)
+
+
+def hvs_psnr(ya, yb, q):
+    """the block error sums of PSNR-HVS and PSNR-HVS-M (csrc/hvs.hip): (B, H, W) float64 luma pairs, min(H, W) >= 8; q: the 64 steps
+    of the luminance quantisation table, natural order -> (B, 2) float64 {without masking, with masking}, summed over the
+    (H // 8) (W // 8) whole blocks.  No synchronisation."""
+    q = np.ascontiguousarray(q, dtype=np.int32)
+    assert q.shape == (64,)
+    return _hvs_measure("psnr", ya, yb, 2, q)
+
+
 def _input_halo(symbol, img_u8, hp, image_offset):
     require_gpu()
     assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3

@@ -38,3 +38,90 @@ def measure(a_u8, b_u8):
     from . import ops
     sse, levels = ops.quality_u8(a_u8.contiguous(), b_u8.contiguous())
     return combine(sse.cpu().numpy(), levels.cpu().numpy(), H, W)
+
+
+# The hand-crafted full-reference measures on luma (evaluate.py --hvs; csrc/hvs.hip)
+
+HVS_FIELDS = ("vifp", "gmsd", "psnr_hvs", "psnr_hvs_m")
+VIFP_WINDOWS = (17, 9, 5, 3)      # N = 2^(4 - s + 1) + 1 of the scales s = 1..4
+PSNR_HVS_MIN_SIDE = 8             # one whole 8 x 8 block
+
+
+def _vifp_min_side():
+    """the smallest side at which scale 4 has one valid sample, from the window arithmetic: scale s > 1 keeps every second sample
+    of the valid filter output of scale s - 1 (n -> ceil((n - N + 1) / 2)), and every scale needs n >= N for its statistics"""
+    def fits(n):
+        for s, N in enumerate(VIFP_WINDOWS):
+            if s and n >= N:
+                n = (n - N + 2) // 2
+            if n < N:
+                return False
+        return True
+    n = 1
+    while not fits(n):
+        n += 1
+    return n
+
+
+VIFP_MIN_SIDE = _vifp_min_side()      # 41
+
+
+def _luma_pair(a_u8, b_u8):
+    import torch
+    from . import ops
+    assert a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.shape == b_u8.shape
+    assert a_u8.dim() == 4 and a_u8.shape[3] == 3 and a_u8.shape[0] >= 1
+    return ops.hvs_luma_u8(a_u8.contiguous()), ops.hvs_luma_u8(b_u8.contiguous())
+
+
+def _vifp(ya, yb):
+    from . import ops
+    H, W = ya.shape[1:]
+    if min(H, W) < VIFP_MIN_SIDE:
+        raise ValueError(f"VIFp needs both sides >= {VIFP_MIN_SIDE} (scale 4 has no valid sample below that), got {H} x {W}")
+    sums = ops.hvs_vifp(ya, yb)
+    equal = (ya == yb).flatten(1).all(dim=1).cpu().numpy()
+    sums = sums.cpu().numpy()
+    num, den = sums[:, 0], sums[:, 1]
+    with np.errstate(divide="ignore", invalid="ignore"):      # a flat original carries no information: 1 for equal images, else 0
+        return np.where(den == 0.0, np.where(equal, 1.0, 0.0), num / den)
+
+
+def _psnr_hvs(ya, yb):
+    from . import ops
+    from .jpeg_enc import _LUMA
+    H, W = ya.shape[1:]
+    if min(H, W) < PSNR_HVS_MIN_SIDE:
+        raise ValueError(f"PSNR-HVS needs both sides >= {PSNR_HVS_MIN_SIDE} (one whole 8 x 8 block), got {H} x {W}")
+    sums = ops.hvs_psnr(ya, yb, _LUMA).cpu().numpy()
+    with np.errstate(divide="ignore"):      # equal images: inf, as "psnr"
+        db = 10.0 * np.log10(65025.0 / (sums / (64.0 * (H // 8) * (W // 8))))
+    return db[:, 0], db[:, 1]
+
+
+def vifp(a_u8, b_u8):
+    """pixel-domain VIF of B pairs: a_u8 (original), b_u8 (reconstruction) (B, H, W, 3) u8 CUDA tensors -> float64 (B,).
+    ValueError for images with a side below VIFP_MIN_SIDE."""
+    return _vifp(*_luma_pair(a_u8, b_u8))
+
+
+def gmsd(a_u8, b_u8):
+    """gradient magnitude similarity deviation of B pairs -> float64 (B,); 0 for equal images"""
+    from . import ops
+    return ops.hvs_gmsd(*_luma_pair(a_u8, b_u8)).cpu().numpy()
+
+
+def psnr_hvs(a_u8, b_u8):
+    """-> (psnr_hvs, psnr_hvs_m): float64 (B,) each, inf for equal images.  ValueError for images with a side below 8."""
+    return _psnr_hvs(*_luma_pair(a_u8, b_u8))
+
+
+def measure_hvs(a_u8, b_u8):
+    """the three measures from one luma plane per image -> {"vifp", "gmsd", "psnr_hvs", "psnr_hvs_m"}: float64 (B,), or None for
+    a measure the images are too small for (vifp below VIFP_MIN_SIDE, psnr_hvs and psnr_hvs_m below 8), as measure() does"""
+    from . import ops
+    ya, yb = _luma_pair(a_u8, b_u8)
+    side = min(ya.shape[1:])
+    hvs, hvs_m = _psnr_hvs(ya, yb) if side >= PSNR_HVS_MIN_SIDE else (None, None)
+    return {"vifp": _vifp(ya, yb) if side >= VIFP_MIN_SIDE else None, "gmsd": ops.hvs_gmsd(ya, yb).cpu().numpy(),
+            "psnr_hvs": hvs, "psnr_hvs_m": hvs_m}
