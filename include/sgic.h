@@ -510,6 +510,34 @@ int sgic_hvs_psnr_work_bytes(int B, int H, int W, size_t *bytes);
 int sgic_hvs_psnr(const double *d_ya, const double *d_yb, int B, int H, int W, const int *h_q, uint8_t *d_work, size_t work_bytes,
                   double *d_out, sgic_stream_t stream);
 
+/* FSIM and FSIMc of evaluate.py --fsim (quality.fsim; DESIGN.md section 21 holds the definition), all in fp64.
+ *
+ * sgic_fsim_planes_u8: d_img (B, H, W, 3) interleaved RGB -> d_out (B, 3, h, w), the reduced Y, I, Q planes: Y = (0.299 R + 0.587 G)
+ * + 0.114 B, I = (0.596 R - 0.274 G) - 0.322 B, Q = (0.211 R - 0.523 G) + 0.312 B, unrounded; with F = max(1, floor(min(H, W) /
+ * 256 + 0.5)), h = ceil(H / F), w = ceil(W / F), sample (i, j) is the sum over input rows i F + F / 2 - F + 1 .. i F + F / 2 and the
+ * same columns (samples outside count 0), added row by row from the lowest offset, divided by F F.
+ *
+ * sgic_fsim_phasecong: d_planes (B, h, w) -> d_pc (B, h, w), the phase congruency map of every plane (four scales, four
+ * orientations, log-Gabor filters built on the device, the 2-D transforms as dense DFT passes with twiddles from a table indexed by
+ * (j k) mod n, the noise threshold from the exact median of |EO_0|^2 by a radix select); a plane with max == min gives 0
+ * everywhere and no transform runs.  2 <= h, w <= 2048.  Planes are transformed in chunks, so the workspace stays near 512 MiB
+ * (one plane's scratch, 368 h w bytes, where that is more).
+ *
+ * sgic_fsim: d_a (originals), d_b (reconstructions) (B, H, W, 3) -> d_fsim[B], d_fsimc[B]: the reduced planes, the PC maps of
+ * both Y planes, Scharr gradient magnitudes, and sum(Spc Sg PCm) / sum(PCm) without and with the chroma term.  Tile partials are
+ * combined per pair in a fixed order (no float atomics): a pair gives the same bits whatever batch and slot it comes in.  Where
+ * sum(PCm) is 0 both values are 1 if the reduced planes of the two images are equal, else 0.  2 <= H, W and max(h, w) <= 2048.
+ *
+ * d_work: 16-byte aligned, at least the *bytes the _work_bytes call returns (host-only, takes no stream).  1 <= B <= 65536,
+ * H, W <= 16384; anything else, a null pointer, a misaligned or too small workspace is SGIC_EINVAL before any launch. */
+int sgic_fsim_planes_u8(const uint8_t *d_img, int B, int H, int W, double *d_out, sgic_stream_t stream);
+int sgic_fsim_phasecong_work_bytes(int B, int h, int w, size_t *bytes);
+int sgic_fsim_phasecong(const double *d_planes, int B, int h, int w, uint8_t *d_work, size_t work_bytes, double *d_pc,
+                        sgic_stream_t stream);
+int sgic_fsim_work_bytes(int B, int H, int W, size_t *bytes);
+int sgic_fsim(const uint8_t *d_a, const uint8_t *d_b, int B, int H, int W, uint8_t *d_work, size_t work_bytes, double *d_fsim,
+              double *d_fsimc, sgic_stream_t stream);
+
 /* LPIPS with the VGG16 trunk (lpips.LpipsVGG, evaluate.py --lpips_ckpt; the reference's taming/modules/losses/lpips.py): the
  * memory-bound glue around sgic_conv3x3_split3_f32, which runs the thirteen convolutions.  All planes are slice-major (a_packed = 1).
  *

@@ -32,6 +32,13 @@ for _m in ("vifp", "gmsd", "psnr"):
 lib.sgic_hvs_vifp.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
 lib.sgic_hvs_gmsd.argtypes = lib.sgic_hvs_vifp.argtypes
 lib.sgic_hvs_psnr.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+# csrc/fsim.hip: sgic_fsim_planes_u8 (d_img, B, H, W, d_out, stream); sgic_fsim_phasecong (d_planes, B, h, w, d_work, work_bytes, d_pc,
+# stream); sgic_fsim (d_a, d_b, B, H, W, d_work, work_bytes, d_fsim, d_fsimc, stream)
+lib.sgic_fsim_planes_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.sgic_fsim_phasecong_work_bytes.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
+lib.sgic_fsim_work_bytes.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
+lib.sgic_fsim_phasecong.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+lib.sgic_fsim.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
 # sgic_jpeg_encode_batch (csrc/jpeg_enc.hip): (d_rgb, B, H, W, subsampling, h_qt, d_work, work_bytes, d_out, cap, d_len, d_err, stream)
 lib.sgic_jpeg_encode_cap.argtypes = [c_int, c_int, c_int, C.POINTER(c_size_t)]
 lib.sgic_jpeg_encode_work_bytes.argtypes = [c_int, c_int, c_int, c_int, C.POINTER(c_size_t)]
@@ -114,7 +121,7 @@ _NO_STREAM = {"sgic_pmf_to_quantized_cdf", "sgic_cdf_table_create", "sgic_profil
               "sgic_jpeg_encode_work_bytes", "sgic_jpeg_encode_opt_cap", "sgic_jpeg_encode_opt_work_bytes", "sgic_jpeg_encode_prog_cap",
               "sgic_jpeg_encode_prog_work_bytes", "sgic_lpips_head_work_bytes", "sgic_dists_moments_work_bytes",
               "sgic_niqe_u8_work_bytes", "sgic_resize_u8_coeffs", "sgic_hvs_vifp_work_bytes", "sgic_hvs_gmsd_work_bytes",
-              "sgic_hvs_psnr_work_bytes"}
+              "sgic_hvs_psnr_work_bytes", "sgic_fsim_work_bytes", "sgic_fsim_phasecong_work_bytes"}
 
 
 def call(name, *args):

@@ -15,10 +15,12 @@ LIB = os.path.join(HERE, "libsgic.so")
 # MSCN samples (a sum of ten products) has to be the CPU restatement's, which has no fma.  resize.hip: the double arithmetic of Pillow's
 # coefficient tables (pil_resample.h, shared with misc.hip) must stay single operations.  hvs.hip: its luma has to be the CPU
 # restatement's bits (identical and constant images give the special values exactly), its maps are compared with a restatement
-# that has no fma.
+# that has no fma.  fsim.hip: its reduced Y / I / Q planes have to be the CPU restatement's bits and equal images have to give exactly
+# 1; the tap loops of its transform ask for fma by name.
 FLAGS = {"entropy.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "quality.hip": ["-ffp-contract=off"],
          "lpips.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "lpips_alex.hip": ["-ffp-contract=off"], "fid.hip": ["-ffp-contract=off"],
-         "niqe.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"], "hvs.hip": ["-ffp-contract=off"]}
+         "niqe.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"], "hvs.hip": ["-ffp-contract=off"],
+         "fsim.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src_list, out):

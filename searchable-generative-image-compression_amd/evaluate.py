@@ -64,6 +64,13 @@
                                                                 (quality.measure_hvs); they need no file.  An image too small for a
                                                                 measure (VIFp: a side below 41; PSNR-HVS: below 8) carries null there
                                                                 and is counted in the summary's "hvs_skipped"
+  evaluate.py ... --fsim                                        adds "fsim" and "fsimc" to every record and to its anchor, directly
+                                                                after "ms_ssim_db" (after "psnr_hvs_m" with --hvs), and their means
+                                                                to the summary ("anchor_*" with an anchor): the feature similarity
+                                                                index on phase congruency and gradient magnitude, and its colour
+                                                                variant with the I / Q chroma term (quality.fsim); they need no
+                                                                file.  An image FSIM refuses (a side below 2, a reduced longer side
+                                                                above 2048) carries null and is counted in "fsim_skipped"
 
 One JSON line per image, sorted by name, to --out (default: stdout); a summary line to stderr, which is also the last line of --out.
 Originals and reconstructions are matched by file stem."""
@@ -77,7 +84,7 @@ from glob import glob
 import numpy as np
 import torch
 
-from .quality import HVS_FIELDS      # --hvs: directly after FIELDS, in a record and in its anchor
+from .quality import FSIM_FIELDS, HVS_FIELDS      # --hvs, then --fsim: directly after FIELDS, in a record and in its anchor
 
 torch.set_grad_enabled(False)
 
@@ -114,7 +121,7 @@ def _json_number(v):
 def summarise(records, fid_sets=None, clip_sets=None):
     """the summary line: count and the fp64 means of bpp, psnr (finite values), ms_ssim; ms_ssim_db of the mean ms_ssim; the mean of
     vifp, gmsd, psnr_hvs, psnr_hvs_m (finite values) and the count hvs_skipped of records with a null among them when the records
-    carry them (--hvs); the mean of lpips, lpips_alex and dists when the records carry them; clip_sets (ClipSets, --clip_ckpt): its
+    carry them (--hvs); the mean of fsim, fsimc and the count fsim_skipped likewise (--fsim); the mean of lpips, lpips_alex and dists when the records carry them; clip_sets (ClipSets, --clip_ckpt): its
     keys after the perceptual means (the anchor's after the anchor's); fid_sets (FidSets, --fid_ckpt): its keys after all the others"""
     def mean(vals):
         return float(np.mean(np.array(vals, dtype=np.float64))) if vals else None
@@ -127,6 +134,10 @@ def summarise(records, fid_sets=None, clip_sets=None):
         for k in HVS_FIELDS:
             out[k] = mean([r[k] for r in records if isinstance(r.get(k), float)])
         out["hvs_skipped"] = sum(1 for r in records if any(r.get(k) is None for k in HVS_FIELDS))
+    if any("fsim" in r for r in records):
+        for k in FSIM_FIELDS:
+            out[k] = mean([r[k] for r in records if isinstance(r.get(k), float)])
+        out["fsim_skipped"] = sum(1 for r in records if any(r.get(k) is None for k in FSIM_FIELDS))
     for k in PAIR_METRICS:
         if any(k in r for r in records):
             out[k] = mean([r[k] for r in records if r.get(k) is not None])
@@ -145,6 +156,9 @@ def summarise(records, fid_sets=None, clip_sets=None):
                     "anchor_ms_ssim_db": _json_number(adb), "anchor_over_rate": sum(1 for a in anchors if a["over_rate"])})
         if any("vifp" in a for a in anchors):
             for k in HVS_FIELDS:
+                out["anchor_" + k] = mean([a[k] for a in anchors if isinstance(a.get(k), float)])
+        if any("fsim" in a for a in anchors):
+            for k in FSIM_FIELDS:
                 out["anchor_" + k] = mean([a[k] for a in anchors if isinstance(a.get(k), float)])
         for k in PAIR_METRICS:
             if any(k in a for a in anchors):
@@ -282,7 +296,7 @@ def choose_scale(candidates):
 
 
 def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=(), decoded_out=None, optimize=False, scales=None,
-                 hvs=False):
+                 hvs=False, fsim=False):
     """the JPEG anchors of a batch of originals: a_u8 (B, H, W, 3) u8 on the device, budgets: the container size of every image in
     bytes (None: unknown) -> list of B anchor records.  Without fixed_quality every image is encoded at the qualities of
     jpeg_enc.LADDER and jpeg_enc.pick_quality takes the largest quality whose whole file fits the budget; the chosen files are decoded
@@ -296,7 +310,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
     to (H, W) with bicubic and measured; every image keeps the scale choose_scale names.  The records then carry "scale",
     "coded_height" and "coded_width" after "subsampling" ("optimize"); "bytes" is the reduced file and "bpp" counts the original's
     pixels.
-    hvs: every record also carries HVS_FIELDS (quality.measure_hvs of the decoded anchor), directly after FIELDS."""
+    hvs: every record also carries HVS_FIELDS (quality.measure_hvs of the decoded anchor), directly after FIELDS.
+    fsim: and FSIM_FIELDS (quality.measure_fsim) after those."""
     from . import jpeg, ops, quality
     from .resize import reduced_size
     B, H, W, _ = a_u8.shape
@@ -324,6 +339,8 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
     m = quality.measure(a_u8, decoded)
     if hvs:
         m.update(quality.measure_hvs(a_u8, decoded))
+    if fsim:
+        m.update(quality.measure_fsim(a_u8, decoded))
     pm = [(k, model.measure(a_u8, decoded)) for k, model in pair_metrics]
     out = []
     for j, ((q, over), data) in enumerate(zip(picks, files)):
@@ -335,7 +352,7 @@ def jpeg_anchors(a_u8, budgets, subsampling, fixed_quality=None, pair_metrics=()
         if coded is not None:
             rec.update({"scale": coded[j][0], "coded_height": coded[j][1][0], "coded_width": coded[j][1][1]})
         rec.update({"bytes": len(data), "bpp": 8 * len(data) / (H * W)})
-        for k in FIELDS + (HVS_FIELDS if hvs else ()):
+        for k in FIELDS + (HVS_FIELDS if hvs else ()) + (FSIM_FIELDS if fsim else ()):
             rec[k] = None if m[k] is None else _json_number(m[k][j])
         for k, v in pm:
             rec[k] = None if v is None else float(v[0][j])
@@ -381,6 +398,9 @@ def main(argv=None):
                          "to every record")
     ap.add_argument("--hvs", action="store_true",
                     help="add \"vifp\", \"gmsd\", \"psnr_hvs\" and \"psnr_hvs_m\" (luma measures that need no file) to every record")
+    ap.add_argument("--fsim", action="store_true",
+                    help="add \"fsim\" and \"fsimc\" (feature similarity on phase congruency, without and with chroma; no file needed) "
+                         "to every record")
     ap.add_argument("--fid_patch", type=int, default=256,
                     help="side of the windows FID and KID are computed on (the HiFiC protocol); 0: whole images")
     args = ap.parse_args(argv)
@@ -463,11 +483,13 @@ def main(argv=None):
             m = quality.measure(a, b)
             if args.hvs:
                 m.update(quality.measure_hvs(a, b))
+            if args.fsim:
+                m.update(quality.measure_fsim(a, b))
             pm = [(k, model.measure(a, b)) for k, model in pair_metrics]
             sizes = [os.path.getsize(containers[stem]) if stem in containers else None for stem, _, _ in members]
             decoded = [] if fid_sets is not None or clip_sets is not None or niqe_model is not None else None
             anchors = jpeg_anchors(a, sizes, args.anchor_subsampling, args.anchor_quality, pair_metrics, decoded, args.anchor_optimize,
-                                   args.anchor_scales, args.hvs) if anchor else None
+                                   args.anchor_scales, args.hvs, args.fsim) if anchor else None
             if clip_sets is not None:
                 from .search import embedded_clip_codes
                 ua, qa = clip_sets.embed(a)
@@ -489,7 +511,7 @@ def main(argv=None):
             for j, (stem, _, _) in enumerate(members):
                 nbytes = sizes[j]
                 rec = {"name": stem, "height": H, "width": W, "bytes": nbytes, "bpp": None if nbytes is None else 8 * nbytes / (H * W)}
-                for k in FIELDS + (HVS_FIELDS if args.hvs else ()):
+                for k in FIELDS + (HVS_FIELDS if args.hvs else ()) + (FSIM_FIELDS if args.fsim else ()):
                     rec[k] = None if m[k] is None else _json_number(m[k][j])
                 for k, v in pm:
                     rec[k] = None if v is None else float(v[0][j])

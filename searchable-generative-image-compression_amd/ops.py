@@ -1379,6 +1379,51 @@ def hvs_psnr(ya, yb, q):
     return _hvs_measure("psnr", ya, yb, 2, q)
 
 
+def fsim_planes_u8(x):
+    """x (B, H, W, 3) u8 RGB, contiguous -> (B, 3, h, w) float64: the reduced Y, I, Q planes FSIM works on (csrc/fsim.hip; DESIGN.md
+    section 21; (h, w) as quality.fsim_reduction says).  No synchronisation."""
+    require_gpu()
+    assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and x.dim() == 4 and x.shape[3] == 3
+    from .quality import fsim_reduction
+    B, H, W, _ = x.shape
+    _, h, w = fsim_reduction(H, W)
+    out = torch.empty(B, 3, h, w, dtype=torch.float64, device=x.device)
+    call("sgic_fsim_planes_u8", _p(x), B, H, W, _p(out))
+    return out
+
+
+def _work(name, device, *dims):
+    nbytes = ctypes.c_size_t(0)
+    call(name, *dims, ctypes.byref(nbytes))
+    return torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=device), ctypes.c_size_t(nbytes.value)
+
+
+def fsim_phasecong(planes):
+    """planes (B, h, w) float64, 2 <= h, w <= 2048 -> (B, h, w) float64: the phase congruency map of every plane (csrc/fsim.hip:
+    dense fp64 DFT passes, the noise threshold from an exact median); 0 everywhere for a constant plane.  No synchronisation."""
+    require_gpu()
+    assert planes.is_cuda and planes.dtype == torch.float64 and planes.is_contiguous() and planes.dim() == 3
+    B, h, w = planes.shape
+    work, nbytes = _work("sgic_fsim_phasecong_work_bytes", planes.device, B, h, w)
+    pc = torch.empty_like(planes)
+    call("sgic_fsim_phasecong", _p(planes), B, h, w, _p(work), nbytes, _p(pc))
+    return pc
+
+
+def fsim(a, b):
+    """a (originals), b (reconstructions) (B, H, W, 3) u8 RGB, contiguous -> (fsim, fsimc): (B,) float64 each (csrc/fsim.hip).
+    No synchronisation."""
+    require_gpu()
+    for t in (a, b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a.device
+    assert a.dim() == 4 and a.shape[3] == 3 and a.shape == b.shape
+    B, H, W, _ = a.shape
+    work, nbytes = _work("sgic_fsim_work_bytes", a.device, B, H, W)
+    out = torch.empty(2, B, dtype=torch.float64, device=a.device)
+    call("sgic_fsim", _p(a), _p(b), B, H, W, _p(work), nbytes, _p(out[0]), _p(out[1]))
+    return out[0], out[1]
+
+
 def _input_halo(symbol, img_u8, hp, image_offset):
     require_gpu()
     assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 4 and img_u8.shape[3] == 3

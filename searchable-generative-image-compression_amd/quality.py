@@ -125,3 +125,57 @@ def measure_hvs(a_u8, b_u8):
     hvs, hvs_m = _psnr_hvs(ya, yb) if side >= PSNR_HVS_MIN_SIDE else (None, None)
     return {"vifp": _vifp(ya, yb) if side >= VIFP_MIN_SIDE else None, "gmsd": ops.hvs_gmsd(ya, yb).cpu().numpy(),
             "psnr_hvs": hvs, "psnr_hvs_m": hvs_m}
+
+
+# FSIM and FSIMc (evaluate.py --fsim; csrc/fsim.hip)
+
+FSIM_FIELDS = ("fsim", "fsimc")
+FSIM_MIN_SIDE = 2                 # the frequency grid of an odd axis divides by n - 1
+FSIM_MAX_REDUCED_SIDE = 2048      # a resource cap: the dense transform is cubic, its twiddle table lives in LDS
+
+
+def fsim_reduction(H, W):
+    """-> (F, h, w): F = max(1, round(min(H, W) / 256)) with MATLAB's round (383 -> 1, 384 -> 2); every plane is averaged over
+    F x F and rows and columns 0, F, 2F, .. are kept"""
+    F = max(1, int(np.floor(min(H, W) / 256.0 + 0.5)))
+    return F, -(-H // F), -(-W // F)
+
+
+def _fsim_check(H, W, reduce=True):
+    if min(H, W) < FSIM_MIN_SIDE:
+        raise ValueError(f"FSIM needs both sides >= {FSIM_MIN_SIDE}, got {H} x {W}")
+    h, w = fsim_reduction(H, W)[1:] if reduce else (H, W)
+    if max(h, w) > FSIM_MAX_REDUCED_SIDE:
+        raise ValueError(f"FSIM needs the reduced longer side <= {FSIM_MAX_REDUCED_SIDE}, got {h} x {w}")
+
+
+def phase_congruency(planes):
+    """planes (B, h, w) float64 CUDA tensor -> float64 (B, h, w) numpy: the phase congruency map FSIM weighs with.  ValueError for
+    a side below FSIM_MIN_SIDE or above FSIM_MAX_REDUCED_SIDE."""
+    from . import ops
+    assert planes.dim() == 3 and planes.shape[0] >= 1
+    _fsim_check(planes.shape[1], planes.shape[2], reduce=False)
+    return ops.fsim_phasecong(planes.contiguous()).cpu().numpy()
+
+
+def fsim(a_u8, b_u8):
+    """FSIM and FSIMc of B pairs: a_u8 (original), b_u8 (reconstruction) (B, H, W, 3) u8 CUDA tensors -> (fsim, fsimc), float64 (B,)
+    each; exactly 1 for equal images.  ValueError for images with a side below FSIM_MIN_SIDE or a reduced longer side above
+    FSIM_MAX_REDUCED_SIDE."""
+    import torch
+    from . import ops
+    assert a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.shape == b_u8.shape
+    assert a_u8.dim() == 4 and a_u8.shape[3] == 3 and a_u8.shape[0] >= 1
+    _fsim_check(a_u8.shape[1], a_u8.shape[2])
+    f, fc = ops.fsim(a_u8.contiguous(), b_u8.contiguous())
+    return f.cpu().numpy(), fc.cpu().numpy()
+
+
+def measure_fsim(a_u8, b_u8):
+    """-> {"fsim", "fsimc"}: float64 (B,), or None for both where fsim() refuses the size, as measure() does"""
+    try:
+        _fsim_check(a_u8.shape[1], a_u8.shape[2])
+    except ValueError:
+        return {"fsim": None, "fsimc": None}
+    f, fc = fsim(a_u8, b_u8)
+    return {"fsim": f, "fsimc": fc}
