@@ -140,7 +140,9 @@ def save_tile_cache(path=None):
             picks = json.load(f).get("picks", {})
     except (OSError, ValueError):
         pass
-    picks.update({"|".join(str(int(x)) if not isinstance(x, str) else x for x in k): int(v) for k, v in _TILE.items()})
+    # measured picks only: _remember enters a measurement into its family as well, _lookup leaves a borrowed pick in _TILE alone
+    picks.update({"|".join(str(int(x)) if not isinstance(x, str) else x for x in k): int(v) for k, v in _TILE.items()
+                  if k[1] in _FAMILY.get((k[0],) + tuple(k[2:]), ())})
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         tmp = f"{path}.{os.getpid()}.tmp"
@@ -163,7 +165,7 @@ def _lookup(key):
         M = key[1]
         near = min(fam, key=lambda x: abs(x - M))
         if M <= 2 * near and near <= 2 * M:
-            _TILE[key] = fam[near]          # not persisted: a borrowed pick, not a measurement
+            _TILE[key] = fam[near]          # a borrowed pick, not a measurement: tile_of reports it, save_tile_cache leaves it out
             return fam[near]
     return None
 
@@ -490,6 +492,9 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out=None, M=None, a_seg=(
     if bias is not None:
         assert bias.shape == (N,) and bias.is_contiguous()
     inplace = residual is not None and out is not None and out.data_ptr() == residual.data_ptr()
+    # the kernels read the residual by logical row and write the output through c_seg: in place these are the same rows only
+    # within the first segment -- beyond it a launch would read rows that other workgroups of the same launch write
+    assert not (inplace and c_seg[0] and M > c_seg[0]), "gemm: in-place residual through a c_seg row map of more than one segment"
 
     if use3:
         wp = weight_planes(w, ldw)
@@ -818,6 +823,10 @@ def conv3x3(x_halo, w, bias, B, H, W, Cin, Cout, residual=None, act=ACT_NONE, ou
     ldr = 0
     if residual is not None:
         residual, ldr = _rows(residual)
+        # the launch-mode race below runs the kernel many times over `out` and restores nothing (unlike gemm's in-place residual)
+        o0, r0, M = out.data_ptr(), residual.data_ptr(), B * H * W
+        assert o0 + ((M - 1) * ldc + Cout) * 4 <= r0 or r0 + ((M - 1) * ldr + Cout) * 4 <= o0, \
+            "conv3x3: out overlaps residual -- an in-place residual is not idempotent and the launch-mode race does not restore out"
 
     if conv_planes_ok(Cin, Cout, residual is not None, precision):
         # implicit split GEMM: the weight's planes are cached; the halo planes come from the producer, or from one split pass
